@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- block hot path throughput on MI355X (see DESIGN.md section "Measurement").
 
-  python bench.py --gpus N --steps K --warmup W [--workload enwik8|enwik9|...]
+  python bench.py --gpus N --steps K --warmup W [--workload enwik8|enwik9|...] [--dump-outputs DIR]
+
+--dump-outputs DIR writes the compressed blocks of the last timed step as DIR/*.npy (float32, under 64 MB: a seeded sample of
+larger outputs, see dump_outputs()); the inputs depend only on the arguments, so two builds can be compared file by file.
 
 A "step" = one pass of the compress hot path (forward BWT -> rANS encode, Jampack::Comp() tail, jampack.cpp:40-41)
 over one batch of 64 MiB blocks, inputs already resident in HBM.
@@ -38,9 +41,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# blocks in flight live on separate HIP streams; the ROCm default of 4 hardware queues serialises them beyond two
-# (tools/dec_scaling.py).  Must be set before the HIP runtime initialises (torch initialises it before our library loads).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 
 import numpy as np  # noqa: E402
 
@@ -123,7 +123,12 @@ def parse():
     ap.add_argument("--no-block-sizes", action="store_true", help="skip the per_block_size extra (1 / 64 / 256 MiB blocks)")
     ap.add_argument("--master-port", type=int, default=29511)
     ap.add_argument("--child-extras", action="store_true", help=argparse.SUPPRESS)     # internal: per_block_size + host_buffers in a fresh process
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed (the compressed blocks a caller receives) to DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_children(args) -> int:
@@ -664,6 +669,39 @@ def run_child_extras(args):
     return None
 
 
+DUMP_BUDGET_BYTES = 60 << 20          # what --dump-outputs writes in all, .npy headers included: below 64 MB
+DUMP_HEAD_BYTES = 64 << 10            # every block's first bytes (header, frequency tables) are kept whole
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir: str, blocks) -> dict:
+    """--dump-outputs: the compressed blocks of the last timed step (uint8 arrays, in the order a caller receives them) as float32
+    .npy files block_NNN.npy, and their sizes as float64 (compressed_sizes.npy).  If all bytes fit the budget every block is written
+    whole; otherwise block i keeps its first bytes and a share of the rest of the budget proportional to its size, at positions drawn
+    by a generator seeded with DUMP_SEED + i and sorted -- the same positions in every run whose block i has the same size."""
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = [len(b) for b in blocks]
+    room = (DUMP_BUDGET_BYTES - (len(blocks) + 1) * 128 - 8 * len(blocks)) // 4        # float32 elements once the headers are paid
+    files = {"compressed_sizes": np.asarray(sizes, dtype=np.float64)}
+    whole = sum(sizes) <= room
+    head = min(DUMP_HEAD_BYTES, room // (2 * max(len(blocks), 1)))
+    heads = [min(head, n) for n in sizes]
+    rest, tails = room - sum(heads), sum(sizes) - sum(heads)
+    for i, b in enumerate(blocks):
+        if whole:
+            keep = b
+        else:
+            h = heads[i]
+            m = rest * (len(b) - h) // tails if tails else 0
+            pos = np.sort(np.random.default_rng(DUMP_SEED + i).choice(len(b) - h, size=m, replace=False)) + h
+            keep = np.concatenate([b[:h], b[pos]])
+        files[f"block_{i:03d}"] = np.asarray(keep).astype(np.float32)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "blocks": len(blocks), "whole": bool(whole),
+            "bytes": int(sum(os.path.getsize(os.path.join(out_dir, n + ".npy")) for n in files))}
+
+
 def main():
     args = parse()
     if args.child_extras:
@@ -860,6 +898,14 @@ def main():
     value = job_bytes / 1e6 / (dt / args.steps)
 
     extra = {}
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: with a gather, rank 0's gathered blocks (file order in stream mode, rank-major
+        # otherwise); on one rank, the loop's own output buffers
+        if gathered[0] is not None:
+            outs = shard.assemble_in_block_order(gathered[0], nblocks_job) if stream_mode else [t for r in gathered[0] for t in r]
+        else:
+            outs = [d_out[i][: sizes[i]] for i in range(nblk)]
+        extra["dump_outputs"] = dump_outputs(args.dump_outputs, [t.cpu().numpy() for t in outs])
     if rank == 0 and world == 1 and not args.no_extras and blocks:
         # the workload variants first: the same loop, the same contexts, right behind the timed steps (before the extras that create contexts
         # and streams of their own: a later leg of this process measures 5-10 % lower, see child_extras)
@@ -1142,7 +1188,7 @@ def main():
                                  "frac": round((14.0 + c) * batch_bytes / 1e9 / (ms_per_step / 1e3) / 8000.0, 5), "one_block_at_a_time_ms": round(comp_ms, 3)}
         # per-kernel HIP-event timing (events recorded by the library on the launch stream) of one more compress pass
         # The extras below bring contexts of their own.  The loop's contexts (each with its stream and up to three encoder group
-        # streams) are closed first: HIP deals streams onto 32 hardware queues, a stream beyond that shares a queue, and a 12 ms
+        # streams) are closed first: HIP deals streams onto a fixed number of hardware queues, a stream beyond that shares a queue, and a 12 ms
         # chain kernel then blocks whatever sits behind it -- with the loop's twenty streams still alive the 8 MiB leg of
         # per_block_size measured 2.8 GB/s where a fresh process measures 3.6 (tools/small_blocks.py).
         pool.shutdown()

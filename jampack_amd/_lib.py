@@ -8,8 +8,6 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")   # see abi.hip: more than two blocks in flight need more HW queues
-
 HERE = os.path.dirname(os.path.abspath(__file__))
 # JPK_LIB=<path>: another build of the library for THIS process (tools/ab_*.sh alternate two builds on one box without touching the
 # product file in place)

@@ -73,7 +73,8 @@ def test_shim_headers_compile_against_reference_call_pattern(tmp_path):
     assert os.path.exists(os.path.join(ROOT, "jampack_amd", "csrc", "shim", "jam_block_pipeline"))
 
 
-REFERENCE = "/root/reference"
+# the reference tree the oracle recipe builds from (oracle/Makefile's REF, overridable the same way)
+REFERENCE = os.environ.get("REF") or re.search(r"^REF \?= *(\S+)", open(os.path.join(ROOT, "oracle", "Makefile")).read(), re.M).group(1)
 
 
 @pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree absent (GPU box)")

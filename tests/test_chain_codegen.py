@@ -20,9 +20,9 @@ HIPCC = "/opt/rocm/bin/hipcc"
 VMEM = re.compile(r"^\s*(global_|buffer_|scratch_|flat_)\w+")
 
 
-def kernel_body():
+def kernel_body(tmp_dir):
     src = os.path.join(ROOT, "jampack_amd", "csrc", "ans_enc.hip")
-    out = "/tmp/jpk_ans_enc_codegen.s"
+    out = os.path.join(str(tmp_dir), "ans_enc.s")
     subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-DJPK_BUILD", "--cuda-device-only", "-S", src, "-o", out],
                           stderr=subprocess.DEVNULL)
     text = open(out).read()
@@ -32,8 +32,8 @@ def kernel_body():
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not present")
-def test_the_encoder_chain_loop_issues_exactly_two_stores_and_one_load_per_batch():
-    body = kernel_body()
+def test_the_encoder_chain_loop_issues_exactly_two_stores_and_one_load_per_batch(tmp_path):
+    body = kernel_body(tmp_path)
     waits = [i for i, ln in enumerate(body) if re.search(r"s_waitcnt\s+vmcnt\(42\)", ln)]
     assert len(waits) == 16, f"expected the sixteen-fold unrolled steady-state loop, found {len(waits)} waits"
     # the loop: a label above the first wait that a branch below the last wait jumps back to
@@ -59,8 +59,8 @@ def test_the_encoder_chain_loop_issues_exactly_two_stores_and_one_load_per_batch
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not present")
-def test_no_record_is_loaded_into_registers_and_m0_is_ours():
-    body = kernel_body()
+def test_no_record_is_loaded_into_registers_and_m0_is_ours(tmp_path):
+    body = kernel_body(tmp_path)
     assert not [ln for ln in body if re.search(r"global_load_dwordx4\s+v", ln)], "a record load with a register destination is back"
     assert not [ln for ln in body if re.match(r"^\s*scratch_", ln)], "the chain kernel spills"
     # sixteen prologue loads + sixteen in the loop, all LDS-DMA; drained before the loop and before the wave releases its LDS

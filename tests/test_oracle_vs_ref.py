@@ -1,4 +1,4 @@
-"""Pins the C restatement against the real reference compiled from /root/reference (oracle/_ref).
+"""Pins the C restatement against the real reference, compiled by oracle/Makefile into oracle/_ref.
 Skipped when oracle/_ref/libjamref.so is absent.  CPU only."""
 import numpy as np
 import pytest

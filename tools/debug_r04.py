@@ -2,7 +2,6 @@
 """focused checks while the run-aware sort and the grouped compress path are being brought up (GPU box)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 import numpy as np, torch
 import jampack_amd as jam
 from oracle.pyoracle import Oracle

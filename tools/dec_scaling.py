@@ -3,7 +3,6 @@
 import os, sys, time
 import concurrent.futures as cf
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '16')
 import numpy as np, torch
 import jampack_amd as jam
 

@@ -9,7 +9,6 @@ threads per CU with ONE kind of work.  The slowdown per hog kind says what the s
    hipcc --offload-arch=gfx950 -O3 -shared -fPIC tools/hog.hip -o tools/_bin/libhog.so
    python tools/interfere.py [contexts=4] [wgs_per_cu=2]"""
 import ctypes, os, sys, threading, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")      # before the HIP runtime starts: the hog needs a hardware queue of its own
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import jampack_amd as jam

@@ -4,7 +4,6 @@ but rANS encodes of a resident image, for a fixed time; blocks per second of eac
 (and the other way round) when neither waits for the other:   python tools/mix_stages.py [seconds] [NF,NE ...]"""
 import os, sys, time, threading
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 import numpy as np, torch
 import jampack_amd as jam
 

@@ -3,7 +3,6 @@
 honours the JPK_PAIR_* knobs:   python tools/real_fwd.py [reps] [sources|binaries[:<skip MiB>]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '16')
 import torch
 import jampack_amd as jam
 from jampack_amd import corpus

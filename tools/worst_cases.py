@@ -2,7 +2,6 @@
 """stage times on adversarial 64 MiB blocks (run on the GPU box)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np, torch
 import jampack_amd as jam
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64 << 20
