@@ -228,6 +228,42 @@ JPK_API int jpk_dev_blocks_decompress(jpk_ctx *ctx, int32_t nblocks, const uint8
 JPK_API int jpk_dev_blocks_compress(jpk_ctx *ctx, int32_t nblocks, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                             const int32_t *out_cap, int32_t *out_len, int32_t *status, int32_t in_flight);
 
+/* ---- whole .jam archives (Jampack::Compress / Jampack::Decompress, jampack.cpp:186-336) ---------------------------------------- */
+/* Checksum::IntegrityCheck of n device segments (any length 0 .. 2^31 - 1, any start address) in one launch pair; crc[i] (host
+ * array) receives segment i's checksum.  jpk_dev_checksum is the batch of one. */
+JPK_API int jpk_dev_checksums(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint32_t *crc);
+/* the largest archive in_len bytes can produce with this block size (0 for in_len 0); JPK_E_ARG (< 0) for a bad argument */
+JPK_API int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size);
+/* The archive of `jampack c` (frames of the block path, no LZ77 / LPX / filter pre-stages): bytes identical to the concatenation of
+ * jpk_dev_jam_block_write over consecutive block_size slices of d_in, the last one short; in_len == 0 gives an empty archive.
+ * block_size in [JPK_MIN_BLOCKSIZE, JPK_MAX_BLOCKSIZE].  Runs through jpk_dev_blocks_compress (in_flight as there: worker contexts,
+ * blocks in flight, groups of small blocks): per pass one batched checksum of the slices, the batch compress into payload slots, one
+ * pack launch that writes the frames.  JPK_E_CAPACITY when the archive does not fit out_cap (jpk_jam_compress_bound always does).
+ * Per-pass HBM: passes of at most 128 frames and 4 GiB of input; the slots take jpk_jam_compress_bound of the pass (about 1.25 bytes
+ * per input byte, <= 5.2 GB) in a scratch buffer of ctx, on top of the workers' arenas of jpk_dev_blocks_compress. */
+JPK_API int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                 int32_t in_flight);
+/* The inverse (Jampack::Decompress, jampack.cpp:262-336, without pre-stages): a frame walk over the whole archive with the checks of
+ * DecompReadBlock (jampack.cpp:140-163: magic, BlockSize range, 0 <= payload size <= MAX_BLOCKSIZE, the payload inside the archive;
+ * 1..14 trailing bytes are a bad frame), every payload's decoded size from its chunk headers (at least the BWT trailer, at most
+ * BlockSize raw bytes), then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out and one batched checksum
+ * compared with the header crcs.
+ *   out_cap too small: JPK_E_CAPACITY, *out_len = the bytes needed, nothing written (out_cap = 0 is the size query).
+ *   bad frame k (header, payload or crc): its status (JPK_E_CORRUPT), *bad_frame = k, *frames = k, *out_len = the raw bytes of frames
+ *   0..k-1, which are verified and in place; bytes past them are unspecified (the reference stops at the first corrupt block).
+ *   success: *frames = the frame count, *bad_frame = -1.  frames and bad_frame may be NULL.
+ * Per-pass HBM: passes of at most 128 frames and 4 GiB of raw bytes; the batch decoder's arena on ctx takes about 4 bytes per raw byte
+ * of the pass (the BWT images, the rank arrays, the RLE0 symbols) plus the inverse BWT's scratch (jpk_dev_blocks_decompress). */
+JPK_API int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                   int32_t *bad_frame);
+/* host-buffer forms of the two: staged one pass at a time through the calling thread's pooled context, same contracts */
+JPK_API int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight);
+JPK_API int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame);
+/* host walk of an archive in host memory with the checks of jpk_dev_jam_decompress's walk (the decoded sizes by jpk_ans_decoded_size):
+ * *frames / *raw_len = count and exact raw bytes of the frames in front of the first bad one, *bad_frame = its index (JPK_E_CORRUPT)
+ * or -1 (JPK_OK).  No device call.  Pointers other than in may be NULL. */
+JPK_API int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame);
+
 /* ---- kernel-level probes used by tests/ and bench.py (device buffers) ------------------------------------ */
 /* Comparator for BASELINE config 3 ("120-way parallel LF-map"): the reference's own GPU kernel shape -- 120 threads, one per
  * stored index, p = Map[p-1] (CUDAInverse<<<40,3>>>, bwt.cpp:8-19, 176-183, 226-229) -- on the same Map.  Same bytes as

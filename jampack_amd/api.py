@@ -176,28 +176,44 @@ def jam_block_read(stream, cap: int):
     return out[: n.value], used.value
 
 
+def jam_compress_bound(n: int, block_size: int = 8 << 20) -> int:
+    """jpk_jam_compress_bound: the largest archive n input bytes can give with this block size"""
+    b = int(lib().jpk_jam_compress_bound(n, block_size))
+    _chk(b if b < 0 else 0, "jpk_jam_compress_bound")
+    return b
+
+
 def jam_compress(data, block_size: int = 8 << 20) -> np.ndarray:
     """Jampack::Compress's block loop (jampack.cpp:186-254) over an in-memory buffer: consecutive frames of
-    block_size input bytes (DEFAULT_BLOCKSIZE 8 MiB, format.hpp:20)."""
+    block_size input bytes (DEFAULT_BLOCKSIZE 8 MiB, format.hpp:20), made by one jpk_jam_compress call (the batch engine)."""
     t = _np_u8(data)
-    frames = [jam_block_write(t[o: o + block_size], block_size) for o in range(0, len(t), block_size)]
-    return np.concatenate(frames) if frames else np.zeros(0, dtype=np.uint8)
+    out = np.empty(max(jam_compress_bound(len(t), block_size), 1), dtype=np.uint8)
+    n = C.c_int64(0)
+    _chk(lib().jpk_jam_compress(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0), "jam_compress")
+    return out[: n.value]
+
+
+def jam_frames(stream):
+    """jpk_jam_frames: host walk of an archive -> (frames, raw bytes, bad frame or -1) of the frames in front of the first bad one"""
+    c = _np_u8(stream)
+    k, raw, bad = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+    rc = lib().jpk_jam_frames(_ptr(c), len(c), C.byref(k), C.byref(raw), C.byref(bad))
+    if rc not in (0, -3):
+        raise JampackError(rc, "jpk_jam_frames")
+    return k.value, raw.value, bad.value
 
 
 def jam_decompress(stream) -> np.ndarray:
-    """Jampack::Decompress's block loop (jampack.cpp:262-336): frames until the stream ends."""
+    """Jampack::Decompress's block loop (jampack.cpp:262-336): frames until the stream ends, decoded by one jpk_jam_decompress call.
+    Raises JampackError(-3) on the first corrupt frame."""
     c = _np_u8(stream)
-    out, o = [], 0
-    while o < len(c):
-        if len(c) - o < JAM_HEADER:
-            raise JampackError(-3, "jam_decompress: truncated header")
-        bs = int(np.frombuffer(c[o + 11: o + 15].tobytes(), dtype="<i4")[0])
-        if not (MIN_BLOCKSIZE <= bs <= MAX_BLOCKSIZE):
-            raise JampackError(-3, "jam_decompress: Refusing to read from corrupt header!")
-        blk, used = jam_block_read(c[o:], bs)
-        out.append(blk)
-        o += used
-    return np.concatenate(out) if out else np.zeros(0, dtype=np.uint8)
+    k, raw, bad = jam_frames(c)
+    if bad >= 0:
+        raise JampackError(-3, f"jam_decompress: corrupt frame {bad}")
+    out = np.empty(max(raw, 1), dtype=np.uint8)
+    n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+    _chk(lib().jpk_jam_decompress(_ptr(c), len(c), out.ctypes.data, raw, C.byref(n), C.byref(nf), C.byref(bf)), "jam_decompress")
+    return out[: n.value]
 
 
 class Lz77:
@@ -381,6 +397,30 @@ class Context:
         n, used = C.c_int32(0), C.c_int32(0)
         _chk(lib().jpk_dev_jam_block_read(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(used)), "jpk_dev_jam_block_read")
         return n.value, used.value
+
+    def checksums(self, d_ins, in_lens):
+        """jpk_dev_checksums: Checksum::IntegrityCheck of device segments in one launch pair -> list of crcs"""
+        n = len(d_ins)
+        P, I = C.c_void_p * max(n, 1), C.c_int32 * max(n, 1)
+        crc = (C.c_uint32 * max(n, 1))()
+        _chk(lib().jpk_dev_checksums(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*in_lens), crc), "jpk_dev_checksums")
+        return list(crc)[:n]
+
+    def jam_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0) -> int:
+        """jpk_dev_jam_compress: the whole archive of d_in[0..in_len) into d_out; returns its length"""
+        n = C.c_int64(0)
+        _chk(lib().jpk_dev_jam_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_compress")
+        return n.value
+
+    def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):
+        """jpk_dev_jam_decompress -> (raw bytes, frames, bad frame); check=False: (raw bytes, frames, bad frame, status), no exception
+        (out_len is the bytes needed on JPK_E_CAPACITY, the verified bytes in front of the bad frame on JPK_E_CORRUPT)"""
+        n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+        rc = lib().jpk_dev_jam_decompress(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf))
+        if not check:
+            return n.value, nf.value, bf.value, int(rc)
+        _chk(rc, "jpk_dev_jam_decompress")
+        return n.value, nf.value, bf.value
 
     def rank_encode(self, d_t, d_freq, n):
         _chk(lib().jpk_dev_rank_encode(self._h, _dptr(d_t), _dptr(d_freq), n), "jpk_dev_rank_encode")

@@ -161,7 +161,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_rs_hist/k_os_digits", "k_rs_scatter/k_os_scatter", "k_scan_*/k_tab_*/k_win_*", "k_gather_win", "k_seg_round", "k_r0_*/k_lg_finish/k_cmp_*", "k_bwt_image",
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
-    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys"};
+    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {
@@ -251,6 +251,7 @@ extern "C" void jpk_ctx_destroy(jpk_ctx *c)
     if (c->stage_in) (void)hipFree(c->stage_in);
     if (c->stage_out) (void)hipFree(c->stage_out);
     if (c->stage_res) (void)hipFree(c->stage_res);
+    if (c->jam_scratch) (void)hipFree(c->jam_scratch);
     if (c->d_mail) (void)hipFree(c->d_mail);
     if (c->h_mail) (void)hipHostFree(c->h_mail);
     if (c->h_map) (void)hipHostFree(c->h_map);
@@ -1905,5 +1906,318 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
     if (jpk_checksum_host(out, m) != crc) return JPK_E_CORRUPT;                              // "Detected corrupt block!"
     *out_len = m;
     if (consumed) *consumed = csize + JPK_JAM_HEADER_BYTES;
+    return JPK_OK;
+}
+
+// ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
+// Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
+// in ctx->jam_scratch, the frame offsets on the host (64-bit), one k_jam_pack launch that writes the frames.  Decompress: the frame
+// walk (k_jam_walk, one launch + one read-back per JPK_JAM_PASS_FRAMES frames) and the decoded sizes (pass 1 of the batch decoder)
+// over the whole archive first -- that is what makes the capacity answer exact and leaves d_out untouched when it is too small --
+// then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out (its payload read in place in the archive),
+// one batched checksum of the outputs, and the comparison with the header crcs.  A pass holds at most JPK_JAM_PASS_FRAMES frames
+// and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
+namespace {
+constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
+
+int jam_pass_frames(int32_t block_size)
+{
+    const uint64_t k = JAM_PASS_RAW / (uint64_t)block_size;
+    return k < (uint64_t)JPK_JAM_PASS_FRAMES ? (int)k : JPK_JAM_PASS_FRAMES;
+}
+
+// one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
+struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
+
+// the checks of the frame walk beyond its header (k_jam_walk / jam_walk_host): the payload declares at least the BWT trailer and at
+// most BlockSize raw bytes (the reference decodes into buffers of 1.05 x BlockSize, jampack.cpp:156-159)
+bool jam_decoded_ok(int64_t decoded, int32_t block_size) { return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= block_size; }
+
+// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none)
+void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad)
+{
+    *bad = -1;
+    int64_t o = 0;
+    while (o < in_len) {
+        const int32_t k = (int32_t)fr.size();
+        if (in_len - o < JPK_JAM_HEADER_BYTES) { *bad = k; return; }       // 1..14 trailing bytes
+        JamFrame f;
+        memcpy(&f.crc, in + o + 3, 4);
+        memcpy(&f.psize, in + o + 7, 4);
+        memcpy(&f.block_size, in + o + 11, 4);
+        // DecompReadBlock, jampack.cpp:140-163
+        if (memcmp(in + o, "JAM", 3) != 0 || !jam_block_size_ok(f.block_size) || f.psize < 0 || f.psize > JPK_MAX_BLOCKSIZE ||
+            (int64_t)f.psize > in_len - o - JPK_JAM_HEADER_BYTES) { *bad = k; return; }
+        f.payload_off = o + JPK_JAM_HEADER_BYTES;
+        int64_t decoded = 0;
+        if (jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size)) { *bad = k; return; }
+        f.raw = decoded - JPK_TRAILER_BYTES;
+        fr.push_back(f);
+        o = f.payload_off + f.psize;
+    }
+}
+
+// the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
+int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad)
+{
+    *bad = -1;
+    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
+    JamWalkFrame *d_tab = reinterpret_cast<JamWalkFrame *>(ctx->jam_scratch);
+    std::vector<JamWalkFrame> h(JPK_JAM_PASS_FRAMES);
+    std::vector<const uint8_t *> ins;
+    std::vector<int32_t> lens, st;
+    std::vector<int64_t> dec;
+    uint64_t o = 0;
+    while (o < (uint64_t)in_len) {
+        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail));
+        JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
+        uint32_t m[4];
+        JPK_TRY(jpk_read_mail(ctx, m, 4));                   // synchronises: the table is on the host too
+        const int n = (int)m[0];
+        ins.resize((size_t)n); lens.resize((size_t)n); st.resize((size_t)n); dec.resize((size_t)n);
+        for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
+        JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
+        for (int i = 0; i < n; i++) {
+            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], h[i].block_size)) { *bad = (int32_t)fr.size(); return JPK_OK; }
+            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, h[i].block_size, dec[i] - JPK_TRAILER_BYTES});
+        }
+        if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
+        o = ((uint64_t)m[3] << 32) | m[2];
+    }
+    return JPK_OK;
+}
+
+// frames [k, e) of fr form the pass that starts at frame k: at most JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW raw bytes (one at least)
+size_t jam_pass_end(const std::vector<JamFrame> &fr, size_t k)
+{
+    size_t e = k;
+    uint64_t raw = 0;
+    while (e < fr.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || raw + (uint64_t)fr[e].raw <= JAM_PASS_RAW)) raw += (uint64_t)fr[e++].raw;
+    return e;
+}
+
+// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len)
+int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
+                      int32_t in_flight)
+{
+    const int n = (int)((len + block_size - 1) / block_size);
+    std::vector<const uint8_t *> ins((size_t)n);
+    std::vector<uint8_t *> slots((size_t)n);
+    std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+    const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
+    size_t need = o_slots;
+    for (int i = 0; i < n; i++) {
+        ins[i] = d_in + (int64_t)i * block_size;
+        lens[i] = (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size);
+        caps[i] = (int32_t)multi_comp_cap(lens[i]);
+        need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
+    }
+    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(ctx->jam_scratch + o_frames);
+    size_t off = o_slots;
+    for (int i = 0; i < n; i++) { slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64); }
+    // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
+    JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
+    JPK_TRY(jpk_dev_blocks_compress(ctx, n, ins.data(), lens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
+    for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
+    std::vector<JamPackFrame> fr((size_t)n);
+    uint64_t pos = 0;
+    for (int i = 0; i < n; i++) {
+        fr[i].slot = slots[i]; fr[i].off = pos; fr[i].psize = outl[i]; fr[i].pad = 0;
+        pos += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)outl[i];
+    }
+    if ((int64_t)pos > out_room) return JPK_E_CAPACITY;
+    JPK_HIP(hipMemcpyAsync(d_frames, fr.data(), (size_t)n * sizeof(JamPackFrame), hipMemcpyHostToDevice, ctx->stream));
+    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, block_size, d_out, pos));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    *pass_len = (int64_t)pos;
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_checksums(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint32_t *crc)
+{
+    JPK_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !crc))) return JPK_E_ARG;
+    for (int i = 0; i < n; i++) if (in_len[i] < 0 || (in_len[i] > 0 && !d_in[i])) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)n * 4));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    JPK_TRY(jpk_checksums_device(ctx, n, d_in, in_len, d_crc));
+    JPK_HIP(hipMemcpyAsync(crc, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    return JPK_OK;
+}
+
+extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size)
+{
+    if (in_len < 0 || !jam_block_size_ok(block_size)) return JPK_E_ARG;
+    const int64_t full = in_len / block_size, rest = in_len % block_size;
+    return full * (JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap(block_size)) + (rest ? JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap((int32_t)rest) : 0);
+}
+
+extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                    int32_t in_flight)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out))) return JPK_E_ARG;
+    if (!jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
+    *out_len = 0;
+    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
+    int64_t pos = 0;
+    for (int64_t o = 0; o < in_len; o += step) {
+        int64_t n = 0;
+        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight));
+        pos += n;
+    }
+    *out_len = pos;
+    return JPK_OK;
+}
+
+extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                      int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    *out_len = 0;
+    if (frames) *frames = 0;
+    if (bad_frame) *bad_frame = -1;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
+    int64_t need = 0;
+    for (const JamFrame &f : fr) need += f.raw;
+    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }         // the size query (out_cap = 0) ends here
+    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * 4));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k);
+        const int n = (int)(e - k);
+        std::vector<const uint8_t *> ins((size_t)n);
+        std::vector<uint8_t *> outs((size_t)n);
+        std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+        std::vector<uint32_t> crc((size_t)n);
+        int64_t o = pos;
+        for (int i = 0; i < n; i++) {
+            const JamFrame &f = fr[k + i];
+            ins[i] = d_in + f.payload_off; lens[i] = f.psize;
+            outs[i] = d_out + o; caps[i] = (int32_t)f.raw;
+            o += f.raw;
+        }
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
+        int fail = n, rc = JPK_OK;
+        for (int i = 0; i < n && fail == n; i++) if (st[i] != JPK_OK || outl[i] != caps[i]) { fail = i; rc = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; }
+        if (fail > 0) {
+            JPK_TRY(jpk_checksums_device(ctx, fail, outs.data(), caps.data(), d_crc));
+            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, (size_t)fail * 4, hipMemcpyDeviceToHost, ctx->stream));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            for (int i = 0; i < fail; i++) if (crc[i] != fr[k + i].crc) { fail = i; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
+        }
+        for (int i = 0; i < fail; i++) pos += caps[i];
+        if (fail < n) {
+            *out_len = pos;
+            if (frames) *frames = (int32_t)(k + fail);
+            if (bad_frame) *bad_frame = (int32_t)(k + fail);
+            return rc;
+        }
+        k = e;
+    }
+    *out_len = pos;
+    if (frames) *frames = (int32_t)fr.size();
+    if (bad >= 0) {
+        if (bad_frame) *bad_frame = bad;
+        return JPK_E_CORRUPT;
+    }
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame)
+{
+    if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad);
+    int64_t raw = 0;
+    for (const JamFrame &f : fr) raw += f.raw;
+    if (frames) *frames = (int32_t)fr.size();
+    if (raw_len) *raw_len = raw;
+    if (bad_frame) *bad_frame = bad;
+    return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
+}
+
+extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out))) return JPK_E_ARG;
+    if (!jam_block_size_ok(block_size)) return JPK_E_ARG;
+    *out_len = 0;
+    jpk_ctx *ctx;
+    JPK_TRY(tls_ctx(&ctx));
+    JPK_HIP(hipSetDevice(ctx->device));
+    // staged one pass at a time: the device call makes the same passes, so the frames are those of one call over the whole input
+    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
+    int64_t pos = 0;
+    for (int64_t o = 0; o < in_len; o += step) {
+        const int64_t len = std::min(step, in_len - o), bound = jpk_jam_compress_bound(len, block_size);
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 64));
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
+        int64_t n = 0;
+        JPK_TRY(jpk_dev_jam_compress(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight));
+        if (n > out_cap - pos) return JPK_E_CAPACITY;
+        JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        pos += n;
+    }
+    *out_len = pos;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    *out_len = 0;
+    if (frames) *frames = 0;
+    if (bad_frame) *bad_frame = -1;
+    jpk_ctx *ctx;
+    JPK_TRY(tls_ctx(&ctx));
+    JPK_HIP(hipSetDevice(ctx->device));
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad);
+    int64_t need = 0;
+    for (const JamFrame &f : fr) need += f.raw;
+    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }
+    // staged one pass at a time: the pass's frames are an archive of their own for the device call
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k);
+        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+        int64_t raw = 0;
+        for (size_t i = k; i < e; i++) raw += fr[i].raw;
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)raw + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+        int64_t n = 0;
+        int32_t nf = 0, bf = -1;
+        const int rc = jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, raw, &n, &nf, &bf);
+        if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        if (rc != JPK_OK) {
+            if (rc == JPK_E_CORRUPT) *out_len = pos + n;
+            if (frames) *frames = (int32_t)k + nf;
+            if (bad_frame && bf >= 0) *bad_frame = (int32_t)k + bf;
+            return rc;
+        }
+        pos += n;
+        k = e;
+    }
+    *out_len = pos;
+    if (frames) *frames = (int32_t)fr.size();
+    if (bad >= 0) {
+        if (bad_frame) *bad_frame = bad;
+        return JPK_E_CORRUPT;
+    }
     return JPK_OK;
 }

@@ -840,6 +840,57 @@ __global__ __launch_bounds__(64) void k_dec_rank(const DecBlock *__restrict__ bl
 
 }  // namespace
 
+namespace {
+// pass 1 of the batch: the block table goes to the head of the arena (behind arena_skip), one k_dec_headers<false> wave per block
+// counts the chunks and totals the sizes; mail[8 b ..] comes back to the host (synchronises the stream)
+int dec_count_pass(jpk_ctx *ctx, const std::vector<DecBlock> &hb, size_t arena_skip, std::vector<uint32_t> &mail)
+{
+    const int nblk = (int)hb.size();
+    hipStream_t st = ctx->stream;
+    const size_t tab_bytes = jpk_align((size_t)nblk * sizeof(DecBlock) + 64), mail_bytes = jpk_align((size_t)nblk * 8 * 4 + 64);
+    if (arena_skip && !jpk_arena_fits(ctx, arena_skip + tab_bytes + mail_bytes + 4096)) return JPK_E_ALLOC;
+    JPK_TRY(jpk_arena_ensure(ctx, arena_skip + tab_bytes + mail_bytes + 4096));
+    DecBlock *d_tab = reinterpret_cast<DecBlock *>(ctx->arena + arena_skip);
+    uint32_t *d_mail = reinterpret_cast<uint32_t *>(ctx->arena + arena_skip + tab_bytes);
+    JPK_HIP(hipMemcpyAsync(d_tab, hb.data(), (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice, st));
+    JPK_LAUNCH(ctx, PROF_DEC_HEADERS, 0, (k_dec_headers<false>), dim3(nblk), dim3(64), d_tab, (ChunkInfo *)nullptr, (int32_t *)nullptr, d_mail);
+    JPK_HIP(hipGetLastError());
+    mail.assign((size_t)nblk * 8, 0u);
+    JPK_HIP(hipMemcpyAsync(mail.data(), d_mail, mail.size() * 4, hipMemcpyDeviceToHost, st));
+    JPK_HIP(hipStreamSynchronize(st));
+    if (ctx->prof_on) jpk_prof_resolve(ctx);
+    return JPK_OK;
+}
+
+DecBlock dec_block(const uint8_t *in, int32_t in_len, uint64_t out_cap)
+{
+    DecBlock b;
+    memset(&b, 0, sizeof(DecBlock));
+    b.in = in;
+    b.in_len = in_len;
+    b.out_cap = out_cap;
+    b.max_chunks = (uint32_t)in_len / 275u + 2u;      // a chunk is >= 259 header bytes + 16 state bytes
+    return b;
+}
+}  // namespace
+
+// the decoded size of each of nblk Ans streams from pass 1 of the batch decoder alone (no capacity applies): decoded[b], or
+// status[b] = JPK_E_CORRUPT where the chunk headers are malformed
+int jpk_ans_decoded_sizes(jpk_ctx *ctx, int nblk, const uint8_t *const *d_in, const int32_t *in_len, int64_t *decoded, int32_t *status)
+{
+    if (nblk <= 0) return JPK_OK;
+    std::vector<DecBlock> hb((size_t)nblk);
+    for (int b = 0; b < nblk; b++) hb[b] = dec_block(d_in[b], in_len[b], ~0ull);
+    std::vector<uint32_t> mail;
+    JPK_TRY(dec_count_pass(ctx, hb, 0, mail));
+    for (int b = 0; b < nblk; b++) {
+        const uint32_t *m = &mail[(size_t)b * 8];
+        status[b] = (int32_t)m[0];
+        decoded[b] = status[b] == JPK_OK ? (int64_t)(((uint64_t)m[3] << 32) | m[2]) : 0;
+    }
+    return JPK_OK;
+}
+
 // Ans::Decode of `nblk` independent blocks in one pass: header walk (count), buffers, header walk (fill), then ONE grid per
 // serial kernel over the chunks of all blocks.  status[b] = JPK_OK / JPK_E_CORRUPT / JPK_E_CAPACITY per block; a corrupt block
 // does not stop the others.  arena_skip: bytes at the start of the arena the caller keeps for itself.
@@ -851,25 +902,14 @@ int jpk_ans_decode_batch(jpk_ctx *ctx, int nblk, const uint8_t *const *d_in, con
     for (int b = 0; b < nblk; b++) {
         out_len[b] = 0;
         status[b] = JPK_OK;
-        memset(&hb[b], 0, sizeof(DecBlock));
-        hb[b].in = d_in[b];
-        hb[b].in_len = in_len[b];
-        hb[b].out_cap = (uint64_t)out_cap[b];
-        hb[b].max_chunks = (uint32_t)in_len[b] / 275u + 2u;      // a chunk is >= 259 header bytes + 16 state bytes
+        hb[b] = dec_block(d_in[b], in_len[b], (uint64_t)out_cap[b]);
     }
     // ---- pass 1: count the chunks, total the sizes ----
     const size_t tab_bytes = jpk_align((size_t)nblk * sizeof(DecBlock) + 64), mail_bytes = jpk_align((size_t)nblk * 8 * 4 + 64);
-    if (arena_skip && !jpk_arena_fits(ctx, arena_skip + tab_bytes + mail_bytes + 4096)) return JPK_E_ALLOC;
-    JPK_TRY(jpk_arena_ensure(ctx, arena_skip + tab_bytes + mail_bytes + 4096));
-    DecBlock *d_tab = reinterpret_cast<DecBlock *>(ctx->arena + arena_skip);
-    uint32_t *d_mail = reinterpret_cast<uint32_t *>(ctx->arena + arena_skip + tab_bytes);
-    JPK_HIP(hipMemcpyAsync(d_tab, hb.data(), (size_t)nblk * sizeof(DecBlock), hipMemcpyHostToDevice, st));
-    JPK_LAUNCH(ctx, PROF_DEC_HEADERS, 0, (k_dec_headers<false>), dim3(nblk), dim3(64), d_tab, (ChunkInfo *)nullptr, (int32_t *)nullptr, d_mail);
-    JPK_HIP(hipGetLastError());
-    std::vector<uint32_t> mail((size_t)nblk * 8);
-    JPK_HIP(hipMemcpyAsync(mail.data(), d_mail, mail.size() * 4, hipMemcpyDeviceToHost, st));
-    JPK_HIP(hipStreamSynchronize(st));
-    if (ctx->prof_on) jpk_prof_resolve(ctx);
+    std::vector<uint32_t> mail;
+    JPK_TRY(dec_count_pass(ctx, hb, arena_skip, mail));
+    DecBlock *d_tab;
+    uint32_t *d_mail;
     uint64_t nch_total = 0, rle_total = 0, out_total = 0;
     std::vector<uint64_t> tot_out((size_t)nblk), tot_rle((size_t)nblk);
     std::vector<uint32_t> nchb((size_t)nblk);

@@ -34,7 +34,7 @@ enum JpkProfId {
     PROF_RS_HIST = 0, PROF_RS_SCATTER, PROF_SCAN, PROF_SA_KEYS, PROF_SA_SEG, PROF_SA_RERANK, PROF_BWT_GATHER,
     PROF_INV_HIST, PROF_INV_BUILD, PROF_INV_WALK, PROF_INV_RANK, PROF_INV_COPY,
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
-    PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_COUNT
+    PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 
@@ -71,6 +71,9 @@ struct jpk_ctx {
     // persistent staging buffers for the host-buffer entry points
     uint8_t *stage_in = nullptr, *stage_out = nullptr, *stage_res = nullptr;
     size_t stage_in_cap = 0, stage_out_cap = 0, stage_res_cap = 0;
+    // the archive calls (jpk_dev_jam_compress / _decompress): crcs, frame tables and payload slots of one pass
+    uint8_t *jam_scratch = nullptr;
+    size_t jam_scratch_cap = 0;
     jpk_stats stats;
     // profiler
     bool prof_on = false;
@@ -207,3 +210,19 @@ int jpk_rank_decode_device(jpk_ctx *ctx, uint8_t *d_r, const int32_t *d_freq, in
 int jpk_rle_encode_device(jpk_ctx *ctx, const uint8_t *d_ranks, int32_t len, uint16_t *d_rle, int32_t *rlen);
 int jpk_model_pairs_device(jpk_ctx *ctx, const uint16_t *d_rle, int32_t rlen, uint32_t *d_pairs);
 int jpk_checksum_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint32_t *d_result);
+// n segments in one pair of launches, crc i -> d_result[i] (device); synchronises the stream when n > 1
+int jpk_checksums_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *len, uint32_t *d_result);
+// pass 1 of jpk_ans_decode_batch alone: the decoded bytes each Ans stream's chunk headers declare (status[b] != JPK_OK: corrupt);
+// synchronises the stream
+int jpk_ans_decoded_sizes(jpk_ctx *ctx, int nblk, const uint8_t *const *d_in, const int32_t *in_len, int64_t *decoded, int32_t *status);
+// .jam archives (jam.hip).  One frame of the walk: where its payload starts, its header fields
+struct JamWalkFrame { uint64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int32_t pad; };
+// one wave walks up to max_frames frame headers of d_in[0..in_len) from `start`: table[0..count); mail[0] = count, mail[1] = 1 when
+// the walk stopped at a bad frame (index count), mail[2..3] = offset where it stopped.  Enqueued only.
+int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
+                         uint32_t *d_mail);
+// one frame of the pack: its payload slot, its offset in the pass's output, its payload size
+struct JamPackFrame { const uint8_t *slot; uint64_t off; int32_t psize; int32_t pad; };
+constexpr int JPK_JAM_PASS_FRAMES = 128;                     // frames per pass of the archive calls (and per pack launch)
+// writes the frames d_frames[0..n) (n <= JPK_JAM_PASS_FRAMES), headers from d_crc[i] / psize / block_size, into d_out[0..total).  Enqueued.
+int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, const uint32_t *d_crc, int32_t block_size, uint8_t *d_out, uint64_t total);

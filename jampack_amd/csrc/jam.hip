@@ -1,0 +1,161 @@
+// jam.hip -- the frames of a .jam archive on gfx950 (Jampack::Compress / Decompress, jampack.cpp:186-336):
+//   k_jam_walk   one wave walks the frame headers of an archive in HBM (DecompReadBlock's checks, jampack.cpp:140-163)
+//   k_jam_pack   writes a run of frames -- "JAM" | u32 crc | i32 payload size | i32 BlockSize | payload, little-endian --
+//                from payload slots in scratch, organised by destination: a thread owns aligned 16-byte words of the output
+// The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress (abi.hip).
+#include "common.hpp"
+
+namespace {
+
+constexpr int PACK_TB = 256;
+
+// One wave.  A frame's 15 header bytes are loaded by lanes 0..14 at once; the chain of frames is serial by format (frame k + 1 starts
+// behind frame k's payload).  A frame is accepted as DecompReadBlock accepts it: magic "JAM", MIN_BLOCKSIZE <= BlockSize <=
+// MAX_BLOCKSIZE, 0 <= payload size <= MAX_BLOCKSIZE, and the payload ends inside the archive; 1..14 bytes left over are a bad frame too.
+__global__ __launch_bounds__(64) void k_jam_walk(const uint8_t *__restrict__ in, uint64_t in_len, uint64_t start, uint32_t max_frames,
+                                                 JamWalkFrame *__restrict__ table, uint32_t *__restrict__ mail)
+{
+    const int l = (int)(threadIdx.x & 63u);
+    uint64_t o = start;
+    uint32_t count = 0, bad = 0;
+    while (count < max_frames && o < in_len) {
+        if (in_len - o < (uint64_t)JPK_JAM_HEADER_BYTES) { bad = 1; break; }
+        const int mine = (l < JPK_JAM_HEADER_BYTES) ? (int)in[o + (uint64_t)l] : 0;
+        uint32_t h[JPK_JAM_HEADER_BYTES];
+#pragma unroll
+        for (int j = 0; j < JPK_JAM_HEADER_BYTES; j++) h[j] = (uint32_t)__builtin_amdgcn_readlane(mine, j);
+        const uint32_t crc = h[3] | (h[4] << 8) | (h[5] << 16) | (h[6] << 24);
+        const int32_t psize = (int32_t)(h[7] | (h[8] << 8) | (h[9] << 16) | (h[10] << 24));
+        const int32_t bs = (int32_t)(h[11] | (h[12] << 8) | (h[13] << 16) | (h[14] << 24));
+        if (h[0] != 'J' || h[1] != 'A' || h[2] != 'M' || bs < JPK_MIN_BLOCKSIZE || bs > JPK_MAX_BLOCKSIZE || psize < 0 || psize > JPK_MAX_BLOCKSIZE ||
+            (uint64_t)psize > in_len - o - JPK_JAM_HEADER_BYTES) { bad = 1; break; }
+        if (l == 0) {
+            JamWalkFrame f;
+            f.payload_off = o + JPK_JAM_HEADER_BYTES; f.psize = psize; f.crc = crc; f.block_size = bs; f.pad = 0;
+            table[count] = f;
+        }
+        o += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)psize;
+        count++;
+    }
+    if (l == 0) {
+        mail[0] = count;
+        mail[1] = bad;
+        mail[2] = (uint32_t)o;
+        mail[3] = (uint32_t)(o >> 32);
+    }
+}
+
+// 16 bytes from src (any alignment) through two aligned 16-byte loads: the slot has at least 16 bytes of padding behind its payload
+__device__ __forceinline__ uint4 load16_unaligned(const uint8_t *src)
+{
+    const uintptr_t a = (uintptr_t)src;
+    const uint4 *p = reinterpret_cast<const uint4 *>(a & ~(uintptr_t)15);
+    const uint32_t sh = (uint32_t)(a & 15u);
+    const uint4 x = p[0];
+    if (sh == 0) return x;
+    const uint4 y = p[1];
+    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    const uint32_t q = sh >> 2, r = sh & 3u;
+    uint32_t v[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {               // v[i] = w[q + i] by selects (q <= 3): no indexed register array
+        uint32_t t = w[i];
+        t = q == 1u ? w[i + 1] : t;
+        t = q == 2u ? w[i + 2] : t;
+        t = q == 3u ? w[i + 3] : t;
+        v[i] = t;
+    }
+    uint4 o;
+    o.x = __builtin_amdgcn_alignbyte(v[1], v[0], r);
+    o.y = __builtin_amdgcn_alignbyte(v[2], v[1], r);
+    o.z = __builtin_amdgcn_alignbyte(v[3], v[2], r);
+    o.w = __builtin_amdgcn_alignbyte(v[4], v[3], r);
+    return o;
+}
+
+// byte p (0 <= p - off < 15 + psize) of frame f: header or payload
+__device__ __forceinline__ uint32_t frame_byte(uint64_t rel, uint32_t crc, int32_t psize, int32_t bs, const uint8_t *slot)
+{
+    if (rel >= (uint64_t)JPK_JAM_HEADER_BYTES) return slot[rel - JPK_JAM_HEADER_BYTES];
+    const uint32_t r = (uint32_t)rel;
+    if (r < 3) return r == 0 ? 'J' : (r == 1 ? 'A' : 'M');
+    const uint32_t v = r < 7 ? crc : (r < 11 ? (uint32_t)psize : (uint32_t)bs);
+    const uint32_t k = r < 7 ? r - 3 : (r < 11 ? r - 7 : r - 11);
+    return (v >> (8 * k)) & 0xFFu;
+}
+
+// Organised by destination: word w is the aligned 16 bytes at base + 16 w (base = d_out rounded down to 16).  Its owner finds the frame
+// of its first byte by a search over the frame offsets, and then either (the whole word inside one payload) moves 16 payload bytes
+// through two aligned loads, or assembles the word byte by byte from headers and payloads.  Every whole word is written once with
+// one 16-byte store; only the partial words at the two ends of the range use byte stores, each byte by its word's owner.
+__global__ __launch_bounds__(PACK_TB) void k_jam_pack(const JamPackFrame *__restrict__ frames, uint32_t n, const uint32_t *__restrict__ crcs,
+                                                      int32_t bs, uint8_t *__restrict__ out, uint64_t total)
+{
+    __shared__ uint64_t s_off[JPK_JAM_PASS_FRAMES + 1];
+    __shared__ const uint8_t *s_slot[JPK_JAM_PASS_FRAMES];
+    __shared__ int32_t s_psize[JPK_JAM_PASS_FRAMES];
+    __shared__ uint32_t s_crc[JPK_JAM_PASS_FRAMES];
+    for (uint32_t i = threadIdx.x; i < n; i += PACK_TB) {
+        const JamPackFrame f = frames[i];
+        s_off[i] = f.off; s_slot[i] = f.slot; s_psize[i] = f.psize; s_crc[i] = crcs[i];
+    }
+    if (threadIdx.x == 0) s_off[n] = total;
+    __syncthreads();
+    const uintptr_t base = (uintptr_t)out & ~(uintptr_t)15;
+    const int64_t lead = (int64_t)((uintptr_t)out - base);                     // bytes of the first word in front of the range
+    const uint64_t words = ((uint64_t)lead + total + 15u) / 16u;
+    for (uint64_t w = (uint64_t)blockIdx.x * PACK_TB + threadIdx.x; w < words; w += (uint64_t)gridDim.x * PACK_TB) {
+        const int64_t p0 = (int64_t)(w * 16u) - lead;                          // archive position of the word's first byte (< 0: before the range)
+        const uint64_t first = p0 < 0 ? 0u : (uint64_t)p0;
+        uint32_t lo = 0, hi = n;                                              // frame of `first`: the last with s_off <= first
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s_off[mid] <= first) lo = mid; else hi = mid; }
+        uint32_t f = lo;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
+        const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
+        const uint64_t pay = s_off[f] + JPK_JAM_HEADER_BYTES;
+        if (whole && (uint64_t)p0 >= pay && (uint64_t)p0 + 16u <= pay + (uint64_t)s_psize[f]) {
+            *reinterpret_cast<uint4 *>(dst) = load16_unaligned(s_slot[f] + ((uint64_t)p0 - pay));
+            continue;
+        }
+        uint32_t b[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t p = p0 + j;
+            b[j] = 0;
+            if (p < 0 || (uint64_t)p >= total) continue;
+            while (f + 1 < n && (uint64_t)p >= s_off[f + 1]) f++;
+            b[j] = frame_byte((uint64_t)p - s_off[f], s_crc[f], s_psize[f], bs, s_slot[f]);
+            if (!whole) dst[j] = (uint8_t)b[j];
+        }
+        if (whole) {
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            *reinterpret_cast<uint4 *>(dst) = v;
+        }
+    }
+}
+
+}  // namespace
+
+int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
+                         uint32_t *d_mail)
+{
+    JPK_LAUNCH(ctx, PROF_JAM, 0, k_jam_walk, dim3(1), dim3(64), d_in, in_len, start, max_frames, d_table, d_mail);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
+
+int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, const uint32_t *d_crc, int32_t block_size, uint8_t *d_out, uint64_t total)
+{
+    if (n <= 0 || n > JPK_JAM_PASS_FRAMES) return JPK_E_ARG;
+    if (total == 0) return JPK_OK;
+    const uint64_t words = (total + 31u) / 16u;
+    uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
+    if (grid > 8192) grid = 8192;                                              // grid-stride beyond: 2M threads cover a pass
+    JPK_LAUNCH(ctx, PROF_JAM, total, k_jam_pack, dim3((unsigned)grid), dim3(PACK_TB), d_frames, (uint32_t)n, d_crc, block_size, d_out, total);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
