@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- block hot path throughput on MI355X (see DESIGN.md section "Measurement").
 
-  python bench.py --gpus N --steps K --warmup W [--workload enwik8|enwik9|...] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--workload enwik8|enwik9|...] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing more: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the result line.  --full also measures and checks everything else (the extra keys below, several minutes).
 
 --dump-outputs DIR writes the compressed blocks of the last timed step as DIR/*.npy (float32, under 64 MB: a seeded sample of
 larger outputs, see dump_outputs()); the inputs depend only on the arguments, so two builds can be compared file by file.
@@ -113,7 +116,10 @@ def parse():
     ap.add_argument("--block-mib", type=int, default=64)
     ap.add_argument("--limit-bytes", type=int, default=0, help="truncate the workload (debug only; marks the line invalid)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (multi-GPU children print this anyway)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: workload variants, stages, roofline, decompress, batch calls, "
+                         "block sizes, host buffers, CPU baseline (several minutes)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed region after all (a plain run does only that)")
     # 8 since round 4: a context's arena is 3.1 GB now (6 GB before), and 8 blocks in flight measured +4.8 % over 4 (+3.2 % with 6) in
     # twelve alternating runs on one box (profiles/r04_blocks_in_flight.txt)
     ap.add_argument("--contexts", type=int, default=10,
@@ -898,6 +904,7 @@ def main():
     value = job_bytes / 1e6 / (dt / args.steps)
 
     extra = {}
+    extras = args.full and not args.no_extras
     if args.dump_outputs and rank == 0:
         # what the last timed step handed its caller: with a gather, rank 0's gathered blocks (file order in stream mode, rank-major
         # otherwise); on one rank, the loop's own output buffers
@@ -906,7 +913,7 @@ def main():
         else:
             outs = [d_out[i][: sizes[i]] for i in range(nblk)]
         extra["dump_outputs"] = dump_outputs(args.dump_outputs, [t.cpu().numpy() for t in outs])
-    if rank == 0 and world == 1 and not args.no_extras and blocks:
+    if rank == 0 and world == 1 and extras and blocks:
         # the workload variants first: the same loop, the same contexts, right behind the timed steps (before the extras that create contexts
         # and streams of their own: a later leg of this process measures 5-10 % lower, see child_extras)
         if args.workload == "enwik8" and not args.limit_bytes:
@@ -1064,10 +1071,10 @@ def main():
                                                                  "frac": onew["frac"]}
         return extra_
 
-    if rank == 0 and world > 1 and not args.no_extras and blocks:
+    if rank == 0 and world > 1 and extras and blocks:
         extra.update(roofline_extra())          # the other ranks wait at the final barrier meanwhile
     # ---- un-timed extras on rank 0 of a 1-GPU run: stage breakdown, decompress leg, parity flags, roofline, CPU baseline ----
-    if rank == 0 and world == 1 and not args.no_extras and blocks:
+    if rank == 0 and world == 1 and extras and blocks:
         reps = max(3, min(args.steps, 10))
         ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731  (same stream as the library's launches)
         names = ("forward_bwt", "ans_encode", "ans_decode", "inverse_bwt")

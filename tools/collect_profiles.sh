@@ -12,7 +12,7 @@ export JAMPACK_CORPUS_CACHE=/tmp/jpk_corpus
 cd /tmp
 # 0. the bench line first, on the untouched box: after the counter-collection passes below the host-buffer extras of a bench run on the
 #    same box were 10-20x slow on two of three boxes (SDMA copies; GPU-resident figures unaffected) -- profiles/r04_bench_after_rocprof_passes.json
-( cd $REPO && python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > "$OUT/bench.json" )
+( cd $REPO && python3 bench.py --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > "$OUT/bench.json" )
 # 1. PMC passes (separate, counters only) of one compress step of the default workload
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$C
@@ -22,7 +22,7 @@ done
 python3 $REPO/tools/pmc_summary.py /tmp/pmc_FETCH_SIZE /tmp/pmc_WRITE_SIZE "$OUT/pmc_traffic.json" > "$OUT/pmc_summary.txt" 2>&1
 # 2. kernel trace + stats of the bench command
 rm -rf /tmp/kt
-rocprofv3 --kernel-trace --stats -d /tmp/kt -o kt -- python3 $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2>/tmp/kt.log
+rocprofv3 --kernel-trace --stats -d "$TMPDIR/kt" -o kt -- python3 $REPO/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > "$OUT/bench_under_rocprof.json" 2>"$TMPDIR/kt.log"
 python3 $REPO/tools/rocpd_stats.py /tmp/kt/kt_results.db > "$OUT/kernel_stats.txt" 2>&1
 # 3. stage-level traces of one 64 MiB block (per-rep numbers)
 rm -rf /tmp/kf /tmp/ke
@@ -35,7 +35,7 @@ python3 $REPO/tools/rocpd_timeline.py /tmp/ke/e_results.db k_density > "$OUT/tim
 cd $REPO
 cp "$OUT/pmc_traffic.json" profiles/${TAG}_pmc_traffic.json 2>/dev/null     # bench.py reads the traffic of the dominant kernel from here (step 0 used the file of the collection before)
 python3 bench.py --workload enwik9 --steps 2 --warmup 1 --no-extras 2>/dev/null | tail -1 > "$OUT/bench_enwik9like.json"
-python3 bench.py --workload silesia --block-mib 256 --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_silesialike_256mib.json"
+python3 bench.py --workload silesia --block-mib 256 --steps 2 --warmup 1 --full --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_silesialike_256mib.json"
 python3 tools/worst_cases.py > "$OUT/worst_cases.txt" 2>/dev/null
 NLIST=1,4,8,16,24,32,48,64 python3 tools/dec_scaling.py batch > "$OUT/decode_batch_scaling.txt" 2>/dev/null
 python3 tools/stage_scaling.py 2>/dev/null | grep contexts > "$OUT/stage_scaling.txt"
