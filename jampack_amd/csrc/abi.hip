@@ -74,59 +74,6 @@ int jpk_read_mail(jpk_ctx *ctx, uint32_t *dst, int words)
     return JPK_OK;
 }
 
-// ---- heavy-phase gate (common.hpp) -----------------------------------------------------------------------------------------
-namespace {
-struct Gate {
-    std::mutex mu[64];
-    jpk_ctx *owner[64] = {nullptr};        // per device: the context whose heavy phases were admitted last
-};
-Gate &gate() { static Gate g; return g; }
-// OFF unless JPK_GATE=1: measured on MI355X the gate LOSES -- default 2-block step 1.89 GB/s with it against 1.99 without,
-// enwik9-like with 8 blocks in flight 2.28 against 2.68 GB/s -- the kernels of interleaved blocks fill each other's latency
-// gaps better than a strict block-after-block order does.  Kept as a switch for the record and for other mixes of blocks.
-bool gate_on() { static const bool on = getenv("JPK_GATE") && atoi(getenv("JPK_GATE")) == 1; return on; }
-}  // namespace
-
-int jpk_gate_enter(jpk_ctx *ctx)
-{
-    if (!gate_on() || ctx->gate_held || ctx->device < 0 || ctx->device >= 64) return JPK_OK;
-    Gate &g = gate();
-    g.mu[ctx->device].lock();
-    jpk_ctx *prev = g.owner[ctx->device];
-    if (prev && prev != ctx)
-        for (int k = 0; k < prev->gate_nev; k++)
-            if (hipStreamWaitEvent(ctx->stream, prev->ev_gate[k], 0) != hipSuccess) { g.mu[ctx->device].unlock(); return JPK_E_DEVICE; }
-    ctx->gate_held = true;
-    ctx->gate_nev = 0;
-    return JPK_OK;
-}
-
-int jpk_gate_mark(jpk_ctx *ctx, hipStream_t stream)
-{
-    if (!ctx->gate_held || ctx->gate_nev >= jpk_ctx::GATE_EVENTS) return JPK_OK;
-    JPK_HIP(hipEventRecord(ctx->ev_gate[ctx->gate_nev], stream));
-    ctx->gate_nev++;
-    return JPK_OK;
-}
-
-void jpk_gate_leave(jpk_ctx *ctx)
-{
-    if (!ctx->gate_held) return;
-    Gate &g = gate();
-    g.owner[ctx->device] = ctx;
-    ctx->gate_held = false;
-    g.mu[ctx->device].unlock();
-}
-
-void jpk_gate_forget(jpk_ctx *ctx)
-{
-    if (ctx->device < 0 || ctx->device >= 64) return;
-    Gate &g = gate();
-    if (ctx->gate_held) { ctx->gate_held = false; g.owner[ctx->device] = nullptr; g.mu[ctx->device].unlock(); return; }
-    std::lock_guard<std::mutex> lk(g.mu[ctx->device]);
-    if (g.owner[ctx->device] == ctx) g.owner[ctx->device] = nullptr;
-}
-
 // ---- per-kernel HIP-event profiler (events are recorded on the launch stream) ------------------------------
 static hipEvent_t prof_event(jpk_ctx *ctx)
 {
@@ -189,6 +136,8 @@ extern "C" int jpk_ctx_profile_get(jpk_ctx *ctx, int id, double *ms, int64_t *la
 }
 
 // ---- contexts ----------------------------------------------------------------------------------------------
+// the kernels are built and tuned for gfx950 only; JPK_ALLOW_ANY_ARCH (presence) lets another device through
+static bool arch_ok(const hipDeviceProp_t &prop) { return strncmp(prop.gcnArchName, "gfx950", 6) == 0 || getenv("JPK_ALLOW_ANY_ARCH"); }
 extern "C" int jpk_device_count(void)
 {
     int n = 0;
@@ -205,7 +154,7 @@ extern "C" int jpk_ctx_create(jpk_ctx **out, int device, void *hip_stream)
     JPK_HIP(hipSetDevice(device));
     hipDeviceProp_t prop;
     JPK_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !getenv("JPK_ALLOW_ANY_ARCH")) return JPK_E_NODEVICE;
+    if (!arch_ok(prop)) return JPK_E_NODEVICE;
     jpk_ctx *c = new (std::nothrow) jpk_ctx();
     if (!c) return JPK_E_ALLOC;
     memset(&c->stats, 0, sizeof c->stats);
@@ -224,8 +173,6 @@ extern "C" int jpk_ctx_create(jpk_ctx **out, int device, void *hip_stream)
     for (int k = 0; k < 2; k++)
         if (hipEventCreateWithFlags(&c->ev_sa[k], hipEventDisableTiming) != hipSuccess) { jpk_ctx_destroy(c); return JPK_E_ALLOC; }
     if (hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming) != hipSuccess) { jpk_ctx_destroy(c); return JPK_E_ALLOC; }
-    for (int k = 0; k < jpk_ctx::GATE_EVENTS; k++)
-        if (hipEventCreateWithFlags(&c->ev_gate[k], hipEventDisableTiming) != hipSuccess) { jpk_ctx_destroy(c); return JPK_E_ALLOC; }
     for (int g = 0; g < jpk_ctx::ENC_GROUPS; g++) {
         // (the encoder's group streams c->aux[] are created on first use: a context that only decodes owns one stream, and
         // streams are dealt round robin onto the hardware queues when they are created)
@@ -244,9 +191,6 @@ extern "C" void jpk_ctx_destroy(jpk_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    jpk_gate_forget(c);
-    for (int k = 0; k < jpk_ctx::GATE_EVENTS; k++)
-        if (c->ev_gate[k]) (void)hipEventDestroy(c->ev_gate[k]);
     if (c->arena) (void)hipFree(c->arena);
     if (c->stage_in) (void)hipFree(c->stage_in);
     if (c->stage_out) (void)hipFree(c->stage_out);
@@ -363,7 +307,7 @@ int jpk_enc_groups_for(int inflight, uint32_t nch)
 // test hooks (host logic only, no device call): the per-device accounting and the grouping rule.  The hooks that CHANGE live state
 // (this one with delta != 0, jpk_debug_combiner_fail_next) work only in a process that sets JPK_DEBUG_HOOKS=1: no caller of the
 // product library can move the in-flight count that drives the encoder's launch grouping by accident.
-static bool debug_hooks_on() { const char *e = getenv("JPK_DEBUG_HOOKS"); return e && atoi(e) != 0; }
+static bool debug_hooks_on() { return jpk_env_long("JPK_DEBUG_HOOKS", 0) != 0; }
 extern "C" int jpk_debug_compress_inflight(int device, int delta)
 {
     if (device < 0 || device >= 64) return JPK_E_ARG;
@@ -458,12 +402,8 @@ extern "C" int jpk_dev_block_compress(jpk_ctx *ctx, const uint8_t *d_in, int32_t
     const size_t mid = (size_t)in_len + JPK_TRAILER_BYTES;
     JPK_TRY(buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, mid));
     if (in_len < JPK_BWT_UNITS) JPK_HIP(hipMemsetAsync(ctx->stage_out, 0, mid, ctx->stream));   // untouched trailer: defined bytes
-    // the gate stays closed from the first kernel of the suffix sort to the last wide kernel of the entropy stage; the encoder
-    // opens it (jpk_gate_leave) once those are enqueued, in front of its first host synchronisation
-    JPK_TRY(jpk_gate_enter(ctx));
     int rc = jpk_fwd_bwt_device(ctx, d_in, in_len, ctx->stage_out);
     if (rc == JPK_OK) rc = jpk_ans_encode_device(ctx, ctx->stage_out, (int32_t)mid, d_out, out_cap, out_len);    // synchronises the stream
-    jpk_gate_leave(ctx);                     // no-op unless an error kept the encoder from doing it
     if (rc == JPK_OK) jpk_sa_stats_sync(ctx);
     return rc;
 }
@@ -528,22 +468,22 @@ extern "C" int jpk_dev_blocks_decompress(jpk_ctx *ctx, int32_t nblocks, const ui
     // Lanes: an inverse BWT is ~30 dependent launches of which only the walk fills the chip (1.6 of 2.5 ms for 64 MiB, the rest
     // is 20-microsecond rank-jump rounds and launch gaps), so up to three run side by side, each on its own stream with its own
     // scratch, behind one event on the decode stream.
-    static const int max_lanes = [] { const char *e = getenv("JPK_INV_LANES"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > jpk_ctx::ENC_GROUPS ? jpk_ctx::ENC_GROUPS : v); }();
+    static const int max_lanes = (int)jpk_env_long("JPK_INV_LANES", 3, 1, jpk_ctx::ENC_GROUPS);
     // ... and up to JPK_INV_LANES_SMALL (default 12) when the batch is many SMALL blocks (<= 4 MiB): an inverse BWT of a 1 MiB block is
     // the same ~30 dependent launches, each a sliver of the chip, and 256 of them on three lanes took 100 ms of a 245 ms call whose
     // chains had finished after 145 (round 4: 1 070 -> 1 400 MB/s with 8 to 16 lanes; what is left is the host's launch rate, 7 700
     // launches per call).  Blocks of 8 MiB gain nothing (nine chains per block: the chains are the call) and would pay 12 scratch areas.
-    static const int small_lanes = [] { const char *e = getenv("JPK_INV_LANES_SMALL"); const int v = e ? atoi(e) : 12; return v < 1 ? 1 : (v > jpk_ctx::INV_LANES_MAX ? jpk_ctx::INV_LANES_MAX : v); }();
+    static const int small_lanes = (int)jpk_env_long("JPK_INV_LANES_SMALL", 12, 1, jpk_ctx::INV_LANES_MAX);
     // Only a batch with many blocks gets lanes: they save the latency part of each inverse BWT (~1 ms of 2.5), nothing next to
     // the 270 ms of a small batch's chains, and every extra stream of a context lands on a hardware queue that another
     // context's chain kernels may be using (eight contexts decoding 2-block passes lost 18 % with a second stream each).
     const bool many_small = nblocks >= 32 && nmax <= (4u << 20);
     // ... or, by default, through ONE set of launches over all of them (bwt_inv.hip jpk_inv_bwt_batch_enqueue; JPK_INV_BATCH=0 keeps the lanes)
-    static const bool batch_on = [] { const char *e = getenv("JPK_INV_BATCH"); return e ? atoi(e) != 0 : true; }();
-    // (in groups of consecutive blocks whose scratch fits JPK_INV_BATCH_GIB, default 8.  Batches of LARGE blocks gain nothing from it --
+    static const bool batch_on = jpk_env_long("JPK_INV_BATCH", 1) != 0;
+    // (in groups of consecutive blocks whose scratch fits 8 GiB.  Batches of LARGE blocks gain nothing from it --
     // 16 / 32 / 64 blocks of 64 MiB: 310 / 350 / 438 ms against 309 / 348 / 435 on the three lanes: their walks fill the chip -- and stay
     // on the lanes.)
-    static const size_t batch_budget = [] { const char *e = getenv("JPK_INV_BATCH_GIB"); const long v = e ? atol(e) : 8; return (size_t)(v < 1 ? 1 : v) << 30; }();
+    constexpr size_t batch_budget = (size_t)8 << 30;
     const bool batched = batch_on && many_small;
     int lanes = (nblocks < 8 || batched) ? 1 : (many_small ? (small_lanes > max_lanes ? small_lanes : max_lanes) : max_lanes);
     hipStream_t lane_stream[jpk_ctx::INV_LANES_MAX] = {};
@@ -816,7 +756,7 @@ int pool_select(CtxPool &p, uint64_t mask)
         if (mask && !((mask >> d) & 1u)) continue;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, d) != hipSuccess) continue;
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !getenv("JPK_ALLOW_ANY_ARCH")) continue;
+        if (!arch_ok(prop)) continue;
         p.devices.push_back(d);
     }
     if (p.devices.empty()) return JPK_E_NODEVICE;
@@ -902,8 +842,8 @@ constexpr int32_t GROUP_BLOCK_MAX = 16 << 20;       // blocks up to this size ar
 // groups in flight: a quarter of the small blocks' bytes, between 8 and 64 MiB.  JPK_GROUP_MIB fixes it.
 size_t group_target_bytes(size_t small_bytes_total)
 {
-    static const long fixed = [] { const char *e = getenv("JPK_GROUP_MIB"); return e ? atol(e) : 0L; }();
-    if (fixed > 0) return (size_t)(fixed > 512 ? 512 : fixed) << 20;
+    static const long fixed = jpk_env_long("JPK_GROUP_MIB", 0, 0, 512);
+    if (fixed > 0) return (size_t)fixed << 20;
     size_t t = small_bytes_total / 4;
     if (t < ((size_t)8 << 20)) t = (size_t)8 << 20;
     if (t > ((size_t)64 << 20)) t = (size_t)64 << 20;
@@ -915,7 +855,7 @@ struct Task { int first, count; };
 // groups of at most 256 blocks and (beyond the first block) at most the target size; a larger block is a task of its own
 void plan_tasks(int nblocks, const int32_t *in_len, std::vector<Task> &tasks)
 {
-    static const bool grouping = [] { const char *e = getenv("JPK_GROUP"); return e ? atoi(e) != 0 : true; }();
+    static const bool grouping = jpk_env_long("JPK_GROUP", 1) != 0;
     size_t small_total = 0;
     for (int k = 0; k < nblocks; k++) if (in_len[k] <= GROUP_BLOCK_MAX) small_total += (size_t)in_len[k];
     const size_t target = group_target_bytes(small_total);
@@ -974,10 +914,8 @@ int group_compress(jpk_ctx *c, int nb, const uint8_t *const *d_in, const int32_t
         // bwt.cpp:35: a block shorter than 120 bytes leaves its 480 trailer bytes alone -- defined bytes here, as in jpk_dev_block_compress
         if (in_len[b] < JPK_BWT_UNITS) JPK_HIP(hipMemsetAsync(img[b], 0, (size_t)mid[b], c->stream));
     }
-    JPK_TRY(jpk_gate_enter(c));
     int rc = jpk_fwd_bwt_group_device(c, nb, d_in, in_len, img.data());
     if (rc == JPK_OK) rc = jpk_ans_encode_group_device(c, nb, c->stage_out, first.data(), mid.data(), d_out, out_cap, out_len, status);   // synchronises
-    jpk_gate_leave(c);
     if (rc == JPK_OK) jpk_sa_stats_sync(c);
     else (void)hipStreamSynchronize(c->stream);            // the pinned tables and the staged images stay valid until the queue is empty
     return rc;
@@ -1264,7 +1202,7 @@ int multi_run(bool compress, uint64_t device_mask, int32_t nblocks, const uint8_
     for (int d : cand) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, d) != hipSuccess) continue;
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !getenv("JPK_ALLOW_ANY_ARCH")) continue;
+        if (!arch_ok(prop)) continue;
         devs.push_back(d);
     }
     if (devs.empty()) return JPK_E_NODEVICE;
@@ -1364,7 +1302,7 @@ int multi_run(bool compress, uint64_t device_mask, int32_t nblocks, const uint8_
 
     // the gather: root's own blocks are device-to-device copies; the others travel over RCCL, one send / receive pair per block.
     // A communicator set belongs to a device LIST and is used under the mutexes of all its devices (this call holds them).
-    static const bool force_rccl = [] { const char *e = getenv("JPK_MULTI_FORCE_RCCL"); return e && atoi(e) != 0; }();
+    static const bool force_rccl = jpk_env_long("JPK_MULTI_FORCE_RCCL", 0) != 0;
     const bool use_rccl = rc == JPK_OK && total > 0 && (G > 1 || force_rccl);
     const std::vector<jpk_nccl_comm_t> *comms = nullptr;
     if (use_rccl) {
@@ -1543,20 +1481,12 @@ int staged(dev_fn fn, const uint8_t *in, int32_t in_len, uint8_t *out, int32_t o
     // the fused entry points use stage_out as their intermediate, so the host-visible result gets its own buffer
     JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)out_cap + 64));
     uint8_t *d_res = ctx->stage_res;
-    static const bool timing = getenv("JPK_TIME_HOST") != nullptr;      // JPK_TIME_HOST=1: where a host-buffer call spends its time
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t0 = timing ? now() : 0;
     if (in_len) JPK_HIP(hipMemcpyAsync(ctx->stage_in, in, (size_t)in_len, hipMemcpyHostToDevice, ctx->stream));
     if (prefill_out && out_cap) JPK_HIP(hipMemcpyAsync(d_res, out, (size_t)out_cap, hipMemcpyHostToDevice, ctx->stream));
-    if (timing) (void)hipStreamSynchronize(ctx->stream);
-    const double t1 = timing ? now() : 0;
     int32_t n = 0;
     JPK_TRY(fn(ctx, ctx->stage_in, in_len, d_res, out_cap, &n));
-    if (timing) (void)hipStreamSynchronize(ctx->stream);
-    const double t2 = timing ? now() : 0;
     if (n > 0) JPK_HIP(hipMemcpyAsync(out, d_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
-    if (timing) fprintf(stderr, "[jampack_amd] host call: in %d B, out %d B: H2D %.2f ms, device %.2f ms, D2H %.2f ms\n", in_len, n, t1 - t0, t2 - t1, now() - t2);
     *out_len = n;
     return JPK_OK;
 }
@@ -1613,7 +1543,7 @@ Combiner &combiner(int device) { static Combiner c[64]; return c[device & 63]; }
 // grace in microseconds the leader grants late arrivals once the process has shown concurrent decode calls; < 0 = combiner off
 int combine_grace_us()
 {
-    static const int v = [] { const char *e = getenv("JPK_COMBINE_US"); return e ? atoi(e) : 300; }();
+    static const int v = (int)jpk_env_long("JPK_COMBINE_US", 300, INT_MIN, INT_MAX);
     return v;
 }
 }  // namespace
@@ -1683,7 +1613,7 @@ extern "C" int jpk_ans_decode(const uint8_t *in, int32_t in_len, uint8_t *out, i
         }
         // the merged pass is bounded: requests beyond JPK_COMBINE_MAX_MIB (default 2048) of output capacity stay with their own
         // threads, so that the hidden combiner context's arena (~3 bytes per output byte) cannot grow without limit
-        static const size_t max_bytes = [] { const char *e = getenv("JPK_COMBINE_MAX_MIB"); const long m = e ? atol(e) : 2048; return (size_t)(m < 1 ? 1 : m) << 20; }();
+        static const size_t max_bytes = (size_t)jpk_env_long("JPK_COMBINE_MAX_MIB", 2048, 1) << 20;
         std::vector<DecReq *> turned_away;
         {
             size_t bytes = 0;

@@ -960,7 +960,7 @@ int jpk_ans_decode_batch(jpk_ctx *ctx, int nblk, const uint8_t *const *d_in, con
     // them to four workgroups per CU; larger batches run without it, because two chains on a SIMD fill each other's issue
     // bubbles and a second round of workgroups would wait for the first (64 blocks: 3.5 -> 4.8 GB/s, tools/dec_scaling.py).
     const unsigned g = (unsigned)nch_total;
-    static const int lds_env = [] { const char *e = getenv("JPK_DEC_LDS"); if (!e) return -1; const int v = atoi(e); return v < 0 ? 0 : (v > 65536 ? 65536 : v); }();
+    static const int lds_env = (int)jpk_env_long("JPK_DEC_LDS", -1, 0, 65536);
     const size_t lds_cap = (size_t)(lds_env >= 0 ? lds_env : (g <= 1024u ? 40960 : 0));
     // more chains than run at once: longest first
     uint32_t *order = nullptr;

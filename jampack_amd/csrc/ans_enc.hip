@@ -610,8 +610,9 @@ __global__ __launch_bounds__(64) void k_quasi_build(EncDims d, const uint32_t *_
 // five k_adapt_* kernels: 4.3 ms per 64 MiB block against 4.9 with 320) -- but the warm-up is pure vector work (two states per item,
 // +62 % on k_adapt_a), and with blocks in flight vector issue is what is short: the bench line prefers 320 (4.41 / 4.38 / 4.29 /
 // 4.15 GB/s for 320 / 384 / 512 / 1280 in one sequence, 4.22 / 4.13 / 4.11 for 320 / 384 / 1280 interleaved three times;
-// profiles/r04_adapt_warm.txt).  JPK_AD_WARM overrides (multiple of 64, 320..4096).
+// profiles/r04_adapt_warm.txt).
 constexpr uint32_t AD_WARM_DEFAULT = 320;
+static_assert(AD_WARM_DEFAULT % 64 == 0 && AD_WARM_DEFAULT >= 320 && AD_WARM_DEFAULT <= 4096, "whole waves of warm-up items, guarantee above");
 
 struct AdRec {                          // one recurrence
     bool exp;                           // exponent model entry (true) or alphabet-2 mantissa model (false)
@@ -1547,13 +1548,7 @@ int run_model(jpk_ctx *ctx, const uint16_t *d_rle, const uint32_t *d_rlen, const
     AdArgs aa;
     aa.cls8 = b.cls8; aa.clist = b.clist; aa.rle_stride = stride; aa.rlen = d_rlen; aa.clstotal = b.clstotal; aa.clsbase = b.clscnt;
     aa.exph = b.exph; aa.mantad = b.mantad;
-    static const uint32_t warm = [] {
-        const char *e = getenv("JPK_AD_WARM");
-        long v = e ? atol(e) : (long)AD_WARM_DEFAULT;
-        v = (v + 63) / 64 * 64;
-        return (uint32_t)(v < 320 ? 320 : (v > 4096 ? 4096 : v));
-    }();
-    aa.warm = warm;
+    aa.warm = AD_WARM_DEFAULT;
     aa.seg_flag = b.seg_flag; aa.seg_lo = b.seg_lo; aa.seg_end = b.seg_end; aa.seg_start = b.seg_start; aa.seg_tab = b.seg_tab;
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_a, dim3((d.tpc + 63) / 64, 9, d.ncl), dim3(64), d, aa);
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_ext, dim3((d.tpc + 63) / 64, 9, d.ncl), dim3(64), d, aa);
@@ -1692,7 +1687,7 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
     // when other blocks fill the machine anyway (more kernels, more streams on the hardware queues): 4 groups alone, 2 beside one
     // other block, 1 beside two or more (default bench, 4 blocks in flight: 3.23 / 3.32 / 3.46 GB/s with 4 / 2 / 1 groups)
     int ngroups = jpk_enc_groups_for(inflight_n, d.nch);
-    static const int groups_env = [] { const char *e = getenv("JPK_ENC_GROUPS"); return e ? atoi(e) : 0; }();
+    static const long groups_env = jpk_env_long("JPK_ENC_GROUPS", 0);
     if (groups_env >= 1 && groups_env <= jpk_ctx::ENC_GROUPS && (uint32_t)groups_env <= d.nch) ngroups = groups_env;
     // group streams are created when a block first needs them and then stay with the context (parked while the device is busy
     // with other blocks: an idle stream costs nothing, destroying and re-creating it under fluctuating load costs a synchronise)
@@ -1730,12 +1725,10 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
             if (gs != st && hipStreamWaitEvent(gs, ctx->ev_pre[0], 0) != hipSuccess) { rc = JPK_E_DEVICE; break; }
             ctx->stream = gs;
             rc = pre_chain(gd);
-            if (rc == JPK_OK) rc = jpk_gate_mark(ctx, gs);        // the wide kernels of this group end here; the chains run beside the next block
             if (rc == JPK_OK) rc = chain(gd);
             ctx->stream = st;
             if (rc == JPK_OK && gs != st && hipEventRecord(ctx->ev_done[g], gs) != hipSuccess) rc = JPK_E_DEVICE;
         }
-        jpk_gate_leave(ctx);                                       // everything GPU-saturating of this block is enqueued
         for (int g = 0; g + 1 < ngroups && rc == JPK_OK; g++)
             if (hipStreamWaitEvent(st, ctx->ev_done[g], 0) != hipSuccess) rc = JPK_E_DEVICE;
         if (rc != JPK_OK) {
@@ -1745,10 +1738,7 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
             return rc;
         }
     } else {
-        int rc = pre_chain(d);
-        if (rc == JPK_OK) rc = jpk_gate_mark(ctx, st);
-        jpk_gate_leave(ctx);
-        JPK_TRY(rc);
+        JPK_TRY(pre_chain(d));
         JPK_TRY(chain(d));
     }
     JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_headers, dim3(d.nch), dim3(256), d, b.freq, b.csize, b.rlen, b.hdr, b.hsize);

@@ -2320,31 +2320,19 @@ __global__ __launch_bounds__(WG1) void k_pair_scan(uint32_t *__restrict__ tFirst
     wg_scan<OpMin, true, true>(tFirst, tFirst, (n + CT - 1) / CT, NONE, sm);      // first stretch end in any LATER tile
 }
 // verdict of the stretch that ends at x with distance p: the pair (x + 1, x + 1 + p).  When the two lie in ONE group with other
-// members between them (x + 1 belongs to a group that mixes two repeats: its neighbour is nearer than p), the pair is decided by the
-// chain of neighbouring pairs from x + 1 up to x + 1 + p if all of them carry one verdict already (`chain`: V holds the verdicts of an
-// earlier pass over the stretches; a value only ever changes from open to decided, so reading it while this pass writes is safe).
+// members between them (x + 1 belongs to a group that mixes two repeats: its neighbour is nearer than p), the pair stays open (0).
 __device__ __forceinline__ uint32_t pair_verdict(uint32_t x, uint32_t p, const uint32_t *__restrict__ ISA, uint32_t n, const uint8_t *__restrict__ blk,
-                                                 const uint32_t *__restrict__ bend, const uint32_t *__restrict__ P, const uint8_t *V, bool chain)
+                                                 const uint32_t *__restrict__ bend)
 {
     const uint32_t lim = bend ? bend[blk[x]] : n;
     const uint64_t b = (uint64_t)x + 1u + p;                     // x + p is a member's position (< lim), so b <= lim
     if (b >= lim) return 2u;
     const uint32_t ra = ISA[x + 1u], rb = ISA[b];
     if (ra != rb) return ra < rb ? 1u : 2u;
-    if (!chain) return 0u;
-    uint32_t z = x + 1u, v = 0u;
-    for (int step = 0; step < 8 && z < (uint32_t)b; step++) {
-        const uint32_t pz = P[z];
-        if (pz == 0u || (pz & PREP)) return 0u;                  // (the first member of its group, or a carried-through position: the chain does not reach b)
-        const uint32_t vz = V[z];
-        if (vz == 0u || (v && vz != v)) return 0u;
-        v = vz;
-        z += pz;
-    }
-    return z == (uint32_t)b ? v : 0u;
+    return 0u;
 }
 __global__ __launch_bounds__(TB) void k_pair_fill(const uint32_t *__restrict__ P, uint32_t n, const uint32_t *__restrict__ tAfter, const uint32_t *__restrict__ ISA,
-                                                 uint8_t *V, const uint8_t *__restrict__ blk, const uint32_t *__restrict__ bend, int chain)
+                                                 uint8_t *V, const uint8_t *__restrict__ blk, const uint32_t *__restrict__ bend)
 {
     __shared__ uint32_t sm[TB / 64 + 1];
     __shared__ uint32_t rv[TB];
@@ -2382,9 +2370,9 @@ __global__ __launch_bounds__(TB) void k_pair_fill(const uint32_t *__restrict__ P
             const uint32_t i = p0 + k;
             if (i < n) {
                 const uint32_t p = pv[k];
-                if (bits & (1u << k)) { nb = i; vnb = p ? pair_verdict(i, p, ISA, n, blk, bend, P, V, chain != 0) : 0u; }
+                if (bits & (1u << k)) { nb = i; vnb = p ? pair_verdict(i, p, ISA, n, blk, bend) : 0u; }
                 if (p) {
-                    if (vnb == NONE) vnb = pair_verdict(nb, p, ISA, n, blk, bend, P, V, chain != 0);   // the stretch runs on into a later thread: P[nb] == p
+                    if (vnb == NONE) vnb = pair_verdict(nb, p, ISA, n, blk, bend);   // the stretch runs on into a later thread: P[nb] == p
                     V[i] = (rep & (1u << k)) ? (uint8_t)0 : (uint8_t)vnb;      // a position the stretch was carried through: ITS pair stays open
                 }
             }
@@ -2586,26 +2574,26 @@ int lg_digit_bits(uint32_t n, int *npass)
 // JPK_KEY_BITS=8 keeps round 0's keys at one byte per symbol whatever the alphabet (the comparator of the packed keys; 0 = from the alphabet)
 int key_force_bits()
 {
-    static const int v = [] { const char *e = getenv("JPK_KEY_BITS"); const int x = e ? atoi(e) : 0; return x < 0 ? 0 : (x > 8 ? 8 : x); }();
+    static const int v = (int)jpk_env_long("JPK_KEY_BITS", 0, 0, 8);
     return v;
 }
 
 // JPK_R0_LOOKBACK=0: round 0's head / survivor bookkeeping in two passes (k_r0_count + k_r0_scan in front of k_r0_finish: the comparator)
 bool r0_lookback()
 {
-    static const bool v = [] { const char *e = getenv("JPK_R0_LOOKBACK"); return e ? atoi(e) != 0 : true; }();
+    static const bool v = jpk_env_long("JPK_R0_LOOKBACK", 1) != 0;
     return v;
 }
 // JPK_KEY_ORDER=0 / 1: the variable-length keys use nothing above the order-0 / order-1 code (comparators; default 2)
 int key_order()
 {
-    static const int v = [] { const char *e = getenv("JPK_KEY_ORDER"); const int x = e ? atoi(e) : 2; return x < 0 ? 0 : x > 2 ? 2 : x; }();
+    static const int v = (int)jpk_env_long("JPK_KEY_ORDER", 2, 0, 2);
     return v;
 }
 // JPK_VARKEYS=0: fixed-width keys whatever the block (the comparator of the variable-length keys)
 bool var_keys_on()
 {
-    static const bool v = [] { const char *e = getenv("JPK_VARKEYS"); return e ? atoi(e) != 0 : true; }();
+    static const bool v = jpk_env_long("JPK_VARKEYS", 1) != 0;
     return v;
 }
 // variable-length keys: sorts (one block, or a group of small ones) of at most 2^28 bytes (the key's depth rides in the spare bits of the 32-bit suffix number:
@@ -2679,29 +2667,24 @@ void launch_lg_pass(jpk_ctx *ctx, SaBufs &b, const uint32_t *kin, const uint32_t
 // negative = never (the comparator: plain prefix doubling)
 int pair_rule_shift()
 {
-    static const int v = [] { const char *e = getenv("JPK_PAIR_SHIFT"); const int x = e ? atoi(e) : 6; return x > 31 ? 31 : x; }();
+    static const int v = (int)jpk_env_long("JPK_PAIR_SHIFT", 6, INT_MIN, 31);
     return v;
 }
-// JPK_PAIR_FROM: the first round that may be a pair round (default 3; 2 is possible since every round is enqueued on exact counts, and
-// measured worse: a 4 KiB period 17.2 -> 13.5 ms, but the silesia-like block 11.9 -> 16.6, long runs 18.9 -> 40.5 ms -- after one doubling
-// round the groups of a repeat still mix everything that shares 30 symbols, and the rule's passes over the text are not free.  Round 1
-// has to be a doubling round in any case: it is the one that spreads the run members)
-int pair_rule_from()
-{
-    static const int v = [] { const char *e = getenv("JPK_PAIR_FROM"); const int x = e ? atoi(e) : 3; return x < 2 ? 2 : x; }();
-    return v;
-}
+// the first round that may be a pair round.  2 measured worse: a 4 KiB period 17.2 -> 13.5 ms, but the silesia-like block 11.9 -> 16.6, long
+// runs 18.9 -> 40.5 ms -- after one doubling round the groups of a repeat still mix everything that shares 30 symbols.  Round 1 has to be a
+// doubling round in any case: it is the one that spreads the run members
+constexpr int PAIR_FROM = 3;
 // JPK_PAIR_EARLY=0: no pair round at round 2 for lists that round 1 left as they were (comparator)
 bool pair_rule_early()
 {
-    static const bool v = [] { const char *e = getenv("JPK_PAIR_EARLY"); return e ? atoi(e) != 0 : true; }();
+    static const bool v = jpk_env_long("JPK_PAIR_EARLY", 1) != 0;
     return v;
 }
 // JPK_PAIR_MIN: ... and at least this many (default 4096; the tests lower it so that tiny inputs take the path);
 // JPK_PAIR_GAP: rounds from one pair round to the next (default 3 = two doubling rounds in between, at least 2)
 uint32_t pair_rule_min()
 {
-    static const uint32_t v = [] { const char *e = getenv("JPK_PAIR_MIN"); const long x = e ? atol(e) : 4096L; return (uint32_t)(x < 2 ? 2 : x); }();
+    static const uint32_t v = (uint32_t)jpk_env_long("JPK_PAIR_MIN", 4096, 2);
     return v;
 }
 // JPK_PAIR_RATIO: ... and the previous round left at least this percentage of ITS list unresolved -- 0 = whatever the previous round did.
@@ -2711,17 +2694,13 @@ uint32_t pair_rule_min()
 // times, every pair round there left 74-90 % of its list and cost 4 ms (k_pair_repair's walks): 35.0 against 22.9 ms per block without them.
 uint32_t pair_rule_ratio()
 {
-    static const uint32_t v = [] { const char *e = getenv("JPK_PAIR_RATIO"); const int x = e ? atoi(e) : 90; return (uint32_t)(x < 0 ? 0 : (x > 100 ? 100 : x)); }();
+    static const uint32_t v = (uint32_t)jpk_env_long("JPK_PAIR_RATIO", 90, 0, 100);
     return v;
 }
-// JPK_PAIR_BUDGET: positions all walks of k_pair_repair together may visit in one pair round, in eighths of n (default 1; 8 n until the end of
-// round 6: no block whose pair rounds pay notices the difference, a pair round that does not pay costs 7 ms less on 64 MiB of real binaries)
-uint32_t pair_rule_budget(uint32_t n)
-{
-    static const uint32_t e8 = [] { const char *e = getenv("JPK_PAIR_BUDGET"); const long x = e ? atol(e) : 1; return (uint32_t)(x < 0 ? 0 : (x > 64 ? 64 : x)); }();
-    const uint64_t b = (uint64_t)n * e8 / 8u;
-    return b > 0xF0000000ull ? 0xF0000000u : (uint32_t)b;
-}
+// positions all walks of k_pair_repair together may visit in one pair round, in eighths of n (8 n until the end of round 6: no block whose
+// pair rounds pay notices the difference, a pair round that does not pay costs 7 ms less on 64 MiB of real binaries)
+constexpr uint32_t PAIR_BUDGET_EIGHTHS = 1;
+uint32_t pair_rule_budget(uint32_t n) { return (uint32_t)((uint64_t)n * PAIR_BUDGET_EIGHTHS / 8u); }
 // JPK_PAIR_KEEP: a pair round that leaves more than this percentage of its list did not pay (default 50; 100 = every one pays): the next one
 // waits twice as long (two doubling rounds, then six, fourteen, thirty).  The Fibonacci word took nine pair rounds that resolved NOTHING, every
 // one a round in which the doubling distance stands still (105 -> 60 ms per 32 MiB); a block that holds a real tree TWICE -- near-duplicate files
@@ -2729,25 +2708,12 @@ uint32_t pair_rule_budget(uint32_t n)
 // (round 12-15 of 23): giving up after the first would cost such a block its best round (tools/pair_yield.py, profiles/r06_real_files_pair_rounds.txt).
 uint32_t pair_rule_keep()
 {
-    static const uint32_t v = [] { const char *e = getenv("JPK_PAIR_KEEP"); const int x = e ? atoi(e) : 50; return (uint32_t)(x < 0 ? 0 : (x > 100 ? 100 : x)); }();
-    return v;
-}
-// JPK_PAIR_ITERS: passes of k_pair_fill per pair round (default 1; 2..4: later passes decide an end pair inside one group by the chain
-// of its neighbouring pairs -- built for groups that mix two repeats, where k_pair_repair turned out to be what helps; kept as an option)
-int pair_rule_iters()
-{
-    static const int v = [] { const char *e = getenv("JPK_PAIR_ITERS"); const int x = e ? atoi(e) : 1; return x < 1 ? 1 : (x > 4 ? 4 : x); }();
-    return v;
-}
-// JPK_PAIR_REPAIR=0: stretches end at every position whose own neighbour is nearer (the comparator of k_pair_repair)
-bool pair_rule_repair()
-{
-    static const bool v = [] { const char *e = getenv("JPK_PAIR_REPAIR"); return e ? atoi(e) != 0 : true; }();
+    static const uint32_t v = (uint32_t)jpk_env_long("JPK_PAIR_KEEP", 50, 0, 100);
     return v;
 }
 int pair_rule_gap()
 {
-    static const int v = [] { const char *e = getenv("JPK_PAIR_GAP"); const int x = e ? atoi(e) : 3; return x < 2 ? 2 : x; }();
+    static const int v = (int)jpk_env_long("JPK_PAIR_GAP", 3, 2, INT_MAX);
     return v;
 }
 
@@ -2764,7 +2730,7 @@ struct PairSchedule {
     {
         if (prev_pair) gap = ((uint64_t)m_now * 100u > (uint64_t)m_prev * pair_rule_keep()) ? 2 * gap + 1 : pair_rule_gap();
         const bool sizeable = pair_rule_shift() >= 0 && m_now >= pair_rule_min() && m_now >= (uint32_t)((uint64_t)n >> pair_rule_shift());
-        bool pair = sizeable && round >= pair_rule_from() && round - last_pair >= gap && (uint64_t)m_now * 100u >= (uint64_t)m_prev * pair_rule_ratio();
+        bool pair = sizeable && round >= PAIR_FROM && round - last_pair >= gap && (uint64_t)m_now * 100u >= (uint64_t)m_prev * pair_rule_ratio();
         // ... and round 2 already when round 1 resolved next to nothing (99 % of its list is still there: periodic data, a block
         // that holds everything twice -- doubling is futile) unless the block is mostly runs, whose groups the run rule is splitting
         if (!pair && round == 2 && exact_from_round_1 && pair_rule_early() && sizeable && !runs_heavy && (uint64_t)m_now * 100u >= (uint64_t)m_prev * 99u) pair = true;
@@ -2881,7 +2847,7 @@ int build_sa(jpk_ctx *ctx, const uint8_t *T, uint32_t n, SaBufs &b)
     // JPK_SA_WAIT_ROUND: the first round that is enqueued on exact counts (default 1 since the context codes: round 1 of text starts with
     // 27 M of 67 M suffixes, round 2 with 49 K -- 48 windows, no large group; enqueued blind they were 65 K / 26 K workgroups per kernel and, in
     // round 2, 23 launches for nothing.  The wait is a few microseconds in front of a round; 3 = round 4's rule)
-    static const int wait_round = [] { const char *e = getenv("JPK_SA_WAIT_ROUND"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
+    static const int wait_round = (int)jpk_env_long("JPK_SA_WAIT_ROUND", 1, 1, INT_MAX);
     // remaining run lengths, only if round 0 left members of runs of >= depth equal bytes behind.  The host knows (round 6: it waits for
     // round 0's counts here, where round 1 would wait a moment later): the three kernels -- 130-160 us each in the timed loop to find
     // nothing to do -- are launched only when there is (enqueued blind they return at once otherwise)
@@ -2940,7 +2906,7 @@ int build_sa(jpk_ctx *ctx, const uint8_t *T, uint32_t n, SaBufs &b)
         // in round 1, of which text uses a few hundred: 21 us per launch to start and retire the rest, 0.3 ms per block.  The grid is capped
         // at JPK_LG_GRID (default 8192; 0 = the bound) unless the block is known to be mostly large groups -- runs, all-zero: there a
         // workgroup per piece is worth 4-7 %)
-        static const unsigned lg_cap = [] { const char *e = getenv("JPK_LG_GRID"); const long v = e ? atol(e) : 8192; return (unsigned)(v <= 0 ? CAP : v); }();
+        static const unsigned lg_cap = [] { const long v = jpk_env_long("JPK_LG_GRID", 8192, 0); return v ? (unsigned)v : CAP; }();
         const unsigned g_pc = cap_grid(pc_bound, 1, lg_heavy ? CAP : lg_cap);
         const unsigned g_tab = cap_grid(pc_bound << lg_db, SC_TILE, CAP);
         prev_pair = pair;
@@ -2955,11 +2921,10 @@ int build_sa(jpk_ctx *ctx, const uint8_t *T, uint32_t n, SaBufs &b)
             JPK_HIP(hipMemsetAsync(&b.state->pair_steps, 0, sizeof(uint32_t), st));
             JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_dist, dim3(g_win), dim3(TB), b.a_sa, b.a_grp, b.state, par, P, b.FH, b.LH);
             JPK_LAUNCH(ctx, PROF_SCAN, 0, k_win_scan1, dim3(1), dim3(WG1), b.FH, b.LH, b.PH, b.NH, b.state, par);
-            if (pair_rule_repair()) JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_repair, dim3(cap_grid(n, TB * 4, 8192)), dim3(TB), P, n, b.ISA, b.blk, b.bend, b.state, pair_rule_budget(n));
+            JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_repair, dim3(cap_grid(n, TB * 4, 8192)), dim3(TB), P, n, b.ISA, b.blk, b.bend, b.state, pair_rule_budget(n));
             JPK_LAUNCH(ctx, PROF_SCAN, 0, k_pair_first, dim3(cap_grid(n, CT, 4096)), dim3(TB), P, n, b.tB);
             JPK_LAUNCH(ctx, PROF_SCAN, 0, k_pair_scan, dim3(1), dim3(WG1), b.tB, n);
-            for (int it = 0; it < pair_rule_iters(); it++)     // later passes decide stretches that end in a group mixing two repeats (pair_verdict)
-                JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_fill, dim3(cap_grid(n, CT, CAP)), dim3(TB), P, n, b.tB, b.ISA, V, b.blk, b.bend, it);
+            JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_fill, dim3(cap_grid(n, CT, CAP)), dim3(TB), P, n, b.tB, b.ISA, V, b.blk, b.bend);
             JPK_LAUNCH(ctx, PROF_SA_KEYS, 0, k_pair_mark, dim3(g_win), dim3(TB), b.a_sa, b.a_grp, b.state, par, V, VL, BAD);
             JPK_LAUNCH(ctx, PROF_SA_RERANK, 0, k_pair_finish, dim3(g_win), dim3(TB), b.a_sa, b.a_grp, b.a_prev, b.state, par, b.PH, b.NH, VL, BAD, b.ISA, b.bwt, b.SA,
                        b.b_sa, b.b_grp, b.b_prev);
@@ -3201,14 +3166,7 @@ int jpk_fwd_bwt_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint8_t *
     JPK_TRY(jpk_arena_ensure(ctx, plan.need));
     Arena real(ctx, false);
     sa_layout(real, (size_t)nlen, b, var_keys_eligible((size_t)nlen, false));
-    // heavy-phase gate: a caller that goes on to the entropy stage (jpk_dev_block_compress) already holds it and releases it
-    // there; a stand-alone forward BWT holds it for the sort only
-    const bool outer = ctx->gate_held;
-    JPK_TRY(jpk_gate_enter(ctx));
-    int rc = build_sa(ctx, d_in, (uint32_t)nlen, b);
-    if (rc == JPK_OK) rc = jpk_gate_mark(ctx, ctx->stream);
-    if (!outer) jpk_gate_leave(ctx);
-    JPK_TRY(rc);
+    JPK_TRY(build_sa(ctx, d_in, (uint32_t)nlen, b));
     JPK_LAUNCH(ctx, PROF_BWT_GATHER, nlen, k_bwt_image, dim3(cap_grid((size_t)nlen, TB * 16, 4096)), dim3(TB), d_in, b.bwt, b.ISA, (uint32_t)nlen, d_out);
     hipLaunchKernelGGL(k_bwt_trailer, dim3(1), dim3(128), 0, ctx->stream, d_in, b.ISA, (uint32_t)nlen, (uint32_t)len, d_out);
     JPK_HIP(hipGetLastError());

@@ -1,6 +1,7 @@
 // common.hpp -- context, HBM arena and launch helpers shared by all translation units of libjampack_amd.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -51,12 +52,6 @@ struct jpk_ctx {
     static constexpr int INV_LANES_MAX = 16;
     hipStream_t inv_lane[INV_LANES_MAX] = {};
     hipEvent_t ev_inv[INV_LANES_MAX] = {};
-    // heavy-phase gate (abi.hip): events that mark the end of this context's GPU-saturating work -- [0] the suffix sort, [1..] the
-    // wide entropy kernels of each chunk group -- and whether this context currently holds the device's gate
-    static constexpr int GATE_EVENTS = 5;
-    hipEvent_t ev_gate[GATE_EVENTS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int gate_nev = 0;
-    bool gate_held = false;
     hipEvent_t ev_batch = nullptr;                 // jpk_dev_blocks_*: "the caller's stream has reached the batch call"
     hipEvent_t ev_sa[2] = {nullptr, nullptr};      // suffix sort: "the count round r left behind has reached the host"
     bool sa_stats_pending = false;   // per-round statistics of the last suffix sort are still in the pinned mailbox
@@ -106,6 +101,16 @@ void jpk_prof_resolve(jpk_ctx *ctx);   // call after a stream synchronisation
 
 static inline size_t jpk_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// The one way to read a numeric JPK_* environment switch: unset -> dflt, set -> atol, clamped to [lo, hi].  Callers keep the result in
+// a `static const` (the environment is read once per process).
+static inline long jpk_env_long(const char *name, long dflt, long lo = LONG_MIN, long hi = LONG_MAX)
+{
+    const char *e = getenv(name);
+    if (!e) return dflt;
+    const long v = atol(e);
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
 struct Arena {
     jpk_ctx *c;
     size_t need = 0;      // planning pass accumulates here
@@ -152,13 +157,6 @@ bool jpk_radix_onesweep();   // round 0's radix passes in the one-pass form (def
 int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n, uint64_t *keysA, uint32_t *valsA, uint64_t *keysB, uint32_t *valsB,
                              uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out, bool group, const uint8_t *slot_tag = nullptr, int tag_shift = 26,
                              uint32_t slot_n = 0);
-// Heavy-phase gate (experiment, off by default -- see gate_on() in abi.hip for the numbers): the GPU-saturating phases of the
-// blocks in flight on one device -- the suffix sort and the wide kernels of the entropy stage in front of the rANS chains --
-// run one block after the other on the GPU, in the order the blocks arrive here, while the chains (a few waves that run for
-// milliseconds) of earlier blocks run beside them.  A stream-level dependency, no host blocking on GPU
-// work: enter() makes ctx->stream wait for the previous holder's events; jpk_gate_mark() records one of this context's
-// events on a stream; leave() publishes them and releases the gate.  The gate is held while the heavy phases are being
-// ENQUEUED.
 // compress-side calls (forward BWT, rANS encode) of the contexts of ONE DEVICE that are running right now: the encoder cuts its
 // chains into fewer launch groups when other blocks are in flight on the same GPU (abi.hip)
 int jpk_compress_inflight_enter(int device);        // returns the count on that device including the caller
@@ -171,10 +169,6 @@ struct JpkCompressInflight {
     JpkCompressInflight(const JpkCompressInflight &) = delete;
     JpkCompressInflight &operator=(const JpkCompressInflight &) = delete;
 };
-int jpk_gate_enter(jpk_ctx *ctx);
-int jpk_gate_mark(jpk_ctx *ctx, hipStream_t stream);
-void jpk_gate_leave(jpk_ctx *ctx);
-void jpk_gate_forget(jpk_ctx *ctx);
 // moves the per-round statistics of the last suffix sort from the pinned mailbox into ctx->stats (call after a stream sync)
 void jpk_sa_stats_sync(jpk_ctx *ctx);
 

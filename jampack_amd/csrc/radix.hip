@@ -3,8 +3,8 @@
 // Per pass (reduce-then-scan):
 //   k_rs_hist     tile histograms from an LDS-staged 256-bin table      reads 8 B/elem
 //   exclusive sum over the digit-major [256][ntiles] table (scan.hip)
-//   k_rs_scatter  stable in-tile ranks by wave match-any + per-wave LDS counters, scatter
-//                                                                        reads 12 B, writes 12 B / elem
+//   k_rs_scatter_staged  stable in-tile ranks by wave match-any + per-wave LDS counters, the tile's pairs re-ordered in LDS,
+//                 scatter                                                reads 12 B, writes 12 B / elem
 // HBM-bound integer work: no MFMA.  Tiles are 4096 elements (256 threads x 16, wave-striped so that
 // every load instruction of a wave is one contiguous 512-B / 256-B segment).
 #include "common.hpp"
@@ -97,55 +97,6 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *__restri
 #pragma unroll
         for (int k = 0; k < RS_WAVES; k++) s += h[k][d];
         tilehist[(size_t)d * ntiles + blockIdx.x] = s;
-    }
-}
-
-template <bool SLOTS>
-__global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
-                                                          uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift,
-                                                          const uint32_t *__restrict__ tileoff, uint32_t ntiles)
-{
-    __shared__ uint32_t cnt[RS_WAVES][256];
-    __shared__ uint32_t gbase[256];
-    for (int i = threadIdx.x; i < RS_WAVES * 256; i += RS_THREADS) (&cnt[0][0])[i] = 0;
-    for (int d = threadIdx.x; d < 256; d += RS_THREADS) gbase[d] = tileoff[(size_t)d * ntiles + blockIdx.x];
-    __syncthreads();
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const size_t base = (size_t)blockIdx.x * RS_TILE + (size_t)w * (64 * RS_ITEMS) + l;
-    uint64_t key[RS_ITEMS];
-    uint32_t val[RS_ITEMS];
-    uint32_t rnk[RS_ITEMS];
-    const uint64_t lt = lanemask_lt();
-    rs_load_tile<SLOTS>(kin, vin, n, base, key, val);
-#pragma unroll
-    for (int it = 0; it < RS_ITEMS; it++) {
-        size_t i = base + (size_t)it * 64;
-        bool valid = i < n;
-        uint32_t d = (uint32_t)(key[it] >> shift) & 255u;
-        uint64_t m = match_any8(d, valid);
-        uint32_t below = (uint32_t)__popcll(m & lt);
-        uint32_t c = valid ? cnt[w][d] : 0;
-        rnk[it] = c + below;
-        // every lane of the match group has read cnt before its leader bumps it: same wave, program order
-        if (valid && below == 0) cnt[w][d] = c + (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    // exclusive scan across waves per digit
-    for (int d = threadIdx.x; d < 256; d += RS_THREADS) {
-        uint32_t s = 0;
-#pragma unroll
-        for (int k = 0; k < RS_WAVES; k++) { uint32_t t = cnt[k][d]; cnt[k][d] = s; s += t; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < RS_ITEMS; it++) {
-        size_t i = base + (size_t)it * 64;
-        if (i < n) {
-            uint32_t d = (uint32_t)(key[it] >> shift) & 255u;
-            size_t dst = (size_t)gbase[d] + cnt[w][d] + rnk[it];
-            kout[dst] = key[it];
-            vout[dst] = val[it];
-        }
     }
 }
 
@@ -346,7 +297,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_staged(const uint64_t
 //     out early; what a tile waits for is that its predecessors HAVE counted their keys.
 // (With the early aggregate the kernel takes 130 registers: three waves per SIMD, three tiles per CU.  Forced back to 128 and four --
 // amdgpu_waves_per_eu(4, 4) -- it measured 7.65 against 7.55 ms per forward BWT and 6 223 against 6 349 MB/s on the bench line; with
-// two tiles per CU (JPK_OS_LDS=16384) 7.72 ms: profiles/r06_scatter_ab.txt.  Three it is.)
+// two tiles per CU (a 16 KB dynamic LDS reservation) 7.72 ms: profiles/r06_scatter_ab.txt.  Three it is.)
 template <bool SLOTS, bool FULL>
 __global__ __launch_bounds__(RS_THREADS) void k_os_scatter(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
                                                           uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift, uint32_t ntiles, OsArgs os)
@@ -372,9 +323,7 @@ void launch_os_scatter(jpk_ctx *ctx, const uint64_t *kin, const uint32_t *vin, u
                        const OsArgs &os)
 {
     const uint32_t nfull = (uint32_t)(n / RS_TILE);
-    // JPK_OS_LDS: extra dynamic LDS per workgroup (bytes), i.e. fewer tiles resident per CU (experiments: 16384 = two per CU)
-    static const size_t extra_lds = [] { const char *e = getenv("JPK_OS_LDS"); const long v = e ? atol(e) : 0; return (size_t)(v < 0 ? 0 : (v > 120000 ? 120000 : v)); }();
-    if (nfull) JPK_LAUNCH_LDS(ctx, PROF_RS_SCATTER, (size_t)nfull * RS_TILE, extra_lds, (k_os_scatter<SLOTS, true>), dim3(nfull), dim3(RS_THREADS), kin, vin, kout, vout, n, shift, ntiles, os);
+    if (nfull) JPK_LAUNCH(ctx, PROF_RS_SCATTER, (size_t)nfull * RS_TILE, (k_os_scatter<SLOTS, true>), dim3(nfull), dim3(RS_THREADS), kin, vin, kout, vout, n, shift, ntiles, os);
     if (nfull < ntiles) JPK_LAUNCH(ctx, PROF_RS_SCATTER, n - (size_t)nfull * RS_TILE, (k_os_scatter<SLOTS, false>), dim3(1), dim3(RS_THREADS), kin, vin, kout, vout, n, shift,
                                    ntiles, os);
 }
@@ -420,13 +369,6 @@ void launch_rs_scatter_staged(jpk_ctx *ctx, const uint64_t *kin, const uint32_t 
                                    shift, tileoff, ntiles, nfull);
 }
 
-// JPK_RS_STAGED=0 keeps the direct scatter (register -> global) for comparison
-bool rs_staged()
-{
-    static const bool on = [] { const char *e = getenv("JPK_RS_STAGED"); return e ? atoi(e) != 0 : true; }();
-    return on;
-}
-
 }  // namespace
 
 size_t jpk_radix_scratch_words(size_t n)
@@ -446,7 +388,7 @@ size_t jpk_radix_scratch_words(size_t n)
 // alternations out of five, groups of 1 MiB blocks +8 %, of 8 MiB blocks +2..10 % (profiles/r04_onesweep_packed.txt).  Default since then.
 static bool rs_onesweep()
 {
-    static const bool on = [] { const char *e = getenv("JPK_ONESWEEP"); return e ? atoi(e) != 0 : true; }();
+    static const bool on = jpk_env_long("JPK_ONESWEEP", 1) != 0;
     return on;
 }
 bool jpk_radix_onesweep() { return rs_onesweep(); }
@@ -468,8 +410,7 @@ int jpk_radix_sort_pairs_u64_nocopy(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals
     for (int p = 0; p < nshifts; p++) {
         JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), ki, n, shifts[p], hist, ntiles);
         JPK_TRY(jpk_exclusive_sum_u32(ctx, hist, hist, table, scan_scratch, nullptr));
-        if (rs_staged()) launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shifts[p], hist, ntiles);
-        else JPK_LAUNCH(ctx, PROF_RS_SCATTER, n, (k_rs_scatter<false>), dim3(ntiles), dim3(RS_THREADS), ki, vi, ko, vo, n, shifts[p], hist, ntiles);
+        launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shifts[p], hist, ntiles);
         uint64_t *tk = ki; ki = ko; ko = tk;
         uint32_t *tv = vi; vi = vo; vo = tv;
     }
@@ -523,10 +464,9 @@ int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n32, uint64_t *keysA, uint32
         uint32_t *H = statusB + table, *gdig = H + OS_PASSES * 256, *tickets = gdig + OS_PASSES * 256;
         JPK_HIP(hipMemsetAsync(statusA, 0, table * 4, ctx->stream));
         JPK_HIP(hipMemsetAsync(statusB, 0, (table + OS_PASSES * 256 + OS_PASSES * 256 + 64) * 4, ctx->stream));
-        {   // (every workgroup ends with up to 8 x 256 atomics on the same counters: against LDS atomics per key -- JPK_DIGITS_GRID, default 2048: 256 / 512 / 768 / 2048 / 4096 / 8192 / 16384 workgroups take 519 / 299 / 227 / 167 / 174 / 206 / 336 us)
-            static const uint32_t dg = [] { const char *e = getenv("JPK_DIGITS_GRID"); const long v = e ? atol(e) : 2048; return (uint32_t)(v < 1 ? 1 : v); }();
-            JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_os_digits, dim3(ntiles < dg ? (ntiles ? ntiles : 1) : dg), dim3(RS_THREADS), keysA, n32, H, npass);
-        }
+        // (every workgroup ends with up to 8 x 256 atomics on the same counters: against LDS atomics per key -- 256 / 512 / 768 / 2048 / 4096 / 8192 / 16384 workgroups take 519 / 299 / 227 / 167 / 174 / 206 / 336 us)
+        constexpr uint32_t dg = 2048;
+        JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_os_digits, dim3(ntiles < dg ? (ntiles ? ntiles : 1) : dg), dim3(RS_THREADS), keysA, n32, H, npass);
         JPK_LAUNCH(ctx, PROF_SCAN, 0, k_os_prefix, dim3(1), dim3(256), H, gdig, npass);
         for (int p = 0; p < npass; p++) {
             const int shift = p < 7 ? 8 * (p + 1) : 0;
@@ -555,15 +495,12 @@ int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n32, uint64_t *keysA, uint32
         if (p == 0) {
             // (the first pass's tile histogram was counted by k_pack_keys, whose tiles are this sort's: hist = scratch, digit-major)
             JPK_TRY(jpk_exclusive_sum_u32(ctx, hist, hist, table, scan_scratch, nullptr));
-            if (rs_staged()) launch_rs_scatter_staged<true>(ctx, keysA, nullptr, keysB, valsB, n, shift, hist, ntiles);
-            else JPK_LAUNCH(ctx, PROF_RS_SCATTER, n, (k_rs_scatter<true>), dim3(ntiles), dim3(RS_THREADS), (const uint64_t *)keysA, (const uint32_t *)nullptr,
-                       keysB, valsB, n, shift, hist, ntiles);
+            launch_rs_scatter_staged<true>(ctx, keysA, nullptr, keysB, valsB, n, shift, hist, ntiles);
             continue;
         }
         JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), (const uint64_t *)ki, n, shift, hist, ntiles);
         JPK_TRY(jpk_exclusive_sum_u32(ctx, hist, hist, table, scan_scratch, nullptr));
-        if (rs_staged()) launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shift, hist, ntiles);
-        else JPK_LAUNCH(ctx, PROF_RS_SCATTER, n, (k_rs_scatter<false>), dim3(ntiles), dim3(RS_THREADS), (const uint64_t *)ki, (const uint32_t *)vi, ko, vo, n, shift, hist, ntiles);
+        launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shift, hist, ntiles);
         uint64_t *tk = ki; ki = ko; ko = tk;
         uint32_t *tv = vi; vi = vo; vo = tv;
     }

@@ -80,10 +80,9 @@ if [ "${JPK_COLLECT_AB:-0}" = 1 ]; then      # (round 5's A/B sections: unchange
   for k in text_survey text_wide; do for v in 1 0; do echo -n "$k JPK_VARKEYS=$v  "; JPK_VARKEYS=$v python3 tools/fwd_once.py $k 3 2>/dev/null | tail -1; done; done
   echo "# ... and by the order of the code (JPK_KEY_ORDER: 0 = the round's first form, 1, 2 = default)"
   for k in text_survey text_wide; do for v in 0 1 2; do echo -n "$k JPK_KEY_ORDER=$v  "; JPK_KEY_ORDER=$v python3 tools/fwd_once.py $k 10 2>/dev/null | tail -1; done; done ) > "$OUT/var_keys.txt"
-( echo "# the pair rule (k_pair_*) against plain prefix doubling (JPK_PAIR_SHIFT=-1) and without the repair walk (JPK_PAIR_REPAIR=0): forward BWT of one 64 MiB block"
+( echo "# the pair rule (k_pair_*) against plain prefix doubling (JPK_PAIR_SHIFT=-1): forward BWT of one 64 MiB block"
   for k in repeat silesia runs text; do
     echo -n "$k default            "; python3 tools/fwd_once.py $k 3 2>/dev/null | tail -1
-    echo -n "$k JPK_PAIR_REPAIR=0  "; JPK_PAIR_REPAIR=0 python3 tools/fwd_once.py $k 3 2>/dev/null | tail -1
     echo -n "$k JPK_PAIR_SHIFT=-1  "; JPK_PAIR_SHIFT=-1 python3 tools/fwd_once.py $k 3 2>/dev/null | tail -1
   done
   echo "# config 5: bench.py --workload silesia --block-mib 256 --steps 4 --warmup 1 --no-extras"
