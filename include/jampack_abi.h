@@ -264,6 +264,42 @@ JPK_API int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, 
  * or -1 (JPK_OK).  No device call.  Pointers other than in may be NULL. */
 JPK_API int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame);
 
+/* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
+/* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the
+ * 64-bit raw offset (the prefix sum of the raw sizes).  jpk_dev_jam_index_create walks an archive in HBM, jpk_jam_index_create one
+ * in host memory (no device call); both apply the checks of jpk_dev_jam_decompress's walk / jpk_jam_frames.  An archive with a bad
+ * frame gives JPK_OK and an index over the frames in front of the first bad one -- a damaged archive stays readable up to the damage --
+ * with *bad_frame = its position (-1: none; may be NULL).  The index keeps no pointer to the archive, is immutable after creation and
+ * may be used from several contexts and threads; jpk_jam_index_destroy releases it (NULL is allowed). */
+typedef struct jpk_jam_index jpk_jam_index;
+JPK_API int jpk_dev_jam_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
+JPK_API int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
+/* *frames = the indexed frames, *raw_len = their raw bytes, *archive_len = the in_len the index was made from.  Pointers may be NULL. */
+JPK_API int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len);
+/* frame k: its raw offset and raw size, where its payload starts in the archive and the payload's size; JPK_E_ARG for k out of range */
+JPK_API int jpk_jam_index_frame(const jpk_jam_index *index, int32_t k, int64_t *raw_off, int64_t *raw, int64_t *payload_off, int32_t *psize);
+JPK_API void jpk_jam_index_destroy(jpk_jam_index *index);
+/* n ranges in raw coordinates, [off[r], off[r] + len[r]) delivered at d_out[r] (a device pointer of any alignment; the buffers must
+ * not overlap).  in_len must be the index's archive length and every range must satisfy 0 <= off, 0 <= len, off + len <= raw_len:
+ * JPK_E_ARG otherwise, before any device work, nothing written.  len == 0 is legal anywhere in [0, raw_len] and touches no frame.
+ * Ranges may be unsorted, overlapping or identical.
+ * Cost: the crc of a frame covers the whole frame, so every frame a range touches is decoded whole -- ONCE per call, however many
+ * ranges want it -- through jpk_dev_blocks_decompress, in passes of at most 128 touched frames and 4 GiB of raw bytes.  A frame that
+ * lies wholly inside a range is decoded straight into that range's buffer (as jpk_dev_jam_decompress decodes in place; further ranges
+ * copy from there), every other one into a padded slot of a scratch buffer of ctx (the raw bytes of the pass's partial frames).  Per
+ * pass: the batch decode, one batched checksum of the touched frames against their header crcs, one gather launch for all pieces of
+ * verified frames.  Nothing outside [d_out[r], d_out[r] + len[r]) is written; a frame no range touches is neither decoded nor checked.
+ * status[r] = JPK_OK, or the status of the lowest-numbered frame of range r that failed to decode or failed its crc (JPK_E_CORRUPT);
+ * ranges whose frames are all good are delivered whatever happens to the others, the buffer of a failed range is unspecified.
+ * *bad_frame = the lowest failing frame any range touches, or -1 (may be NULL).  Returns as jpk_dev_blocks_decompress: with a
+ * status array JPK_OK once the arguments were accepted, with status == NULL the first failing range's status. */
+JPK_API int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                             uint8_t *const *d_out, int32_t *status, int32_t *bad_frame);
+/* host-buffer form through the calling thread's pooled context: only the payloads of the touched frames are staged to the device,
+ * pass by pass, and only the ranges travel back; same contract (the arguments are checked before a device is looked for) */
+JPK_API int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out,
+                         int32_t *status, int32_t *bad_frame);
+
 /* ---- kernel-level probes used by tests/ and bench.py (device buffers) ------------------------------------ */
 /* Comparator for BASELINE config 3 ("120-way parallel LF-map"): the reference's own GPU kernel shape -- 120 threads, one per
  * stored index, p = Map[p-1] (CUDAInverse<<<40,3>>>, bwt.cpp:8-19, 176-183, 226-229) -- on the same Map.  Same bytes as

@@ -216,6 +216,65 @@ def jam_decompress(stream) -> np.ndarray:
     return out[: n.value]
 
 
+class JamIndex:
+    """jpk_jam_index: the frame table of one archive -- `frames`, `raw_len`, `archive_len`, `bad_frame` (-1: the whole archive is
+    indexed; otherwise the index covers the frames in front of that one) and `frame(k)`.  Keeps no reference to the archive."""
+
+    def __init__(self, handle, bad_frame: int):
+        self._h = handle
+        k, raw, alen = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        _chk(lib().jpk_jam_index_info(self._h, C.byref(k), C.byref(raw), C.byref(alen)), "jpk_jam_index_info")
+        self.frames, self.raw_len, self.archive_len, self.bad_frame = k.value, raw.value, alen.value, int(bad_frame)
+
+    def frame(self, k: int):
+        """(raw offset, raw size, payload offset, payload size) of frame k"""
+        ro, raw, po, ps = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _chk(lib().jpk_jam_index_frame(self._h, k, C.byref(ro), C.byref(raw), C.byref(po), C.byref(ps)), "jpk_jam_index_frame")
+        return ro.value, raw.value, po.value, ps.value
+
+    def close(self):
+        if self._h:
+            lib().jpk_jam_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def jam_index(stream) -> JamIndex:
+    """jpk_jam_index_create: the index of an archive in host memory (no device call)"""
+    c = _np_u8(stream)
+    h, bad = C.c_void_p(), C.c_int32(-1)
+    _chk(lib().jpk_jam_index_create(_ptr(c), len(c), C.byref(h), C.byref(bad)), "jpk_jam_index_create")
+    return JamIndex(h, bad.value)
+
+
+def _ranges(ranges):
+    n = len(ranges)
+    L = C.c_int64 * max(n, 1)
+    return n, L(*[int(o) for o, _ in ranges]), L(*[int(l) for _, l in ranges])
+
+
+def jam_read(stream, ranges, index: JamIndex | None = None):
+    """jpk_jam_read: the byte ranges [(raw offset, length), ...] of an archive in host memory -> list of numpy arrays.  Only the frames
+    the ranges touch are staged and decoded.  Raises JampackError with the first failing range's status."""
+    c = _np_u8(stream)
+    ix = index if index is not None else jam_index(c)
+    try:
+        n, off, ln = _ranges(ranges)
+        outs = [np.empty(max(int(l), 0), dtype=np.uint8) for _, l in ranges]
+        P = C.c_void_p * max(n, 1)
+        bad = C.c_int32(-1)
+        _chk(lib().jpk_jam_read(ix._h, _ptr(c), len(c), n, off, ln, P(*[o.ctypes.data for o in outs]), None, C.byref(bad)), "jpk_jam_read")
+        return outs
+    finally:
+        if index is None:
+            ix.close()
+
+
 class Lz77:
     """Decoder side of `class Lz77` (lz77.hpp:21-22); host code."""
 
@@ -421,6 +480,26 @@ class Context:
             return n.value, nf.value, bf.value, int(rc)
         _chk(rc, "jpk_dev_jam_decompress")
         return n.value, nf.value, bf.value
+
+    def jam_index(self, d_in, in_len) -> JamIndex:
+        """jpk_dev_jam_index_create: the index of an archive in HBM"""
+        h, bad = C.c_void_p(), C.c_int32(-1)
+        _chk(lib().jpk_dev_jam_index_create(self._h, _dptr(d_in), in_len, C.byref(h), C.byref(bad)), "jpk_dev_jam_index_create")
+        return JamIndex(h, bad.value)
+
+    def jam_read(self, index: JamIndex, d_in, in_len, ranges, d_outs, check: bool = True):
+        """jpk_dev_jam_read: the ranges [(raw offset, length), ...] of the archive d_in[0..in_len) into the device buffers d_outs
+        -> (status list, bad frame or -1).  check=True raises JampackError with the first failing range's status."""
+        n, off, ln = _ranges(ranges)
+        P = C.c_void_p * max(n, 1)
+        st, bad = (C.c_int32 * max(n, 1))(), C.c_int32(-1)
+        _chk(lib().jpk_dev_jam_read(self._h, index._h, _dptr(d_in), in_len, n, off, ln, P(*[_dptr(x) for x in d_outs]), st, C.byref(bad)), "jpk_dev_jam_read")
+        status = list(st)[:n]
+        if check:
+            for r, s in enumerate(status):
+                if s != 0:
+                    raise JampackError(s, f"jpk_dev_jam_read: range {r} (frame {bad.value})")
+        return status, bad.value
 
     def rank_encode(self, d_t, d_freq, n):
         _chk(lib().jpk_dev_rank_encode(self._h, _dptr(d_t), _dptr(d_freq), n), "jpk_dev_rank_encode")

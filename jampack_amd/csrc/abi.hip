@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <deque>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <vector>
 
@@ -2150,4 +2151,303 @@ extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *ou
         return JPK_E_CORRUPT;
     }
     return JPK_OK;
+}
+
+// ---- range reads of a .jam archive: jpk_jam_index + jpk_dev_jam_read / jpk_jam_read -----------------------------------------------
+// The index is the frame table of the walks with the 64-bit prefix sum of the raw sizes.  A read maps every range to the frames it
+// touches, decodes each touched frame ONCE -- in place in the first range that contains it whole, otherwise into a padded slot of
+// ctx->jam_scratch -- in passes with the limits of the archive calls, checks every decoded frame against its header crc, and delivers
+// the pieces of the verified frames with one k_jam_gather launch per pass.  A frame no range touches is neither decoded nor checked.
+struct jpk_jam_index {
+    struct Frame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
+    std::vector<Frame> fr;
+    std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
+    int64_t archive_len = 0;
+    int32_t bad = -1;
+};
+
+namespace {
+jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad)
+{
+    jpk_jam_index *ix = new (std::nothrow) jpk_jam_index;
+    if (!ix) return nullptr;
+    try {
+        ix->fr.reserve(fr.size());
+        ix->raw_off.reserve(fr.size() + 1);
+    } catch (const std::bad_alloc &) { delete ix; return nullptr; }
+    int64_t raw = 0;
+    for (const JamFrame &f : fr) {
+        ix->fr.push_back(jpk_jam_index::Frame{f.payload_off, f.psize, f.crc, f.block_size, f.raw});
+        ix->raw_off.push_back(raw);
+        raw += f.raw;
+    }
+    ix->raw_off.push_back(raw);
+    ix->archive_len = in_len;
+    ix->bad = bad;
+    return ix;
+}
+
+// the argument checks of both read entries: nothing is touched before they pass
+int jam_read_check(const jpk_jam_index *ix, const void *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out)
+{
+    if (!ix || n < 0 || in_len != ix->archive_len || (n > 0 && (!off || !len || !out))) return JPK_E_ARG;
+    const int64_t raw_len = ix->raw_off.back();
+    for (int32_t r = 0; r < n; r++) {
+        if (off[r] < 0 || len[r] < 0 || off[r] > raw_len || len[r] > raw_len - off[r]) return JPK_E_ARG;
+        if (len[r] > 0 && (!out[r] || !in)) return JPK_E_ARG;
+    }
+    return JPK_OK;
+}
+
+// The read itself.  The archive is d_in (HBM) or, when d_in is NULL, h_in (host memory: the payloads of a pass's frames are staged
+// through ctx->stage_in); d_out[] are device buffers in both cases.  status has n entries.
+int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
+                    uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    const size_t F = ix->fr.size();
+    const std::vector<int64_t> &ro = ix->raw_off;
+    // frames [first[r], last[r]] of range r; pieces per frame (a piece = the part of one frame one range wants); the in-place home of
+    // a frame: inside the first range that contains it whole
+    std::vector<int32_t> first((size_t)n, -1), last((size_t)n, -1);
+    std::vector<size_t> start(F + 1, 0);
+    std::vector<uint8_t *> home(F, nullptr);
+    for (int32_t r = 0; r < n; r++) {
+        status[r] = JPK_OK;
+        if (len[r] == 0) continue;
+        const int64_t a = off[r], b = a + len[r];
+        first[r] = (int32_t)(std::upper_bound(ro.begin(), ro.end(), a) - ro.begin()) - 1;
+        last[r] = (int32_t)(std::lower_bound(ro.begin(), ro.end(), b) - ro.begin()) - 1;
+        for (int32_t f = first[r]; f <= last[r]; f++) {
+            if (ix->fr[(size_t)f].raw == 0) continue;
+            start[(size_t)f + 1]++;
+            if (!home[(size_t)f] && ro[(size_t)f] >= a && ro[(size_t)f + 1] <= b) home[(size_t)f] = d_out[r] + (ro[(size_t)f] - a);
+        }
+    }
+    std::vector<size_t> touched;
+    for (size_t f = 0; f < F; f++) {
+        if (start[f + 1]) touched.push_back(f);
+        start[f + 1] += start[f];
+    }
+    std::vector<int32_t> piece_range(start[F]);
+    {
+        std::vector<size_t> fill(start.begin(), start.end() - 1);
+        for (int32_t r = 0; r < n; r++)
+            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
+                if (ix->fr[(size_t)f].raw) piece_range[fill[(size_t)f]++] = r;
+    }
+    std::vector<int32_t> fstat(F, JPK_OK);
+    const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    for (size_t k = 0; k < touched.size();) {
+        size_t e = k;
+        uint64_t pass_raw = 0;
+        while (e < touched.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || pass_raw + (uint64_t)ix->fr[touched[e]].raw <= JAM_PASS_RAW))
+            pass_raw += (uint64_t)ix->fr[touched[e++]].raw;
+        const int m = (int)(e - k);
+        size_t npieces = 0, slot_bytes = 0, stage_bytes = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            npieces += start[f + 1] - start[f];
+            if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
+        }
+        const size_t o_slots = o_tab + jpk_align(npieces * sizeof(JamGatherPiece));
+        JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, o_slots + slot_bytes));
+        if (!d_in) JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+        JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
+        std::vector<const uint8_t *> ins((size_t)m);
+        std::vector<uint8_t *> outs((size_t)m);
+        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m);
+        size_t slot = o_slots, stage = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            const jpk_jam_index::Frame &fr = ix->fr[f];
+            if (d_in) ins[i] = d_in + fr.payload_off;
+            else {
+                JPK_HIP(hipMemcpyAsync(ctx->stage_in + stage, h_in + fr.payload_off, (size_t)fr.psize, hipMemcpyHostToDevice, ctx->stream));
+                ins[i] = ctx->stage_in + stage;
+                stage += jpk_align((size_t)fr.psize + 64);
+            }
+            lens[i] = fr.psize; caps[i] = (int32_t)fr.raw;
+            if (home[f]) outs[i] = home[f];
+            else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
+        }
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
+        // one batched checksum of the frames that decoded, against their header crcs
+        std::vector<int> dec;
+        std::vector<const uint8_t *> cin;
+        std::vector<int32_t> clen;
+        for (int i = 0; i < m; i++) {
+            if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
+            dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
+        }
+        if (!dec.empty()) {
+            std::vector<uint32_t> crc(dec.size());
+            JPK_TRY(jpk_checksums_device(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc));
+            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, dec.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            for (size_t q = 0; q < dec.size(); q++)
+                if (crc[q] != ix->fr[touched[k + (size_t)dec[q]]].crc) fstat[touched[k + (size_t)dec[q]]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
+        }
+        // the pieces of the verified frames (the one a frame was decoded into in place is already where it belongs)
+        std::vector<JamGatherPiece> tab;
+        tab.reserve(npieces);
+        uint64_t words = 0, bytes = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            if (fstat[f] != JPK_OK) continue;
+            const int64_t raw = ix->fr[f].raw;
+            const uint8_t *hi = home[f] ? outs[i] + raw : outs[i] + ((raw + 15) & ~(int64_t)15) + 16;
+            for (size_t q = start[f]; q < start[f + 1]; q++) {
+                const int32_t r = piece_range[q];
+                const int64_t a = std::max(ro[f], off[r]), b = std::min(ro[f + 1], off[r] + len[r]);
+                JamGatherPiece pc;
+                pc.src = outs[i] + (a - ro[f]); pc.dst = d_out[r] + (a - off[r]); pc.len = (uint64_t)(b - a); pc.word0 = words;
+                pc.src_lo = outs[i]; pc.src_hi = hi;
+                if (pc.src == pc.dst) continue;
+                words += (((uint64_t)(uintptr_t)pc.dst & 15u) + pc.len + 15u) / 16u;
+                bytes += pc.len;
+                tab.push_back(pc);
+            }
+        }
+        if (!tab.empty()) {
+            JPK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(JamGatherPiece), hipMemcpyHostToDevice, ctx->stream));
+            JPK_TRY(jpk_jam_gather_enqueue(ctx, d_tab, (uint32_t)tab.size(), words, bytes));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        k = e;
+    }
+    int32_t bad = -1;
+    for (size_t f : touched) if (fstat[f] != JPK_OK) { bad = (int32_t)f; break; }
+    if (bad >= 0)
+        for (int32_t r = 0; r < n; r++)
+            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
+                if (ix->fr[(size_t)f].raw && fstat[(size_t)f] != JPK_OK) { status[r] = fstat[(size_t)f]; break; }
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+// n and the number of pieces are the caller's: the host tables of a read that does not fit in memory end in JPK_E_ALLOC, not in an
+// exception that leaves through the C ABI
+int jam_read_run(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
+                 uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    try {
+        return jam_read_pieces(ctx, ix, d_in, h_in, n, off, len, d_out, status, bad_frame);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);             // nothing queued may outlive the tables it reads
+        return JPK_E_ALLOC;
+    }
+}
+
+// no range wants a byte: nothing to decode, every status JPK_OK
+bool jam_read_empty(int32_t n, const int64_t *len, int32_t *status)
+{
+    for (int32_t r = 0; r < n; r++) if (len[r] > 0) return false;
+    if (status) for (int32_t r = 0; r < n; r++) status[r] = JPK_OK;
+    return true;
+}
+
+int jam_read_result(int32_t n, const int32_t *st, int32_t *status)
+{
+    if (status) { for (int32_t r = 0; r < n; r++) status[r] = st[r]; return JPK_OK; }
+    for (int32_t r = 0; r < n; r++) if (st[r] != JPK_OK) return st[r];
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!index || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
+    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    if (!index || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad);
+    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len)
+{
+    if (!index) return JPK_E_ARG;
+    if (frames) *frames = (int32_t)index->fr.size();
+    if (raw_len) *raw_len = index->raw_off.back();
+    if (archive_len) *archive_len = index->archive_len;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_frame(const jpk_jam_index *index, int32_t k, int64_t *raw_off, int64_t *raw, int64_t *payload_off, int32_t *psize)
+{
+    if (!index || k < 0 || (size_t)k >= index->fr.size()) return JPK_E_ARG;
+    if (raw_off) *raw_off = index->raw_off[(size_t)k];
+    if (raw) *raw = index->fr[(size_t)k].raw;
+    if (payload_off) *payload_off = index->fr[(size_t)k].payload_off;
+    if (psize) *psize = index->fr[(size_t)k].psize;
+    return JPK_OK;
+}
+
+extern "C" void jpk_jam_index_destroy(jpk_jam_index *index) { delete index; }
+
+extern "C" int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                                uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    // (JPK_ENTER taken apart: the argument checks come before the first device call)
+    if (!ctx) return JPK_E_ARG;
+    JPK_TRY(jam_read_check(index, d_in, in_len, n, off, len, d_out));
+    JPK_HIP(hipSetDevice(ctx->device));
+    if (bad_frame) *bad_frame = -1;
+    if (jam_read_empty(n, len, status)) return JPK_OK;
+    std::vector<int32_t> st;
+    try { st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+    JPK_TRY(jam_read_run(ctx, index, d_in, nullptr, n, off, len, d_out, st.data(), bad_frame));
+    return jam_read_result(n, st.data(), status);
+}
+
+extern "C" int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out,
+                            int32_t *status, int32_t *bad_frame)
+{
+    JPK_TRY(jam_read_check(index, in, in_len, n, off, len, out));
+    if (bad_frame) *bad_frame = -1;
+    if (jam_read_empty(n, len, status)) return JPK_OK;
+    jpk_ctx *ctx;
+    JPK_TRY(tls_ctx(&ctx));
+    JPK_HIP(hipSetDevice(ctx->device));
+    // the ranges side by side in ctx->stage_res (a range may start at any address); only they travel back
+    std::vector<uint8_t *> d_out;
+    std::vector<int32_t> st;
+    try { d_out.resize((size_t)n); st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+    int64_t total = 0;
+    for (int32_t r = 0; r < n; r++) total += len[r];
+    JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)total + 64));
+    total = 0;
+    for (int32_t r = 0; r < n; r++) { d_out[(size_t)r] = ctx->stage_res + total; total += len[r]; }
+    JPK_TRY(jam_read_run(ctx, index, nullptr, in, n, off, len, d_out.data(), st.data(), bad_frame));
+    // few ranges: one copy each; many small ones: one copy of all of them and the split on the host
+    if (n <= 16 || total > (64ll << 20)) {
+        for (int32_t r = 0; r < n; r++)
+            if (len[r] > 0 && st[(size_t)r] == JPK_OK) JPK_HIP(hipMemcpyAsync(out[r], d_out[(size_t)r], (size_t)len[r], hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+    } else {
+        std::vector<uint8_t> all;
+        try { all.resize((size_t)total); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+        JPK_HIP(hipMemcpyAsync(all.data(), ctx->stage_res, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        for (int32_t r = 0; r < n; r++)
+            if (len[r] > 0 && st[(size_t)r] == JPK_OK) memcpy(out[r], all.data() + (d_out[(size_t)r] - ctx->stage_res), (size_t)len[r]);
+    }
+    return jam_read_result(n, st.data(), status);
 }

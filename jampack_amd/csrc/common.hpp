@@ -220,3 +220,8 @@ struct JamPackFrame { const uint8_t *slot; uint64_t off; int32_t psize; int32_t 
 constexpr int JPK_JAM_PASS_FRAMES = 128;                     // frames per pass of the archive calls (and per pack launch)
 // writes the frames d_frames[0..n) (n <= JPK_JAM_PASS_FRAMES), headers from d_crc[i] / psize / block_size, into d_out[0..total).  Enqueued.
 int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, const uint32_t *d_crc, int32_t block_size, uint8_t *d_out, uint64_t total);
+// One piece of a range read (jpk_dev_jam_read): len decoded bytes from src to dst, any alignment.  word0 = the aligned 16-byte destination
+// words of the pieces in front of it (a piece has (dst % 16 + len + 15) / 16); [src_lo, src_hi) = the bytes that may be read around src.
+struct JamGatherPiece { const uint8_t *src; uint8_t *dst; uint64_t len; uint64_t word0; const uint8_t *src_lo; const uint8_t *src_hi; };
+// delivers d_pieces[0..n) (len > 0 each, `words` destination words and `bytes` bytes in all) with one launch.  Enqueued.
+int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_t n, uint64_t words, uint64_t bytes);

@@ -2,7 +2,9 @@
 //   k_jam_walk   one wave walks the frame headers of an archive in HBM (DecompReadBlock's checks, jampack.cpp:140-163)
 //   k_jam_pack   writes a run of frames -- "JAM" | u32 crc | i32 payload size | i32 BlockSize | payload, little-endian --
 //                from payload slots in scratch, organised by destination: a thread owns aligned 16-byte words of the output
-// The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress (abi.hip).
+//   k_jam_gather delivers the pieces of a range read -- (source, destination, length) of decoded bytes -- organised by destination
+//                in the same way: a thread owns aligned 16-byte words of a piece's destination
+// The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress / jpk_dev_jam_read (abi.hip).
 #include "common.hpp"
 
 namespace {
@@ -138,6 +140,50 @@ __global__ __launch_bounds__(PACK_TB) void k_jam_pack(const JamPackFrame *__rest
     }
 }
 
+// Organised by destination, piece by piece: word w of piece i is the aligned 16 bytes at base_i + 16 (w - word0_i) (base_i = the piece's
+// dst rounded down to 16), and word0 is the prefix sum of the pieces' word counts, so a thread finds the piece of its word by a search
+// over word0.  A word that lies wholly inside the piece is written with one 16-byte store -- fed by load16_unaligned when its two
+// aligned loads stay inside [src_lo, src_hi), the bytes the source may be read at (a scratch slot with its padding; a frame decoded
+// in place in a caller's buffer has none, so the words at its ends are assembled byte by byte); the partial words at the piece's two
+// ends use byte stores.  Nothing outside [dst, dst + len) is written, so pieces that share a destination word do not disturb each other.
+// The search is log2(n) reads of 48-byte entries per word, through L2 (the table of a call is not bounded, so it is not staged in LDS as
+// k_jam_pack's 128 frames are): neighbouring threads walk the same entries, and next to the decode of whole frames that every read
+// pays for, the gather is small (profiles/jam_read_ranges.txt, variant c).
+__global__ __launch_bounds__(PACK_TB) void k_jam_gather(const JamGatherPiece *__restrict__ pieces, uint32_t n, uint64_t words)
+{
+    for (uint64_t w = (uint64_t)blockIdx.x * PACK_TB + threadIdx.x; w < words; w += (uint64_t)gridDim.x * PACK_TB) {
+        uint32_t lo = 0, hi = n;                                              // piece of word w: the last with word0 <= w
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (pieces[mid].word0 <= w) lo = mid; else hi = mid; }
+        const JamGatherPiece pc = pieces[lo];
+        const uintptr_t d = (uintptr_t)pc.dst, base = d & ~(uintptr_t)15;
+        const int64_t p0 = (int64_t)((w - pc.word0) * 16u) - (int64_t)(d - base);   // piece position of the word's first byte (< 0: before the piece)
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + (w - pc.word0) * 16u);
+        if (p0 >= 0 && (uint64_t)p0 + 16u <= pc.len) {
+            const uint8_t *src = pc.src + p0;
+            const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
+            uint4 v;
+            if (a >= (uintptr_t)pc.src_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= (uintptr_t)pc.src_hi) {
+                v = load16_unaligned(src);
+            } else {
+                uint32_t b[16];
+#pragma unroll
+                for (int j = 0; j < 16; j++) b[j] = src[j];
+                v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+                v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+                v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+                v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            }
+            *reinterpret_cast<uint4 *>(dst) = v;
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t p = p0 + j;
+            if (p >= 0 && (uint64_t)p < pc.len) dst[j] = pc.src[p];
+        }
+    }
+}
+
 }  // namespace
 
 int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
@@ -156,6 +202,16 @@ int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, cons
     uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
     if (grid > 8192) grid = 8192;                                              // grid-stride beyond: 2M threads cover a pass
     JPK_LAUNCH(ctx, PROF_JAM, total, k_jam_pack, dim3((unsigned)grid), dim3(PACK_TB), d_frames, (uint32_t)n, d_crc, block_size, d_out, total);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
+
+int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_t n, uint64_t words, uint64_t bytes)
+{
+    if (n == 0 || words == 0) return JPK_OK;
+    uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
+    if (grid > 8192) grid = 8192;                                              // grid-stride beyond, as k_jam_pack
+    JPK_LAUNCH(ctx, PROF_JAM, bytes, k_jam_gather, dim3((unsigned)grid), dim3(PACK_TB), d_pieces, n, words);
     JPK_HIP(hipGetLastError());
     return JPK_OK;
 }
