@@ -182,6 +182,17 @@ JPK_API uint32_t jpk_checksum_host(const uint8_t *p, int32_t size);
 JPK_API int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed);
 
 /* ---- device-buffer entry points (all pointers except ctx/out_len are HBM addresses on ctx's device) ---- */
+/* ADDRESSES AND BOUNDS of every jpk_dev_* stage entry and probe (tests/test_gpu_stage_contracts.py, tests/test_gpu_primitives.py):
+ *   - a byte buffer (const uint8_t *d_in, uint8_t *d_out, the in-place d_t / d_ranks) may start at ANY address and have any length: the
+ *     kernels peel to their vector width themselves;
+ *   - a typed array (int32_t *d_freq256 / d_sa, uint16_t *d_rle, uint32_t *d_pairs / d_vals / d_data, uint64_t *d_keys) needs the
+ *     alignment of its element type and no more;
+ *   - a call writes NOTHING outside [d_out, d_out + out_cap), whatever it returns (JPK_E_CAPACITY included), and leaves a const input as
+ *     it found it -- jpk_dev_ans_encode too, like jpk_ans_encode;
+ *   - on JPK_OK it writes nothing at or beyond d_out + *out_len: capacity the call did not need keeps the caller's bytes;
+ *   - out_cap is exact: *out_len bytes fit out_cap == *out_len, and one byte less is JPK_E_CAPACITY.
+ * The in-place entries and the probes that name no capacity write exactly their result: len bytes, int32[256] frequencies, int32[n]
+ * suffixes, *rlen uint16 symbols (jpk_dev_rle_encode; at most len), 2 * rlen uint32 words (jpk_dev_model_pairs), n keys / values / words. */
 JPK_API int jpk_dev_bwt_forward(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, uint8_t *d_out, int32_t out_cap, int32_t *out_len);
 JPK_API int jpk_dev_bwt_inverse(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len_with_trailer, uint8_t *d_out, int32_t out_cap, int32_t *out_len);
 JPK_API int jpk_dev_ans_encode(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, uint8_t *d_out, int32_t out_cap, int32_t *out_len);
@@ -308,7 +319,8 @@ JPK_API int jpk_dev_bwt_inverse_chains120(jpk_ctx *ctx, const uint8_t *d_in, int
                                   int32_t *out_len, float *chase_ms);
 /* suffix array of d_t[0..n) into d_sa (int32[n]) -- the divsufsort() replacement, divsufsort.cpp:1721 */
 JPK_API int jpk_dev_suffix_array(jpk_ctx *ctx, const uint8_t *d_t, int32_t n, int32_t *d_sa);
-/* stable LSD radix sort of (u64 key, u32 value) pairs on bits [bit_lo, bit_hi) */
+/* stable LSD radix sort of (u64 key, u32 value) pairs on bits [bit_lo, bit_hi): 0 <= bit_lo <= bit_hi <= 64, any width -- the key bits outside the
+ * range decide nothing (pairs that agree inside it keep their order) and travel with their pair; bit_lo == bit_hi leaves the arrays as they are */
 JPK_API int jpk_dev_sort_pairs_u64(jpk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int32_t n, int32_t bit_lo, int32_t bit_hi);
 /* exclusive prefix sum of uint32[n] in place; returns the total in *total */
 JPK_API int jpk_dev_exclusive_scan_u32(jpk_ctx *ctx, uint32_t *d_data, int32_t n, uint32_t *total);

@@ -631,7 +631,9 @@ extern "C" int jpk_dev_sort_pairs_u64(jpk_ctx *ctx, uint64_t *d_keys, uint32_t *
     uint32_t *sc = real.get<uint32_t>(jpk_radix_scratch_words(n));
     int shifts[8], ns = 0;
     for (int s = bit_lo; s < bit_hi; s += 8) shifts[ns++] = s;
-    JPK_TRY(jpk_radix_sort_pairs_u64(ctx, d_keys, d_vals, ka, va, (size_t)n, shifts, ns, sc));
+    // the last pass ends at bit_hi: the key bits from there up must not decide anything
+    const int last_bits = ns ? bit_hi - shifts[ns - 1] : 8;
+    JPK_TRY(jpk_radix_sort_pairs_u64(ctx, d_keys, d_vals, ka, va, (size_t)n, shifts, ns, sc, last_bits));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     return JPK_OK;
 }

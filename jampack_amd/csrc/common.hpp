@@ -148,11 +148,12 @@ int jpk_exclusive_sum_u32(jpk_ctx *ctx, const uint32_t *in, uint32_t *out, size_
 int jpk_inclusive_max_u32(jpk_ctx *ctx, const uint32_t *in, uint32_t *out, size_t n, uint32_t *scratch);
 
 size_t jpk_radix_scratch_words(size_t n);
-// LSD radix sort on bit ranges; result is left in keys/vals (alt buffers used for ping-pong)
+// LSD radix sort on bit ranges; result is left in keys/vals (alt buffers used for ping-pong).  A pass sorts on the 8 key bits from its
+// shift up, the last pass on `last_bits` of them (1..8)
 int jpk_radix_sort_pairs_u64(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t *keys_alt, uint32_t *vals_alt, size_t n,
-                             const int *shifts, int nshifts, uint32_t *scratch);
+                             const int *shifts, int nshifts, uint32_t *scratch, int last_bits = 8);
 int jpk_radix_sort_pairs_u64_nocopy(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t *keys_alt, uint32_t *vals_alt, size_t n,
-                                    const int *shifts, int nshifts, uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out);
+                                    const int *shifts, int nshifts, uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out, int last_bits = 8);
 bool jpk_radix_onesweep();   // round 0's radix passes in the one-pass form (default; JPK_ONESWEEP=0: histogram + scan + scatter per pass)
 int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n, uint64_t *keysA, uint32_t *valsA, uint64_t *keysB, uint32_t *valsB,
                              uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out, bool group, const uint8_t *slot_tag = nullptr, int tag_shift = 26,

@@ -48,7 +48,8 @@ __device__ __forceinline__ void rs_load_tile(const uint64_t *__restrict__ kin, c
         if (base + (size_t)it * 64 >= n) { key[it] = 0; val[it] = 0; }
 }
 
-__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *__restrict__ keys, size_t n, int shift,
+// dmask: the digit's bits (255: a whole byte; the last pass of a bit range that is no multiple of 8 wide keeps fewer)
+__global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *__restrict__ keys, size_t n, int shift, uint32_t dmask,
                                                        uint32_t *__restrict__ tilehist, uint32_t ntiles)
 {
     __shared__ uint32_t h[RS_WAVES][256];
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *__restri
     // conflicts and cost about as much as the whole scatter pass.  (Round 4 tried both per row -- atomics where the row's digits are
     // spread out, as the packed keys' are, the match where they are not: 12 % fewer vector instructions per block and the same
     // bench line, profiles/r04_hist_rows.txt -- the kernel waits for its loads either way.)
-    if ((shift & 7) == 0 && (size_t)(blockIdx.x + 1) * RS_TILE <= n) {
+    if ((shift & 7) == 0 && dmask == 255u && (size_t)(blockIdx.x + 1) * RS_TILE <= n) {
         // a whole tile of keys and a digit that is a byte of the key (every pass of the suffix sort): the digit is loaded as that
         // byte from a wave-uniform base with the item offset in the instruction -- no clamp, no 64-bit shift, no validity masks
         const uint8_t *bp = reinterpret_cast<const uint8_t *>(keys + (size_t)blockIdx.x * RS_TILE + (size_t)w * (64 * RS_ITEMS)) + (shift >> 3);
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_hist(const uint64_t *__restri
 #pragma unroll
         for (int it = 0; it < RS_ITEMS; it++) {
             const size_t i = base + (size_t)it * 64, ic = i < n ? i : n - 1;
-            dig[it] = (uint32_t)(keys[ic] >> shift) & 255u;
+            dig[it] = (uint32_t)(keys[ic] >> shift) & dmask;
         }
 #pragma unroll
         for (int it = 0; it < RS_ITEMS; it++) {
@@ -128,7 +129,7 @@ template <bool SLOTS, bool FULL, bool LOOKBACK = false>
 __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
                                                        uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift,
                                                        const uint32_t *__restrict__ tileoff, uint32_t ntiles, uint32_t tile, uint32_t (*cnt)[256],
-                                                       uint32_t *gbase, uint64_t *stage, uint32_t *sm, const OsArgs *os = nullptr)
+                                                       uint32_t *gbase, uint64_t *stage, uint32_t *sm, const OsArgs *os = nullptr, uint32_t dmask = 255u)
 {
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), l = threadIdx.x & 63;
     const size_t tbase = (size_t)tile * RS_TILE;
@@ -169,7 +170,7 @@ __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restric
     if (LOOKBACK) {
 #pragma unroll
         for (int it = 0; it < RS_ITEMS; it++)
-            if (FULL || base + (size_t)it * 64 < n) atomicAdd(&gbase[(uint32_t)(key[it] >> shift) & 255u], 1u);
+            if (FULL || base + (size_t)it * 64 < n) atomicAdd(&gbase[(uint32_t)(key[it] >> shift) & dmask], 1u);
         __syncthreads();
         const uint32_t s0 = gbase[threadIdx.x];
         __hip_atomic_store(os->status + (size_t)tile * 256u + threadIdx.x, (tile == 0 ? OS_FLAG_PFX : OS_FLAG_AGG) | s0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -177,7 +178,7 @@ __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restric
 #pragma unroll
     for (int it = 0; it < RS_ITEMS; it++) {
         const bool valid = FULL || base + (size_t)it * 64 < n;
-        const uint32_t d = (uint32_t)(key[it] >> shift) & 255u;
+        const uint32_t d = (uint32_t)(key[it] >> shift) & dmask;
         const uint64_t m = match_any8(d, valid);
         const uint32_t below = (uint32_t)__popcll(m & lt);
         const uint32_t c = valid ? cnt[w][d] : 0;
@@ -238,7 +239,7 @@ __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restric
     uint32_t pos[RS_ITEMS];
 #pragma unroll
     for (int it = 0; it < RS_ITEMS; it++) {
-        const uint32_t d = (uint32_t)(key[it] >> shift) & 255u;
+        const uint32_t d = (uint32_t)(key[it] >> shift) & dmask;
         pos[it] = cnt[w][d] + rnk[it];
         if (FULL || base + (size_t)it * 64 < n) stage[pos[it]] = key[it];
     }
@@ -250,7 +251,7 @@ __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restric
         dstv[it] = 0xFFFFFFFFu;
         if (FULL || p < tcount) {
             const uint64_t k = stage[p];
-            const uint32_t d = (uint32_t)(k >> shift) & 255u;
+            const uint32_t d = (uint32_t)(k >> shift) & dmask;
             dstv[it] = gbase[d] + p;
             kout[dstv[it]] = k;
         }
@@ -271,7 +272,7 @@ __device__ __forceinline__ void rs_scatter_staged_tile(const uint64_t *__restric
 // two launches per pass: the full tiles (no bounds logic) and, if n is not a multiple of the tile, the last tile alone
 template <bool SLOTS, bool FULL>
 __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_staged(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin,
-                                                                 uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift,
+                                                                 uint64_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift, uint32_t dmask,
                                                                  const uint32_t *__restrict__ tileoff, uint32_t ntiles, uint32_t tile0)
 {
     __shared__ uint32_t cnt[RS_WAVES][256];
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter_staged(const uint64_t
     __shared__ uint32_t sm[RS_THREADS / 64 + 1];
     for (int i = threadIdx.x; i < RS_WAVES * 256; i += RS_THREADS) (&cnt[0][0])[i] = 0;
     __syncthreads();
-    rs_scatter_staged_tile<SLOTS, FULL>(kin, vin, kout, vout, n, shift, tileoff, ntiles, tile0 + blockIdx.x, cnt, gbase, stage, sm);
+    rs_scatter_staged_tile<SLOTS, FULL>(kin, vin, kout, vout, n, shift, tileoff, ntiles, tile0 + blockIdx.x, cnt, gbase, stage, sm, nullptr, dmask);
 }
 
 // (two launches per pass, like the two-pass form: the full tiles -- no bounds logic, a third of the registers -- and then the last,
@@ -360,13 +361,13 @@ __global__ __launch_bounds__(256) void k_os_prefix(const uint32_t *__restrict__ 
 
 template <bool SLOTS>
 void launch_rs_scatter_staged(jpk_ctx *ctx, const uint64_t *kin, const uint32_t *vin, uint64_t *kout, uint32_t *vout, size_t n, int shift,
-                              const uint32_t *tileoff, uint32_t ntiles)
+                              const uint32_t *tileoff, uint32_t ntiles, uint32_t dmask = 255u)
 {
     const uint32_t nfull = (uint32_t)(n / RS_TILE);
     if (nfull) JPK_LAUNCH(ctx, PROF_RS_SCATTER, (size_t)nfull * RS_TILE, (k_rs_scatter_staged<SLOTS, true>), dim3(nfull), dim3(RS_THREADS), kin, vin, kout, vout, n, shift,
-                          tileoff, ntiles, 0u);
+                          dmask, tileoff, ntiles, 0u);
     if (nfull < ntiles) JPK_LAUNCH(ctx, PROF_RS_SCATTER, n - (size_t)nfull * RS_TILE, (k_rs_scatter_staged<SLOTS, false>), dim3(1), dim3(RS_THREADS), kin, vin, kout, vout, n,
-                                   shift, tileoff, ntiles, nfull);
+                                   shift, dmask, tileoff, ntiles, nfull);
 }
 
 }  // namespace
@@ -394,10 +395,12 @@ static bool rs_onesweep()
 bool jpk_radix_onesweep() { return rs_onesweep(); }
 
 // the sorted pairs end up in (*keys_out, *vals_out): the caller's buffers after an even number of passes, the alt buffers after an
-// odd number -- no copy back
+// odd number -- no copy back.  Every pass sorts on the 8 key bits from its shift up, the last one on `last_bits` (1..8) of them: a bit
+// range that is no multiple of 8 wide ends where it says, the key bits above it do not take part.
 int jpk_radix_sort_pairs_u64_nocopy(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t *keys_alt, uint32_t *vals_alt, size_t n,
-                                    const int *shifts, int nshifts, uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out)
+                                    const int *shifts, int nshifts, uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out, int last_bits)
 {
+    if (last_bits < 1 || last_bits > 8) return JPK_E_ARG;
     *keys_out = keys;
     *vals_out = vals;
     if (n == 0 || nshifts == 0) return JPK_OK;
@@ -408,9 +411,10 @@ int jpk_radix_sort_pairs_u64_nocopy(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals
     uint64_t *ki = keys, *ko = keys_alt;
     uint32_t *vi = vals, *vo = vals_alt;
     for (int p = 0; p < nshifts; p++) {
-        JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), ki, n, shifts[p], hist, ntiles);
+        const uint32_t dmask = p + 1 == nshifts ? (1u << last_bits) - 1u : 255u;
+        JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), ki, n, shifts[p], dmask, hist, ntiles);
         JPK_TRY(jpk_exclusive_sum_u32(ctx, hist, hist, table, scan_scratch, nullptr));
-        launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shifts[p], hist, ntiles);
+        launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shifts[p], hist, ntiles, dmask);
         uint64_t *tk = ki; ki = ko; ko = tk;
         uint32_t *tv = vi; vi = vo; vo = tv;
     }
@@ -421,11 +425,11 @@ int jpk_radix_sort_pairs_u64_nocopy(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals
 }
 
 int jpk_radix_sort_pairs_u64(jpk_ctx *ctx, uint64_t *keys, uint32_t *vals, uint64_t *keys_alt, uint32_t *vals_alt, size_t n,
-                             const int *shifts, int nshifts, uint32_t *scratch)
+                             const int *shifts, int nshifts, uint32_t *scratch, int last_bits)
 {
     uint64_t *ki;
     uint32_t *vi;
-    JPK_TRY(jpk_radix_sort_pairs_u64_nocopy(ctx, keys, vals, keys_alt, vals_alt, n, shifts, nshifts, scratch, &ki, &vi));
+    JPK_TRY(jpk_radix_sort_pairs_u64_nocopy(ctx, keys, vals, keys_alt, vals_alt, n, shifts, nshifts, scratch, &ki, &vi, last_bits));
     if (ki != keys) {
         JPK_HIP(hipMemcpyAsync(keys, ki, n * 8, hipMemcpyDeviceToDevice, ctx->stream));
         JPK_HIP(hipMemcpyAsync(vals, vi, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -498,7 +502,7 @@ int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n32, uint64_t *keysA, uint32
             launch_rs_scatter_staged<true>(ctx, keysA, nullptr, keysB, valsB, n, shift, hist, ntiles);
             continue;
         }
-        JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), (const uint64_t *)ki, n, shift, hist, ntiles);
+        JPK_LAUNCH(ctx, PROF_RS_HIST, n, k_rs_hist, dim3(ntiles), dim3(RS_THREADS), (const uint64_t *)ki, n, shift, 255u, hist, ntiles);
         JPK_TRY(jpk_exclusive_sum_u32(ctx, hist, hist, table, scan_scratch, nullptr));
         launch_rs_scatter_staged<false>(ctx, ki, vi, ko, vo, n, shift, hist, ntiles);
         uint64_t *tk = ki; ki = ko; ko = tk;

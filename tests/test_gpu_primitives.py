@@ -51,6 +51,59 @@ def test_radix_sort_pairs_is_stable_and_sorted(ctx, n, bits):
     assert np.array_equal(gk, keys[order])
 
 
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 1_000_003])
+def test_exclusive_scan_wraps_mod_2_32(ctx, n):
+    """values from the whole 32-bit range: the running sum wraps many times; expected from a 64-bit cumsum reduced mod 2^32"""
+    rng = np.random.default_rng(500 + n)
+    a = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    d = _dev(a.view(np.int32))
+    tot = ctx.exclusive_scan_u32(d, n)
+    got = d.cpu().numpy().view(np.uint32)
+    inc = np.cumsum(a, dtype=np.uint64)
+    exp = (np.concatenate((np.zeros(1, np.uint64), inc[:-1])) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    assert tot == int(inc[-1] & np.uint64(0xFFFFFFFF))
+    bad = np.nonzero(got != exp)[0]
+    assert bad.size == 0, f"first mismatch at {bad[:5]}: got {got[bad[:5]]} exp {exp[bad[:5]]}"
+
+
+def test_exclusive_scan_of_words_off_the_16_byte_boundary(ctx):
+    """d_data 4 bytes behind an aligned address (uint32 needs no more than its own alignment; the kernels load uint4 from in + base),
+    guards directly around the n words"""
+    import torch
+    from stage_guard import Guarded
+    n = 3 * 4096 + 17                                          # whole tiles through the vector path and a ragged one
+    rng = np.random.default_rng(77)
+    a = rng.integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    g = Guarded(torch, a.astype("<u4"), 4)
+    assert g.ptr % 16 == 4
+    tot = ctx.exclusive_scan_u32(g.ptr, n)
+    inc = np.cumsum(a, dtype=np.uint64)
+    exp = (np.concatenate((np.zeros(1, np.uint64), inc[:-1])) & np.uint64(0xFFFFFFFF)).astype("<u4")
+    assert tot == int(inc[-1] & np.uint64(0xFFFFFFFF))
+    g.check_output(exp, what="exclusive_scan_u32 at +4")
+
+
+# RS_TILE in radix.hip is 4096 pairs: one short of, exactly and one past a tile; one pair; many tiles with a ragged last one
+@pytest.mark.parametrize("n", [1, 4095, 4096, 4097, 100_003])
+@pytest.mark.parametrize("bit_lo,bit_hi", [(0, 8), (3, 13), (8, 16), (5, 5), (1, 64), (56, 64), (17, 40), (60, 64)])
+def test_radix_sort_pairs_on_a_bit_range(ctx, n, bit_lo, bit_hi):
+    """keys drawn from all 64 bits: only the bits [bit_lo, bit_hi) may decide the order (a last pass that looks at a whole byte would sort
+    on the bits above bit_hi too), the pairs move with all 64 key bits intact, (5, 5) is the empty range: the identity"""
+    from stage_guard import bit_range_order
+    rng = np.random.default_rng(1000 * bit_lo + bit_hi + n)
+    keys = rng.integers(0, 2 ** 64, n, dtype=np.uint64)
+    keys[: n // 3] = keys[n // 2: n // 2 + n // 3]          # whole-key duplicates on top of the ties inside the range: stability matters
+    vals = np.arange(n, dtype=np.uint32)
+    dk, dv = _dev(keys.view(np.int64)), _dev(vals.view(np.int32))
+    ctx.sort_pairs_u64(dk, dv, n, bit_lo, bit_hi)
+    gk = dk.cpu().numpy().view(np.uint64)
+    gv = dv.cpu().numpy().view(np.uint32)
+    order = bit_range_order(keys, bit_lo, bit_hi)
+    bad = np.nonzero(gv != order.astype(np.uint32))[0]
+    assert bad.size == 0, f"first mismatch at {bad[:5]}: got {gv[bad[:5]]} exp {order[bad[:5]]}"
+    assert np.array_equal(gk, keys[order])
+
+
 @pytest.mark.parametrize("kind", ["text", "two", "zero", "random", "repeat4k", "dna", "runs"])
 @pytest.mark.parametrize("n", [1, 2, 7, 8, 100, 5000, 200_000])
 def test_suffix_array_equals_oracle(ctx, oracle, kind, n):
