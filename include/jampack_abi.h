@@ -275,6 +275,45 @@ JPK_API int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, 
  * or -1 (JPK_OK).  No device call.  Pointers other than in may be NULL. */
 JPK_API int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame);
 
+/* ---- archives of the stock CLI: the pre-stage decoders on the device, whole archives in one batched call ---------------------------- */
+/* The three decoders the stock `jampack c` needs behind Ans::Decode + InverseBwt (Jampack::Decomp(), jampack.cpp:47-60), for n independent
+ * blocks that sit in HBM, one launch per call.  Arrays of n device pointers / sizes (the arrays themselves are host memory) as for
+ * jpk_dev_blocks_ans_decode; status may be NULL (the call then returns the first failing block's status), otherwise status[b] receives
+ * block b's jpk_status and a bad block does not stop the others.  Output and status are those of the host decoders (jpk_lz77_decompress,
+ * jpk_lpx_decode, jpk_filters_decode) on the same bytes; the buffer of a failed block is unspecified inside [d_out, d_out + out_cap).
+ * ADDRESSES AND BOUNDS above holds; input and output of a block must not overlap.
+ *   Lz77::Decompress(Buffer,Buffer)            lz77.hpp:22, lz77.cpp:678-714    one workgroup per block */
+JPK_API int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                           const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/*   Lpx::Decode(Buffer,Buffer,Options)         lpx.hpp:32, lpx.cpp:101-169      one workgroup per part (len / 4 bytes), one lane runs its model;
+ *   writes exactly len[b] bytes; every byte string is a valid stream */
+JPK_API int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status);
+/*   Filters::Decode(Buffer,Buffer)             filters.hpp:44, filters.cpp:442-490   one workgroup per 64 KiB filter block */
+JPK_API int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                          const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/* Jampack::Decompress (jampack.cpp:262-336) of an archive written by an unmodified `jampack c` (any -m / -f setting; the frames of
+ * jpk_jam_cli_block_read, back to back): the frame walk of jpk_dev_jam_decompress, with an entropy-decoded size of at most
+ * 1.05 x BlockSize + 4096 per frame (the reference's stage buffers, jampack.cpp:156), then per pass jpk_dev_blocks_decompress into
+ * per-frame slots of a scratch buffer of ctx, the four batched pre-stage launches in the order of Jampack::Decomp() (Lz77, Lpx, Filters,
+ * Lz77), one batched checksum compared with the header crcs, and one gather launch that packs the verified frames back to back into d_out.
+ *   bad frame k (header, payload, a pre-stage stream, a raw size above BlockSize, crc): its status (JPK_E_CORRUPT), *bad_frame = k,
+ *   *frames = k, *out_len = the raw bytes of frames 0..k-1, which are verified and in place.
+ *   capacity: a frame's raw size is known only when it has been decoded.  The sum of the frames' BlockSize (*raw_bound of
+ *   jpk_jam_cli_frames) always suffices.  When the frames of a pass do not fit the rest of out_cap: JPK_E_CAPACITY, *out_len = that sum,
+ *   *frames = the frames of the earlier passes, which may be in place; nothing at or beyond d_out + out_cap is written.
+ *   success: *frames = the frame count, *bad_frame = -1.  frames and bad_frame may be NULL.  1..14 trailing bytes are a bad frame.
+ * Per-pass HBM: passes of at most 128 frames and 4 GiB of BlockSize; two slots of 1.05 x BlockSize + 4096 per frame (<= 9 GB) in the
+ * scratch buffer, plus the batch decoder's arena (about 4 bytes per entropy-decoded byte of the pass). */
+JPK_API int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                       int32_t *bad_frame);
+/* host-buffer form through the calling thread's pooled context, staged one pass at a time; same contract (the arguments are checked
+ * before a device is looked for) */
+JPK_API int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame);
+/* host walk of a stock-CLI archive in host memory with the checks of jpk_dev_jam_cli_decompress's walk: *frames = the frames in front of
+ * the first bad one, *raw_bound = the sum of their BlockSize (an out_cap that always suffices), *bad_frame = its index (JPK_E_CORRUPT)
+ * or -1 (JPK_OK).  No device call.  Pointers other than in may be NULL. */
+JPK_API int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame);
+
 /* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
 /* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the
  * 64-bit raw offset (the prefix sum of the raw sizes).  jpk_dev_jam_index_create walks an archive in HBM, jpk_jam_index_create one

@@ -104,6 +104,12 @@ _SIGS = {
     "jpk_jam_index_destroy": (None, [_vp]),
     "jpk_dev_jam_read": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_vp), _i32p, _i32p]),
     "jpk_jam_read": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_vp), _i32p, _i32p]),
+    "jpk_dev_blocks_lz77_decompress": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
+    "jpk_dev_blocks_lpx_decode": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p]),
+    "jpk_dev_blocks_filters_decode": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
+    "jpk_dev_jam_cli_decompress": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_jam_cli_decompress": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_jam_cli_frames": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(C.c_int64), _i32p]),
     "jpk_dev_suffix_array": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "jpk_dev_sort_pairs_u64": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32]),
     "jpk_dev_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_uint32)]),

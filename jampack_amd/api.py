@@ -338,6 +338,32 @@ def jam_cli_decompress(stream) -> np.ndarray:
     return np.concatenate(out) if out else np.zeros(0, dtype=np.uint8)
 
 
+def jam_cli_frames(stream):
+    """jpk_jam_cli_frames: host walk of a stock-CLI archive -> (frames, raw bound, bad frame or -1) of the frames in front of the first
+    bad one; the raw bound (the sum of their BlockSize) is an output capacity that always suffices"""
+    c = _np_u8(stream)
+    k, bound, bad = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+    rc = lib().jpk_jam_cli_frames(_ptr(c), len(c), C.byref(k), C.byref(bound), C.byref(bad))
+    if rc not in (0, -3):
+        raise JampackError(rc, "jpk_jam_cli_frames")
+    return k.value, bound.value, bad.value
+
+
+def jam_cli_decompress_all(stream, check: bool = True):
+    """`jampack d` over an in-memory .jam stream of the stock CLI by ONE jpk_jam_cli_decompress call: every frame of a pass through the
+    batched entropy decode, inverse BWT and pre-stage decoders on the GPU.  Returns the raw bytes; check=False: (raw bytes in front of
+    the first bad frame, frames, bad frame, status), no exception."""
+    c = _np_u8(stream)
+    _, bound, _ = jam_cli_frames(c)
+    out = np.empty(max(bound, 1), dtype=np.uint8)
+    n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+    rc = lib().jpk_jam_cli_decompress(_ptr(c), len(c), out.ctypes.data, bound, C.byref(n), C.byref(nf), C.byref(bf))
+    if not check:
+        return out[: n.value if rc in (0, -3) else 0], nf.value, bf.value, int(rc)
+    _chk(rc, f"jam_cli_decompress_all: frame {bf.value}")
+    return out[: n.value]
+
+
 def _dptr(x):
     """device pointer of a torch CUDA tensor or a raw int"""
     if x is None:
@@ -441,6 +467,33 @@ class Context:
         il, oc, ol, st = I(*in_lens), I(*out_caps), I(), I()
         _chk(lib().jpk_dev_blocks_compress(self._h, n, ins, il, outs, oc, ol, st, int(in_flight)), "jpk_dev_blocks_compress")
         return list(ol), list(st)
+
+    def blocks_lz77_decompress(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_lz77_decompress: Lz77::Decompress of independent blocks in one launch -> (out_len list, status list)"""
+        return self._batch(lib().jpk_dev_blocks_lz77_decompress, "jpk_dev_blocks_lz77_decompress", d_ins, in_lens, d_outs, out_caps)
+
+    def blocks_lpx_decode(self, d_ins, lens, d_outs):
+        """jpk_dev_blocks_lpx_decode: Lpx::Decode of independent blocks in one launch (output length = input length) -> status list"""
+        n = len(d_ins)
+        P, I = C.c_void_p * max(n, 1), C.c_int32 * max(n, 1)
+        st = I()
+        _chk(lib().jpk_dev_blocks_lpx_decode(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*lens), P(*[_dptr(x) for x in d_outs]), st), "jpk_dev_blocks_lpx_decode")
+        return list(st)[:n]
+
+    def blocks_filters_decode(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_filters_decode: Filters::Decode of independent blocks in one launch -> (out_len list, status list)"""
+        return self._batch(lib().jpk_dev_blocks_filters_decode, "jpk_dev_blocks_filters_decode", d_ins, in_lens, d_outs, out_caps)
+
+    def jam_cli_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):
+        """jpk_dev_jam_cli_decompress: a whole stock-CLI archive in HBM -> (raw bytes, frames, bad frame); check=False: (raw bytes,
+        frames, bad frame, status), no exception (out_len is the raw bound on JPK_E_CAPACITY, the verified bytes in front of the bad
+        frame on JPK_E_CORRUPT)"""
+        n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+        rc = lib().jpk_dev_jam_cli_decompress(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf))
+        if not check:
+            return n.value, nf.value, bf.value, int(rc)
+        _chk(rc, "jpk_dev_jam_cli_decompress")
+        return n.value, nf.value, bf.value
 
     def checksum(self, d_in, in_len) -> int:
         crc = C.c_uint32(0)

@@ -109,7 +109,8 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_rs_hist/k_os_digits", "k_rs_scatter/k_os_scatter", "k_scan_*/k_tab_*/k_win_*", "k_gather_win", "k_seg_round", "k_r0_*/k_lg_finish/k_cmp_*", "k_bwt_image",
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
-    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack"};
+    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
+    "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {
@@ -1865,9 +1866,14 @@ struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t bloc
 // the checks of the frame walk beyond its header (k_jam_walk / jam_walk_host): the payload declares at least the BWT trailer and at
 // most BlockSize raw bytes (the reference decodes into buffers of 1.05 x BlockSize, jampack.cpp:156-159)
 bool jam_decoded_ok(int64_t decoded, int32_t block_size) { return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= block_size; }
+// ... and for a frame of the stock CLI, whose entropy-decoded bytes are the output of its pre-stages (filter headers and LZ tokens add
+// bytes): at most the reference's stage buffers, 1.05 x BlockSize + 4096 (jampack.cpp:156), as jpk_jam_cli_block_read has them
+int32_t jam_cli_cap(int32_t block_size) { return (int32_t)((int64_t)((double)block_size * 1.05) + 4096); }
+bool jam_cli_decoded_ok(int64_t decoded, int32_t block_size) { return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= jam_cli_cap(block_size); }
 
-// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none)
-void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad)
+// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); cli: frames of the
+// stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders)
+void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
 {
     *bad = -1;
     int64_t o = 0;
@@ -1883,7 +1889,8 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
             (int64_t)f.psize > in_len - o - JPK_JAM_HEADER_BYTES) { *bad = k; return; }
         f.payload_off = o + JPK_JAM_HEADER_BYTES;
         int64_t decoded = 0;
-        if (jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size)) { *bad = k; return; }
+        if (jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK ||
+            !(cli ? jam_cli_decoded_ok(decoded, f.block_size) : jam_decoded_ok(decoded, f.block_size))) { *bad = k; return; }
         f.raw = decoded - JPK_TRAILER_BYTES;
         fr.push_back(f);
         o = f.payload_off + f.psize;
@@ -1891,7 +1898,7 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
 }
 
 // the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
-int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad)
+int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
 {
     *bad = -1;
     JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
@@ -1911,7 +1918,7 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
         for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
         JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
         for (int i = 0; i < n; i++) {
-            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], h[i].block_size)) { *bad = (int32_t)fr.size(); return JPK_OK; }
+            if (st[i] != JPK_OK || !(cli ? jam_cli_decoded_ok(dec[i], h[i].block_size) : jam_decoded_ok(dec[i], h[i].block_size))) { *bad = (int32_t)fr.size(); return JPK_OK; }
             fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, h[i].block_size, dec[i] - JPK_TRAILER_BYTES});
         }
         if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
@@ -2135,6 +2142,202 @@ extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *ou
         int64_t n = 0;
         int32_t nf = 0, bf = -1;
         const int rc = jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, raw, &n, &nf, &bf);
+        if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        if (rc != JPK_OK) {
+            if (rc == JPK_E_CORRUPT) *out_len = pos + n;
+            if (frames) *frames = (int32_t)k + nf;
+            if (bad_frame && bf >= 0) *bad_frame = (int32_t)k + bf;
+            return rc;
+        }
+        pos += n;
+        k = e;
+    }
+    *out_len = pos;
+    if (frames) *frames = (int32_t)fr.size();
+    if (bad >= 0) {
+        if (bad_frame) *bad_frame = bad;
+        return JPK_E_CORRUPT;
+    }
+    return JPK_OK;
+}
+
+// ---- whole archives of the stock CLI: every frame through the four pre-stage decoders on the device (prestage_dev.hip) -------------
+// Per pass: jpk_dev_blocks_decompress into slot A of every frame, then Lz77 A -> B, Lpx B -> A, Filters A -> B, Lz77 B -> A (the
+// order of Jampack::Decomp(), jampack.cpp:51-57), one batched checksum of the A slots against the header crcs, one k_jam_gather
+// launch that packs the verified frames back to back into d_out.  A frame's raw size is known only behind its last stage; every stage
+// works on the frames in front of the first one that has failed so far, which is where the call stops.
+namespace {
+// frames [k, e) of fr form the pass that starts at frame k: at most JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW bytes of BlockSize
+size_t jam_cli_pass_end(const std::vector<JamFrame> &fr, size_t k)
+{
+    size_t e = k;
+    uint64_t sum = 0;
+    while (e < fr.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || sum + (uint64_t)fr[e].block_size <= JAM_PASS_RAW)) sum += (uint64_t)fr[e++].block_size;
+    return e;
+}
+
+// the first block of st[0..m) that failed (*rc = its status), m when none did.  A stage that runs out of its slot (1.05 x BlockSize +
+// 4096, or BlockSize behind the last stage) met a bad frame: JPK_E_CAPACITY is kept for the caller's out_cap.
+int jam_cli_cut(const std::vector<int32_t> &st, int m, int *rc)
+{
+    for (int i = 0; i < m; i++) if (st[(size_t)i] != JPK_OK) { *rc = st[(size_t)i] == JPK_E_CAPACITY ? JPK_E_CORRUPT : st[(size_t)i]; return i; }
+    return m;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                          int32_t *frames, int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    *out_len = 0;
+    if (frames) *frames = 0;
+    if (bad_frame) *bad_frame = -1;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, true));
+    int64_t raw_bound = 0;
+    for (const JamFrame &f : fr) raw_bound += f.block_size;
+    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_cli_pass_end(fr, k);
+        const int n = (int)(e - k);
+        std::vector<const uint8_t *> ins((size_t)n), a_in((size_t)n), b_in((size_t)n);
+        std::vector<uint8_t *> a((size_t)n), b((size_t)n);
+        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), l0((size_t)n), l1((size_t)n), l3((size_t)n), raw((size_t)n), st((size_t)n);
+        std::vector<size_t> slot((size_t)n);
+        size_t need = o_slots;
+        for (int i = 0; i < n; i++) {
+            const JamFrame &f = fr[k + i];
+            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size;
+            caps[i] = jam_cli_cap(f.block_size);
+            slot[i] = jpk_align((size_t)caps[i] + 64);           // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            need += 2 * slot[i];
+        }
+        JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
+        size_t off = o_slots;
+        for (int i = 0; i < n; i++) {
+            a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i];
+            a_in[i] = a[i]; b_in[i] = b[i];
+        }
+        int rc = JPK_OK;
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), a.data(), caps.data(), l0.data(), st.data()));   // Ans::Decode + InverseBwt
+        int m = jam_cli_cut(st, n, &rc);
+        if (m) {
+            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, a_in.data(), l0.data(), b.data(), caps.data(), l1.data(), st.data()));   // Lz->Decompress
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, b_in.data(), l1.data(), a.data(), st.data()));                             // LocalModel->Decode
+        if (m) {
+            JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, a_in.data(), l1.data(), b.data(), caps.data(), l3.data(), st.data()));    // Filter->Decode
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) {
+            // Lz->Decompress; a frame that decodes to more than its BlockSize is a bad frame
+            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, b_in.data(), l3.data(), a.data(), bsz.data(), raw.data(), st.data()));
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) {
+            std::vector<uint32_t> crc((size_t)m);
+            JPK_TRY(jpk_checksums_device(ctx, m, a_in.data(), raw.data(), d_crc));
+            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            for (int i = 0; i < m; i++) if (crc[i] != fr[k + i].crc) { m = i; rc = JPK_E_CORRUPT; break; }      // "Detected corrupt block!", jampack.cpp:59
+        }
+        int64_t sum = 0;
+        for (int i = 0; i < m; i++) sum += raw[i];
+        if (sum > out_cap - pos) {
+            *out_len = raw_bound;
+            if (frames) *frames = (int32_t)k;
+            return JPK_E_CAPACITY;
+        }
+        std::vector<JamGatherPiece> pieces;
+        uint64_t words = 0;
+        int64_t o = pos;
+        for (int i = 0; i < m; i++) {
+            if (raw[i] == 0) continue;
+            uint8_t *dst = d_out + o;
+            pieces.push_back(JamGatherPiece{a[i], dst, (uint64_t)raw[i], words, a[i], a[i] + slot[i]});
+            words += (((uintptr_t)dst & 15u) + (uint64_t)raw[i] + 15u) / 16u;
+            o += raw[i];
+        }
+        if (!pieces.empty()) {
+            JPK_HIP(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(JamGatherPiece), hipMemcpyHostToDevice, ctx->stream));
+            JPK_TRY(jpk_jam_gather_enqueue(ctx, d_pieces, (uint32_t)pieces.size(), words, (uint64_t)sum));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            if (ctx->prof_on) jpk_prof_resolve(ctx);
+        }
+        pos += sum;
+        if (m < n) {
+            *out_len = pos;
+            if (frames) *frames = (int32_t)k + m;
+            if (bad_frame) *bad_frame = (int32_t)k + m;
+            return rc;
+        }
+        k = e;
+    }
+    *out_len = pos;
+    if (frames) *frames = (int32_t)fr.size();
+    if (bad >= 0) {
+        if (bad_frame) *bad_frame = bad;
+        return JPK_E_CORRUPT;
+    }
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame)
+{
+    if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad, true);
+    int64_t bound = 0;
+    for (const JamFrame &f : fr) bound += f.block_size;
+    if (frames) *frames = (int32_t)fr.size();
+    if (raw_bound) *raw_bound = bound;
+    if (bad_frame) *bad_frame = bad;
+    return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
+}
+
+extern "C" int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    *out_len = 0;
+    if (frames) *frames = 0;
+    if (bad_frame) *bad_frame = -1;
+    jpk_ctx *ctx;
+    JPK_TRY(tls_ctx(&ctx));
+    JPK_HIP(hipSetDevice(ctx->device));
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad, true);
+    int64_t raw_bound = 0;
+    for (const JamFrame &f : fr) raw_bound += f.block_size;
+    // staged one pass at a time: the pass's frames are an archive of their own for the device call, which decodes them into what is
+    // left of out_cap (at most the pass's BlockSize bytes)
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_cli_pass_end(fr, k);
+        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+        int64_t room = 0;
+        for (size_t i = k; i < e; i++) room += fr[i].block_size;
+        room = std::min(room, out_cap - pos);
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+        int64_t n = 0;
+        int32_t nf = 0, bf = -1;
+        const int rc = jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
+        if (rc == JPK_E_CAPACITY) {
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            *out_len = raw_bound;
+            if (frames) *frames = (int32_t)k;
+            return rc;
+        }
         if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         JPK_HIP(hipStreamSynchronize(ctx->stream));
         if (rc != JPK_OK) {

@@ -1,0 +1,439 @@
+// prestage_dev.hip -- the decoders of the three stages the stock CLI runs in front of the BWT (Jampack::Decomp, jampack.cpp:47-60), on gfx950,
+// for batches of blocks that already sit in HBM behind the batched rANS decode + inverse BWT:
+//   k_pre_lz77     Lz77::Decompress (lz77.cpp:678-714)   one workgroup per block: every lane parses the token, all lanes copy
+//   k_pre_lpx      Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
+//   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
+// Each is bit-identical to its host form in prestage.cpp (statuses included) and keeps that file's bounds checks: every read is checked
+// against in_len and every write against out_cap before it is made, in 64-bit arithmetic.  No workgroup waits for another one, every
+// loop is bounded by the stream length or the output capacity, and a bad stream sets the block's mail word and ends the workgroup.
+#include <vector>
+
+#include "common.hpp"
+
+namespace {
+
+// one block of a batch: wg0 = the workgroups of the blocks in front of it (k_pre_lpx, k_pre_filters: several workgroups per block)
+struct PreJob { const uint8_t *in; uint8_t *out; int32_t in_len; int32_t out_cap; uint32_t wg0; uint32_t pad; };
+
+constexpr int PRE_TB = 256;
+
+// the block of workgroup w: the last job with wg0 <= w (jobs without workgroups share the wg0 of their successor and are skipped by it)
+__device__ __forceinline__ uint32_t job_of(const PreJob *__restrict__ jobs, uint32_t n, uint32_t w)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (jobs[mid].wg0 <= w) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// ---- LZ77 ----------------------------------------------------------------------------------------------------------------------
+// A token is at most 16 bytes (token, three LEB128 values of up to five bytes): every wave loads the 16 bytes at `pos` once, lane l the
+// byte (l & 15), and reads them back by index, so the parse is the same in every lane and costs one load per token.
+__device__ __forceinline__ uint32_t win_byte(uint32_t w, int j) { return (uint32_t)__shfl((int)w, j, 64); }
+
+// leb_read of prestage.cpp on the window: the value at window offset `at`, avail = bytes of the stream from there
+__device__ __forceinline__ int leb_win(uint32_t w, int at, int64_t avail, int32_t *v)
+{
+    int d = 0;
+    uint32_t x = 0, b;
+    for (;;) {
+        if (d >= avail) return -1;
+        b = win_byte(w, at + d);
+        if (b & 0x80u) break;
+        if (d >= 4) return -1;
+        x = (x << 7) | b;
+        d++;
+    }
+    x = (x << 7) | (b & 0x7fu);
+    if (d > 0) x += d == 1 ? 127u : (d == 2 ? 16510u : (d == 3 ? 2113661u : 270549116u));
+    *v = (int32_t)x;
+    return d + 1;
+}
+
+// mail[2 b] = status, mail[2 b + 1] = out_len.  The match copy out[op + k] = out[op - off + k mod off] reads only bytes below op, which
+// the tokens in front of this one (and this token's literals) wrote: one fence + barrier per token, between the literal copy and the
+// match copy, orders all of them -- the literals of the next token touch no byte a match of this one reads or writes.
+__global__ __launch_bounds__(PRE_TB) void k_pre_lz77(const PreJob *__restrict__ jobs, uint32_t *__restrict__ mail)
+{
+    const PreJob jb = jobs[blockIdx.x];
+    const uint8_t *in = jb.in;
+    uint8_t *out = jb.out;
+    const int64_t in_len = jb.in_len, out_cap = jb.out_cap;
+    const uint32_t tid = threadIdx.x;
+    uint32_t *res = mail + 2 * (size_t)blockIdx.x;
+    int64_t pos = 0, op = 0;
+    int status = JPK_OK;
+    while (pos < in_len) {
+        const int64_t wi = pos + (int64_t)(tid & 15u);
+        const uint32_t w = wi < in_len ? in[wi] : 0u;
+        const uint32_t token = win_byte(w, 0);
+        int at = 1;
+        int32_t off = 0;
+        int64_t len = (int64_t)(token >> 3), lit = (int64_t)(token & 7u);
+        int n = leb_win(w, at, in_len - pos - at, &off);
+        if (n < 0) { status = JPK_E_CORRUPT; break; }
+        at += n;
+        if (len == 31) {
+            int32_t e = 0;
+            n = leb_win(w, at, in_len - pos - at, &e);
+            if (n < 0 || e < 0) { status = JPK_E_CORRUPT; break; }
+            at += n;
+            len += e;
+        }
+        len += 4;                                                      // MIN_MATCH, lz77.hpp:33
+        if (lit == 7) {
+            int32_t e = 0;
+            n = leb_win(w, at, in_len - pos - at, &e);
+            if (n < 0 || e < 0) { status = JPK_E_CORRUPT; break; }
+            at += n;
+            lit += e;
+        }
+        pos += at;
+        if (off == 0) {                                                // end marker: raw remainder
+            const int64_t rest = in_len - pos;
+            if (op + rest > out_cap) { status = JPK_E_CAPACITY; break; }
+            for (int64_t k = tid; k < rest; k += PRE_TB) out[op + k] = in[pos + k];
+            op += rest;
+            break;
+        }
+        if (off < 0 || lit > in_len - pos) { status = JPK_E_CORRUPT; break; }
+        if (lit + len > out_cap - op) { status = JPK_E_CAPACITY; break; }
+        for (int64_t k = tid; k < lit; k += PRE_TB) out[op + k] = in[pos + k];
+        op += lit;
+        pos += lit;
+        if ((int64_t)off > op) { status = JPK_E_CORRUPT; break; }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __syncthreads();
+        {
+            const uint32_t L = (uint32_t)len, O = (uint32_t)off;       // len <= out_cap - op, off <= op: both below 2^31
+            uint8_t *dst = out + op;
+            const uint8_t *src = dst - O;
+            if (O >= L) {
+                for (uint32_t k = tid; k < L; k += PRE_TB) dst[k] = src[k];
+            } else {
+                uint32_t r = tid % O;
+                const uint32_t step = (uint32_t)PRE_TB % O;
+                for (uint32_t k = tid; k < L; k += PRE_TB) {
+                    dst[k] = src[r];
+                    r += step;
+                    if (r >= O) r -= O;
+                }
+            }
+        }
+        op += len;
+    }
+    if (tid == 0) { res[0] = (uint32_t)status; res[1] = status == JPK_OK ? (uint32_t)op : 0u; }
+}
+
+// ---- LPX -----------------------------------------------------------------------------------------------------------------------
+struct PrefixRecord { uint32_t cxt, pos, hits, miss; int32_t threshold; };
+constexpr int LPX_MAX_THRESHOLD = 128, LPX_MIN_THRESHOLD = 4;
+constexpr uint32_t LPX_MAX_RECORD = 64u << 10;
+constexpr uint32_t LPX_TILE = 16u << 10;
+constexpr uint32_t LPX_RING = LPX_MAX_RECORD + LPX_TILE;         // position p lives at p mod LPX_RING until p + LPX_RING is written
+
+// LpxState::update of prestage.cpp (lpx.cpp:11-52), the tables in LDS
+__device__ __forceinline__ void lpx_update(PrefixRecord (*table)[256], uint32_t cxt, int &order, uint32_t pos)
+{
+    const uint32_t lp = (cxt >> (order * 8)) & 0xffu;
+    const uint32_t ls = cxt & ((1u << (order * 8)) - 1u);
+    PrefixRecord *r = &table[order - 1][lp];
+    const int32_t distance = (int32_t)(pos - r->pos);
+    const int32_t lower = LPX_MIN_THRESHOLD;
+    int32_t upper;
+    if (r->hits < (uint32_t)LPX_MAX_THRESHOLD) upper = distance > LPX_MIN_THRESHOLD ? distance : LPX_MIN_THRESHOLD;
+    else { const int32_t a = distance >> order, b = LPX_MAX_THRESHOLD >> order; upper = a < b ? a : b; }
+    const int32_t bound = (distance <= lower) ? lower : (distance > upper ? upper : distance);
+    if (pos <= (uint32_t)order) return;
+    if (r->cxt == ls) {
+        r->pos = pos - (uint32_t)order;
+        r->hits++;
+        r->miss = 0;
+        if (r->hits > (uint32_t)((r->threshold << order) << 3) && order > 1 && order <= 3) order--;
+        r = &table[order - 1][lp];                                     // re-indexed with the UPDATED order, as the reference does
+        if (r->hits > (uint32_t)(r->threshold << 1) && r->miss == 0) r->threshold += (bound - r->threshold) >> order;
+    } else {
+        r->hits >>= 2;
+        r->miss++;
+        r->cxt = ls;
+        if (r->miss > (uint32_t)(r->threshold * r->threshold * order) && order >= 1 && order < 3) order++;
+        r = &table[order - 1][lp];
+        if (r->miss > (uint32_t)r->threshold) r->threshold += (LPX_MAX_THRESHOLD - r->threshold) >> (4 - order);
+    }
+}
+
+// One workgroup per part (Lpx::Decode cuts a block into parts of len / 4 bytes, each with a fresh model).  The model is byte-serial and
+// adaptive -- every byte's prediction depends on the tables the byte in front of it left -- so the chain of a part is ONE lane, with
+// the three tables (15 KiB), the input tile and the last 64 KiB + one tile of output in LDS; the other lanes only move tiles between HBM
+// and LDS.  lpx_decode_part's inner do-while (a predicted stretch runs on while the error byte is 0) is the `run` flag here, so that a
+// stretch may cross a tile edge.
+__global__ __launch_bounds__(PRE_TB) void k_pre_lpx(const PreJob *__restrict__ jobs, uint32_t n)
+{
+    __shared__ PrefixRecord table[3][256];
+    __shared__ uint8_t s_in[LPX_TILE];
+    __shared__ uint8_t ring[LPX_RING];
+    const uint32_t tid = threadIdx.x;
+    const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
+    const uint32_t len = (uint32_t)jb.in_len, part = len / 4u, pi = blockIdx.x - jb.wg0;
+    const uint32_t start = part ? pi * part : 0u;
+    if (start >= len) return;
+    const uint32_t plen = (part && part < len - start) ? part : len - start;
+    const uint8_t *in = jb.in + start;
+    uint8_t *out = jb.out + start;
+    for (uint32_t k = tid; k < 3u * 256u; k += PRE_TB) {
+        PrefixRecord r;
+        r.cxt = 0; r.pos = 0; r.hits = 0; r.miss = 0; r.threshold = LPX_MAX_THRESHOLD >> 1;
+        table[k >> 8][k & 255u] = r;
+    }
+    uint32_t cxt = 0, dist = 0;
+    int order = 3;
+    bool run = false;
+    for (uint32_t base = 0; base < plen; base += LPX_TILE) {
+        const uint32_t cnt = plen - base < LPX_TILE ? plen - base : LPX_TILE;
+        const uint32_t rb = base % LPX_RING;
+        for (uint32_t k = tid; k < cnt; k += PRE_TB) s_in[k] = in[base + k];
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t wi = rb;                                          // ring index of position i
+            for (uint32_t k = 0; k < cnt; k++) {
+                const uint32_t i = base + k;
+                if (!run) {
+                    const PrefixRecord *r = &table[order - 1][cxt & 0xffu];
+                    const uint32_t d = i - r->pos;
+                    if (r->hits > (uint32_t)r->threshold && d < LPX_MAX_RECORD && d <= i) { run = true; dist = d; }
+                }
+                const uint8_t e = s_in[k];
+                uint8_t o = e;
+                if (run) {
+                    const uint32_t hi = wi >= dist ? wi - dist : wi + LPX_RING - dist;
+                    o = (uint8_t)(ring[hi] ^ e);
+                    if (e != 0) run = false;
+                }
+                ring[wi] = o;
+                lpx_update(table, cxt, order, i);
+                cxt = (cxt << 8) | o;
+                wi = wi + 1 == LPX_RING ? 0u : wi + 1;
+            }
+        }
+        __syncthreads();
+        for (uint32_t k = tid; k < cnt; k += PRE_TB) {
+            const uint32_t q = rb + k;
+            out[base + k] = ring[q >= LPX_RING ? q - LPX_RING : q];
+        }
+    }
+}
+
+// ---- filters -------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t FBS = 64u << 10;
+
+// Running sums with stride W in LDS, in place: s[k0 + m W + c] += s[k0 + (m - 1) W + c] for m = 1 .. M - 1, every channel c < W on
+// its own (mod 256).  Thread t owns channel t mod W and the (t / W)-th run of rows: partial sums, their prefix over the runs in front
+// of its own, then the running sum over its rows.  All threads of the workgroup call it.
+__device__ __forceinline__ void scan_stride(uint8_t *s, uint32_t *part, uint32_t k0, uint32_t W, uint32_t M)
+{
+    const uint32_t tid = threadIdx.x, ch = tid % W, sg = tid / W, nseg = (uint32_t)PRE_TB / W;
+    const uint32_t rows = (M + nseg - 1) / nseg;
+    const uint32_t m0 = sg < nseg ? (sg * rows < M ? sg * rows : M) : M, m1 = m0 + rows < M ? m0 + rows : M;
+    uint32_t sum = 0;
+    for (uint32_t m = m0; m < m1; m++) sum += s[k0 + m * W + ch];
+    part[tid] = sum;
+    __syncthreads();
+    uint32_t acc = 0;
+    if (sg < nseg) for (uint32_t g = 0; g < sg; g++) acc += part[g * W + ch];
+    for (uint32_t m = m0; m < m1; m++) {
+        acc += s[k0 + m * W + ch];
+        s[k0 + m * W + ch] = (uint8_t)acc;
+    }
+    __syncthreads();
+}
+
+// One workgroup per filter block: block j of a stream starts at j (65536 + 2) and writes at j 65536 (all blocks but the last are full).
+// mail[b] (preset to 0xFFFFFFFF) takes the minimum of (j << 1 | capacity) over the blocks that fail, so that the host reports what
+// jpk_filters_decode reports: the status of the FIRST failing block, its header checked before its capacity.
+__global__ __launch_bounds__(PRE_TB) void k_pre_filters(const PreJob *__restrict__ jobs, uint32_t n, uint32_t *__restrict__ mail)
+{
+    __shared__ uint8_t s[FBS];
+    __shared__ uint32_t part[PRE_TB];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t b = job_of(jobs, n, blockIdx.x);
+    const PreJob jb = jobs[b];
+    const int64_t in_len = jb.in_len, out_cap = jb.out_cap;
+    const uint32_t j = blockIdx.x - jb.wg0;
+    const int64_t i0 = (int64_t)j * (FBS + 2);
+    if (i0 >= in_len) return;
+    if (i0 + 2 > in_len) { if (tid == 0) atomicMin(&mail[b], j << 1); return; }
+    const uint32_t type = jb.in[i0], width = jb.in[i0 + 1];
+    if (type >= 3 || width > 32) { if (tid == 0) atomicMin(&mail[b], j << 1); return; }       // "unsupported configuration", filters.cpp:455
+    const uint32_t len = in_len - (i0 + 2) < (int64_t)FBS ? (uint32_t)(in_len - (i0 + 2)) : FBS;
+    const int64_t op = (int64_t)j * FBS;
+    if (op + len > out_cap) { if (tid == 0) atomicMin(&mail[b], (j << 1) | 1u); return; }
+    const uint8_t *src = jb.in + i0 + 2;
+    uint8_t *dst = jb.out + op;
+    if (width == 0) {
+        for (uint32_t k = tid; k < len; k += PRE_TB) dst[k] = src[k];
+        return;
+    }
+    for (uint32_t k = tid; k < len; k += PRE_TB) s[k] = src[k];
+    __syncthreads();
+    if (type == 2) {                                                   // InlineUndelta: running sum per channel in place, behind a raw head
+        const uint32_t k0 = len % width;
+        scan_stride(s, part, k0, width, (len - k0) / width);
+        for (uint32_t k = tid; k < len; k += PRE_TB) dst[k] = s[k];
+        return;
+    }
+    if (type == 0) {                                                   // DeltaDecode: running sum over the whole block
+        scan_stride(s, part, 0, 1, len);
+    } else {                                                           // LpcDecode: x = w + 2 p1 - p2 - err, w += (err - w) >> 6; serial
+        if (tid == 0) {
+            int32_t weight = 0;
+            uint8_t p1 = 0, p2 = 0;
+            for (uint32_t k = 0; k < len; k++) {
+                const uint8_t err = s[k];
+                const uint8_t cur = (uint8_t)(weight + (((int32_t)p1 - (int32_t)p2) + (int32_t)p1) - (int32_t)err);
+                s[k] = cur;
+                weight += ((int32_t)err - weight) >> 6;
+                p2 = p1;
+                p1 = cur;
+            }
+        }
+        __syncthreads();
+    }
+    // Unreorder: channel c holds bytes c, c + width, ...: it has len / width elements, one more when c < len mod width
+    const uint32_t q = len / width, r = len % width;
+    for (uint32_t k = tid; k < len; k += PRE_TB) {
+        const uint32_t c = k % width;
+        dst[k] = s[c * q + (c < r ? c : r) + k / width];
+    }
+}
+
+// jobs + mail words of one call in the context's arena
+struct PreCall {
+    PreJob *d_jobs = nullptr;
+    uint32_t *d_mail = nullptr;
+};
+
+int pre_upload(jpk_ctx *ctx, const std::vector<PreJob> &jobs, size_t mail_words, int mail_fill, PreCall *pc)
+{
+    Arena plan(ctx, true);
+    plan.get<PreJob>(jobs.size());
+    plan.get<uint32_t>(mail_words + 1);
+    JPK_TRY(jpk_arena_ensure(ctx, plan.need));
+    Arena real(ctx, false);
+    pc->d_jobs = real.get<PreJob>(jobs.size());
+    pc->d_mail = real.get<uint32_t>(mail_words + 1);
+    JPK_HIP(hipMemcpyAsync(pc->d_jobs, jobs.data(), jobs.size() * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
+    if (mail_words) JPK_HIP(hipMemsetAsync(pc->d_mail, mail_fill, mail_words * 4, ctx->stream));
+    return JPK_OK;
+}
+
+int pre_enter(jpk_ctx *ctx)
+{
+    if (!ctx) return JPK_E_ARG;
+    JPK_HIP(hipSetDevice(ctx->device));
+    return JPK_OK;
+}
+
+int pre_finish(jpk_ctx *ctx, const uint32_t *d_mail, std::vector<uint32_t> &mail)
+{
+    JPK_HIP(hipGetLastError());
+    if (!mail.empty()) JPK_HIP(hipMemcpyAsync(mail.data(), d_mail, mail.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof_on) jpk_prof_resolve(ctx);
+    return JPK_OK;
+}
+
+int first_status(int32_t n, const int32_t *st)
+{
+    for (int b = 0; b < n; b++) if (st[b] != JPK_OK) return st[b];
+    return JPK_OK;
+}
+
+}  // namespace
+
+extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                              const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    std::vector<PreJob> jobs((size_t)n);
+    uint64_t bytes = 0;
+    for (int b = 0; b < n; b++) {
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
+        jobs[(size_t)b] = PreJob{d_in[b], d_out[b], in_len[b], out_cap[b], (uint32_t)b, 0u};
+        bytes += (uint32_t)in_len[b];
+    }
+    PreCall pc;
+    JPK_TRY(pre_upload(ctx, jobs, 2 * (size_t)n, 0, &pc));
+    JPK_LAUNCH(ctx, PROF_PRE_LZ77, bytes, k_pre_lz77, dim3((unsigned)n), dim3(PRE_TB), pc.d_jobs, pc.d_mail);
+    std::vector<uint32_t> mail(2 * (size_t)n);
+    JPK_TRY(pre_finish(ctx, pc.d_mail, mail));
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    for (int b = 0; b < n; b++) {
+        stp[b] = (int32_t)mail[2 * (size_t)b];
+        out_len[b] = stp[b] == JPK_OK ? (int32_t)mail[2 * (size_t)b + 1] : 0;
+    }
+    return status ? JPK_OK : first_status(n, stp);
+}
+
+extern "C" int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !len || !d_out))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    std::vector<PreJob> jobs((size_t)n);
+    uint64_t wgs = 0, bytes = 0;
+    for (int b = 0; b < n; b++) {
+        if (len[b] < 0 || (len[b] > 0 && (!d_in[b] || !d_out[b]))) return JPK_E_ARG;
+        jobs[(size_t)b] = PreJob{d_in[b], d_out[b], len[b], len[b], (uint32_t)wgs, 0u};
+        // Lpx::Decode's loop `for (i = 0; i < len; i += part)` with part = len / 4: four parts, more when len is not a multiple of 4
+        // (a fifth, short one; up to seven for len < 8); one part for len < 4
+        const uint32_t part = (uint32_t)len[b] / 4u;
+        wgs += part ? ((uint32_t)len[b] + part - 1) / part : (len[b] ? 1u : 0u);
+        bytes += (uint32_t)len[b];
+    }
+    if (wgs > 0x7fffffffull) return JPK_E_ARG;
+    if (wgs) {
+        PreCall pc;
+        JPK_TRY(pre_upload(ctx, jobs, 0, 0, &pc));
+        JPK_LAUNCH(ctx, PROF_PRE_LPX, bytes, k_pre_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n);
+        std::vector<uint32_t> none;
+        JPK_TRY(pre_finish(ctx, nullptr, none));
+    }
+    if (status) for (int b = 0; b < n; b++) status[b] = JPK_OK;      // any byte string is a valid stream
+    return JPK_OK;
+}
+
+extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                             const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    std::vector<PreJob> jobs((size_t)n);
+    std::vector<uint32_t> nfb((size_t)n);
+    uint64_t wgs = 0, bytes = 0;
+    for (int b = 0; b < n; b++) {
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
+        jobs[(size_t)b] = PreJob{d_in[b], d_out[b], in_len[b], out_cap[b], (uint32_t)wgs, 0u};
+        nfb[(size_t)b] = (uint32_t)(((int64_t)in_len[b] + FBS + 1) / (FBS + 2));
+        wgs += nfb[(size_t)b];
+        bytes += (uint32_t)in_len[b];
+    }
+    if (wgs > 0x7fffffffull) return JPK_E_ARG;
+    std::vector<uint32_t> mail((size_t)n, 0xFFFFFFFFu);
+    if (wgs) {
+        PreCall pc;
+        JPK_TRY(pre_upload(ctx, jobs, (size_t)n, 0xFF, &pc));
+        JPK_LAUNCH(ctx, PROF_PRE_FILTERS, bytes, k_pre_filters, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n, pc.d_mail);
+        JPK_TRY(pre_finish(ctx, pc.d_mail, mail));
+    }
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    for (int b = 0; b < n; b++) {
+        const uint32_t m = mail[(size_t)b];
+        stp[b] = m == 0xFFFFFFFFu ? JPK_OK : ((m & 1u) ? JPK_E_CAPACITY : JPK_E_CORRUPT);
+        out_len[b] = stp[b] == JPK_OK ? in_len[b] - 2 * (int32_t)nfb[(size_t)b] : 0;
+    }
+    return status ? JPK_OK : first_status(n, stp);
+}
