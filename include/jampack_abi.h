@@ -157,8 +157,9 @@ JPK_API int jpk_checksum(const uint8_t *in, int32_t in_len, uint32_t *crc);
 /* One framed block of a .jam stream: Jampack::Comp() (crc of the input, jampack.cpp:31) + CompWriteBlock
  * (jampack.cpp:122-135):  "JAM" | u32 crc | i32 payload size | i32 BlockSize | payload   (15-byte header, LE).
  * The payload is jpk_block_compress(in): the reference CLI additionally runs its LZ77 / filter / LPX pre-stages in
- * front of the BWT (jampack.cpp:33-38), so frames interchange with a reference build whose Comp()/Decomp() call
- * this path, not with the stock CLI.  block_size is Options.BlockSize and must lie in
+ * front of the BWT (jampack.cpp:33-38), so these frames interchange with a reference build whose Comp()/Decomp() call
+ * this path; an unmodified `jampack d` rejects them.  jpk_jam_cli_block_write below writes the frame
+ * the stock CLI decodes.  block_size is Options.BlockSize and must lie in
  * [JPK_MIN_BLOCKSIZE, JPK_MAX_BLOCKSIZE] with in_len <= block_size. */
 JPK_API int jpk_jam_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len);
 /* DecompReadBlock + Decomp() (jampack.cpp:140-164, 47-60): validates the header exactly as the reference does
@@ -167,11 +168,14 @@ JPK_API int jpk_jam_block_write(const uint8_t *in, int32_t in_len, int32_t block
  * runs past in_len, or a crc mismatch ("Detected corrupt block!", jampack.cpp:59). */
 JPK_API int jpk_jam_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed);
 
-/* ---- pre-stage decoders + frames of the stock CLI (host code, no GPU involved) ------------ */
+/* ---- pre-stage decoders, stored-form encoders + frames of the stock CLI (host code) ------- */
 /* Lz77::Decompress(Buffer,Buffer)                      lz77.hpp:22, lz77.cpp:678-714 */
 JPK_API int jpk_lz77_decompress(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len);
 /* Lpx::Decode(Buffer,Buffer,Options)                   lpx.hpp:32, lpx.cpp:101-169 (output length = input length) */
 JPK_API int jpk_lpx_decode(const uint8_t *in, int32_t len, uint8_t *out);
+/* Lpx::Encode(Buffer,Buffer,Options)                   lpx.hpp:31, lpx.cpp:56-99, 148-158 (output length = input length),
+ * bit-identical to the reference; jpk_lpx_decode(jpk_lpx_encode(x)) == x */
+JPK_API int jpk_lpx_encode(const uint8_t *in, int32_t len, uint8_t *out);
 /* Filters::Decode(Buffer,Buffer)                       filters.hpp:44, filters.cpp:442-490 */
 JPK_API int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len);
 /* Checksum::IntegrityCheck on the host                 checksum.cpp:12-36 */
@@ -180,6 +184,23 @@ JPK_API uint32_t jpk_checksum_host(const uint8_t *p, int32_t size);
  * (jampack.cpp:47-60, 140-164) -- Ans::Decode and InverseBwt on the GPU, Lz77::Decompress, Lpx::Decode,
  * Filters::Decode, Lz77::Decompress on the host, then the crc check.  *consumed = 15 + payload size. */
 JPK_API int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed);
+
+/* The stages the stock CLI's decoder undoes behind its inverse BWT, written WITHOUT match finding or filter selection (the format
+ * lets LZ77 and Filters be written as "stored"; Lpx::Encode runs exactly).  For a raw block R of n bytes:
+ *   S1 = 04 80 | R                  the LZ77 end token (offset 0: the rest are literals, lz77.cpp:620, 705-711)
+ *   S2 = every 64 KiB piece of S1 behind a 00 00 header (raw, filters.cpp:421-426); split as filters.cpp:245
+ *   S3 = Lpx::Encode(S2),  S4 = 04 80 | S3
+ * jpk_cli_stages_bound: |S4| = n + 4 + 2 * ceil((n + 2) / 65536), exact (JPK_E_ARG, < 0, for n < 0).  jpk_cli_stages_encode writes S4:
+ * *out_len = the bound, JPK_E_CAPACITY when out_cap is below it.  The stock encoder's output for the same block differs (it finds
+ * matches and picks filters); both decode to R. */
+JPK_API int64_t jpk_cli_stages_bound(int64_t n);
+JPK_API int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len);
+/* The counterpart of jpk_jam_cli_block_read: one frame an unmodified `jampack d` decodes -- the 15-byte header of jpk_jam_block_write
+ * (crc of `in`, payload size, BlockSize) + jpk_block_compress(S4).  The stages run on the host, ForwardBwt + Ans::Encode on the GPU.
+ * Arguments as jpk_jam_block_write: block_size in [JPK_MIN_BLOCKSIZE, JPK_MAX_BLOCKSIZE], in_len <= block_size (JPK_E_ARG), out_cap
+ * below the header or the frame JPK_E_CAPACITY.  With the BWT trailer S4 fits the decoder's (int)(BlockSize * 1.05) stage buffers
+ * (jampack.cpp:157) for every such in_len (the arithmetic is in prestage.cpp). */
+JPK_API int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len);
 
 /* ---- device-buffer entry points (all pointers except ctx/out_len are HBM addresses on ctx's device) ---- */
 /* ADDRESSES AND BOUNDS of every jpk_dev_* stage entry and probe (tests/test_gpu_stage_contracts.py, tests/test_gpu_primitives.py):
@@ -291,6 +312,14 @@ JPK_API int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t *co
 /*   Filters::Decode(Buffer,Buffer)             filters.hpp:44, filters.cpp:442-490   one workgroup per 64 KiB filter block */
 JPK_API int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                           const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/*   Lpx::Encode(Buffer,Buffer,Options)         lpx.hpp:31, lpx.cpp:56-99, 148-158   the mirror image: one workgroup per part, one lane runs
+ *   its model over the input; the bytes of jpk_lpx_encode; writes exactly len[b] bytes */
+JPK_API int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status);
+/*   the whole stage chain of jpk_cli_stages_encode, two launches for all blocks (the stored forms, then Lpx::Encode; S2 lives in ctx's
+ *   arena): out_len[b] = jpk_cli_stages_bound(in_len[b]), the bytes of the host form.  A block whose out_cap is below that reports
+ *   JPK_E_CAPACITY alone, out_len[b] = 0, and nothing of it is written. */
+JPK_API int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                             const int32_t *out_cap, int32_t *out_len, int32_t *status);
 /* Jampack::Decompress (jampack.cpp:262-336) of an archive written by an unmodified `jampack c` (any -m / -f setting; the frames of
  * jpk_jam_cli_block_read, back to back): the frame walk of jpk_dev_jam_decompress, with an entropy-decoded size of at most
  * 1.05 x BlockSize + 4096 per frame (the reference's stage buffers, jampack.cpp:156), then per pass jpk_dev_blocks_decompress into
@@ -313,6 +342,19 @@ JPK_API int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *o
  * the first bad one, *raw_bound = the sum of their BlockSize (an out_cap that always suffices), *bad_frame = its index (JPK_E_CORRUPT)
  * or -1 (JPK_OK).  No device call.  Pointers other than in may be NULL. */
 JPK_API int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame);
+
+/* The archive an unmodified `jampack d` decodes (with any -t / -T): the frames of jpk_jam_cli_block_write over consecutive block_size
+ * slices of the input, back to back.  The contract is that of jpk_jam_compress_bound / jpk_dev_jam_compress / jpk_jam_compress: the last
+ * slice short, in_len == 0 gives an empty archive, block_size in [JPK_MIN_BLOCKSIZE, JPK_MAX_BLOCKSIZE], JPK_E_CAPACITY when the archive
+ * does not fit out_cap (the bound always suffices), in_flight as jpk_dev_blocks_compress, arguments checked before a device is looked
+ * for.  Per pass: one batched checksum of the raw slices, k_enc_wrap into slot A of every frame, k_enc_lpx from A into slot B (the BWT
+ * inputs), jpk_dev_blocks_compress from the B slots into payload slots, one pack launch.
+ * Per-pass HBM: passes of at most 128 frames and 4 GiB of input; per input byte about 1 byte of slot A, 1 of slot B and 1.25 of
+ * payload slot (<= 14 GB) in the scratch buffer of ctx, on top of the workers' arenas of jpk_dev_blocks_compress. */
+JPK_API int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size);
+JPK_API int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                     int32_t in_flight);
+JPK_API int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight);
 
 /* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
 /* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the

@@ -287,7 +287,15 @@ class Lz77:
 
 
 class Lpx:
-    """Decoder side of `class Lpx` (lpx.hpp:31-32); host code."""
+    """`class Lpx` (lpx.hpp:31-32); host code."""
+
+    def Encode(self, buf) -> np.ndarray:
+        t = _np_u8(buf)
+        out = np.zeros(max(len(t), 1), dtype=np.uint8)
+        _chk(lib().jpk_lpx_encode(_ptr(t), len(t), out.ctypes.data), "Lpx::Encode")
+        return out[: len(t)]
+
+    encode = Encode
 
     def Decode(self, buf) -> np.ndarray:
         t = _np_u8(buf)
@@ -320,6 +328,51 @@ def jam_cli_block_read(stream, cap: int):
     n, used = C.c_int32(0), C.c_int32(0)
     _chk(lib().jpk_jam_cli_block_read(_ptr(c), len(c), out.ctypes.data, cap, C.byref(n), C.byref(used)), "jam_cli_block_read")
     return out[: n.value], used.value
+
+
+def cli_stages_bound(n: int) -> int:
+    """jpk_cli_stages_bound: the bytes the stored-form stage chain makes of an n-byte block (what goes into the BWT)"""
+    b = int(lib().jpk_cli_stages_bound(n))
+    _chk(b if b < 0 else 0, "jpk_cli_stages_bound")
+    return b
+
+
+def cli_stages_encode(block, cap: int | None = None) -> np.ndarray:
+    """jpk_cli_stages_encode: end token | Lpx::Encode(raw filter pieces of (end token | block)) -- what the stock decoder's four
+    pre-stage decoders turn back into `block`; host code."""
+    t = _np_u8(block)
+    cap = cli_stages_bound(len(t)) if cap is None else cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_int32(0)
+    _chk(lib().jpk_cli_stages_encode(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "jpk_cli_stages_encode")
+    return out[: n.value]
+
+
+def jam_cli_block_write(block, block_size: int, cap: int | None = None) -> np.ndarray:
+    """One frame an unmodified `jampack d` decodes: the header of jam_block_write + block_compress of the stage chain of `block`."""
+    t = _np_u8(block)
+    cap = JAM_HEADER + ans_capacity(cli_stages_bound(len(t)) + TRAILER) if cap is None else cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_int32(0)
+    _chk(lib().jpk_jam_cli_block_write(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n)), "jam_cli_block_write")
+    return out[: n.value]
+
+
+def jam_cli_compress_bound(n: int, block_size: int = 8 << 20) -> int:
+    """jpk_jam_cli_compress_bound: the largest stock-CLI archive n input bytes can give with this block size"""
+    b = int(lib().jpk_jam_cli_compress_bound(n, block_size))
+    _chk(b if b < 0 else 0, "jpk_jam_cli_compress_bound")
+    return b
+
+
+def jam_cli_compress(data, block_size: int = 8 << 20) -> np.ndarray:
+    """The archive an unmodified `jampack d` decodes, made by one jpk_jam_cli_compress call: frames of block_size input bytes, the
+    pre-stages written in their stored forms + Lpx::Encode on the GPU, then the batch engine."""
+    t = _np_u8(data)
+    out = np.empty(max(jam_cli_compress_bound(len(t), block_size), 1), dtype=np.uint8)
+    n = C.c_int64(0)
+    _chk(lib().jpk_jam_cli_compress(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0), "jam_cli_compress")
+    return out[: n.value]
 
 
 def jam_cli_decompress(stream) -> np.ndarray:
@@ -480,6 +533,18 @@ class Context:
         _chk(lib().jpk_dev_blocks_lpx_decode(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*lens), P(*[_dptr(x) for x in d_outs]), st), "jpk_dev_blocks_lpx_decode")
         return list(st)[:n]
 
+    def blocks_lpx_encode(self, d_ins, lens, d_outs):
+        """jpk_dev_blocks_lpx_encode: Lpx::Encode of independent blocks in one launch (output length = input length) -> status list"""
+        n = len(d_ins)
+        P, I = C.c_void_p * max(n, 1), C.c_int32 * max(n, 1)
+        st = I()
+        _chk(lib().jpk_dev_blocks_lpx_encode(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*lens), P(*[_dptr(x) for x in d_outs]), st), "jpk_dev_blocks_lpx_encode")
+        return list(st)[:n]
+
+    def blocks_cli_stages_encode(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_cli_stages_encode: the stored-form stage chain of independent blocks in two launches -> (out_len list, status list)"""
+        return self._batch(lib().jpk_dev_blocks_cli_stages_encode, "jpk_dev_blocks_cli_stages_encode", d_ins, in_lens, d_outs, out_caps)
+
     def blocks_filters_decode(self, d_ins, in_lens, d_outs, out_caps):
         """jpk_dev_blocks_filters_decode: Filters::Decode of independent blocks in one launch -> (out_len list, status list)"""
         return self._batch(lib().jpk_dev_blocks_filters_decode, "jpk_dev_blocks_filters_decode", d_ins, in_lens, d_outs, out_caps)
@@ -522,6 +587,12 @@ class Context:
         """jpk_dev_jam_compress: the whole archive of d_in[0..in_len) into d_out; returns its length"""
         n = C.c_int64(0)
         _chk(lib().jpk_dev_jam_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_compress")
+        return n.value
+
+    def jam_cli_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0) -> int:
+        """jpk_dev_jam_cli_compress: the archive of d_in[0..in_len) an unmodified `jampack d` decodes, into d_out; returns its length"""
+        n = C.c_int64(0)
+        _chk(lib().jpk_dev_jam_cli_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_cli_compress")
         return n.value
 
     def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):

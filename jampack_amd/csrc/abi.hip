@@ -110,7 +110,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
     "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
-    "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
+    "k_enc_wrap", "k_enc_lpx", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {
@@ -1843,6 +1843,28 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
     return JPK_OK;
 }
 
+// The counterpart: crc (jampack.cpp:31), the stage chain of jpk_cli_stages_encode on the host in place of Jampack::Comp()'s four
+// pre-stage encoders (jampack.cpp:36-39), ForwardBwt + Ans::Encode on the GPU, the header of CompWriteBlock (jampack.cpp:122-135).
+extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    if (!jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
+    if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
+    const int32_t cap = (int32_t)jpk_cli_stages_bound(in_len);                       // < 2^31 for in_len <= JPK_MAX_BLOCKSIZE (prestage.cpp)
+    static thread_local std::vector<uint8_t> s4;
+    try { if (s4.size() < (size_t)cap) s4.resize((size_t)cap); } catch (...) { return JPK_E_ALLOC; }
+    int32_t m = 0, n = 0;
+    JPK_TRY(jpk_cli_stages_encode(in, in_len, s4.data(), cap, &m));
+    JPK_TRY(jpk_block_compress(s4.data(), m, out + JPK_JAM_HEADER_BYTES, out_cap - JPK_JAM_HEADER_BYTES, &n));
+    const uint32_t crc = jpk_checksum_host(in, in_len);
+    memcpy(out, "JAM", 3);
+    memcpy(out + 3, &crc, 4);
+    memcpy(out + 7, &n, 4);
+    memcpy(out + 11, &block_size, 4);
+    *out_len = n + JPK_JAM_HEADER_BYTES;
+    return JPK_OK;
+}
+
 // ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
 // Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
 // in ctx->jam_scratch, the frame offsets on the host (64-bit), one k_jam_pack launch that writes the frames.  Decompress: the frame
@@ -1851,6 +1873,9 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
 // then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out (its payload read in place in the archive),
 // one batched checksum of the outputs, and the comparison with the header crcs.  A pass holds at most JPK_JAM_PASS_FRAMES frames
 // and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
+// The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
+// the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
+// of the raw slices.
 namespace {
 constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
 
@@ -1936,30 +1961,46 @@ size_t jam_pass_end(const std::vector<JamFrame> &fr, size_t k)
     return e;
 }
 
-// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len)
+// what the batch compress is given for a raw slice of len bytes: the slice, or its S4 (cli; prestage.cpp) -- and the payload it can give
+int32_t jam_bwt_len(int32_t len, bool cli) { return cli ? (int32_t)jpk_cli_stages_bound(len) : len; }
+int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap(jam_bwt_len(len, cli)); }
+
+// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
+// of the stock CLI
 int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
-                      int32_t in_flight)
+                      int32_t in_flight, bool cli)
 {
     const int n = (int)((len + block_size - 1) / block_size);
-    std::vector<const uint8_t *> ins((size_t)n);
-    std::vector<uint8_t *> slots((size_t)n);
-    std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+    std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
+    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n);
+    std::vector<int32_t> lens((size_t)n), blens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
     const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
     size_t need = o_slots;
     for (int i = 0; i < n; i++) {
         ins[i] = d_in + (int64_t)i * block_size;
         lens[i] = (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size);
-        caps[i] = (int32_t)multi_comp_cap(lens[i]);
+        blens[i] = jam_bwt_len(lens[i], cli);
+        caps[i] = (int32_t)multi_comp_cap(blens[i]);
         need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
+        if (cli) need += 2 * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
     }
     JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
     uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
     JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(ctx->jam_scratch + o_frames);
     size_t off = o_slots;
-    for (int i = 0; i < n; i++) { slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64); }
+    for (int i = 0; i < n; i++) {
+        slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64);
+        bwt_in[i] = ins[i];
+        if (cli) {
+            sa[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
+            sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
+            bwt_in[i] = sb[i];
+        }
+    }
     // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
     JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
-    JPK_TRY(jpk_dev_blocks_compress(ctx, n, ins.data(), lens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
+    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data()));
+    JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
     for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
     std::vector<JamPackFrame> fr((size_t)n);
     uint64_t pos = 0;
@@ -1990,15 +2031,16 @@ extern "C" int jpk_dev_checksums(jpk_ctx *ctx, int32_t n, const uint8_t *const *
     return JPK_OK;
 }
 
-extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size)
+namespace {
+int64_t jam_compress_bound(int64_t in_len, int32_t block_size, bool cli)
 {
     if (in_len < 0 || !jam_block_size_ok(block_size)) return JPK_E_ARG;
     const int64_t full = in_len / block_size, rest = in_len % block_size;
-    return full * (JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap(block_size)) + (rest ? JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap((int32_t)rest) : 0);
+    return full * jam_frame_bound(block_size, cli) + (rest ? jam_frame_bound((int32_t)rest, cli) : 0);
 }
 
-extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                    int32_t in_flight)
+int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                     int32_t in_flight, bool cli)
 {
     JPK_ENTER(ctx);
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out))) return JPK_E_ARG;
@@ -2008,11 +2050,27 @@ extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t i
     int64_t pos = 0;
     for (int64_t o = 0; o < in_len; o += step) {
         int64_t n = 0;
-        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight));
+        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli));
         pos += n;
     }
     *out_len = pos;
     return JPK_OK;
+}
+}  // namespace
+
+extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, false); }
+extern "C" int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, true); }
+
+extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                    int32_t in_flight)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, false);
+}
+
+extern "C" int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                        int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true);
 }
 
 extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
@@ -2087,7 +2145,8 @@ extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames
     return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
 }
 
-extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+namespace {
+int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli)
 {
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out))) return JPK_E_ARG;
     if (!jam_block_size_ok(block_size)) return JPK_E_ARG;
@@ -2099,12 +2158,12 @@ extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block
     const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
     int64_t pos = 0;
     for (int64_t o = 0; o < in_len; o += step) {
-        const int64_t len = std::min(step, in_len - o), bound = jpk_jam_compress_bound(len, block_size);
+        const int64_t len = std::min(step, in_len - o), bound = jam_compress_bound(len, block_size, cli);
         JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 64));
         JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
         JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
         int64_t n = 0;
-        JPK_TRY(jpk_dev_jam_compress(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight));
+        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli));
         if (n > out_cap - pos) return JPK_E_CAPACITY;
         JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         JPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -2112,6 +2171,17 @@ extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block
     }
     *out_len = pos;
     return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, false);
+}
+
+extern "C" int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true);
 }
 
 extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)

@@ -36,7 +36,7 @@ enum JpkProfId {
     PROF_INV_HIST, PROF_INV_BUILD, PROF_INV_WALK, PROF_INV_RANK, PROF_INV_COPY,
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
     PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM,
-    PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
+    PROF_ENC_WRAP, PROF_ENC_LPX, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 
@@ -142,6 +142,35 @@ static inline int jpk_bits_for(uint32_t maxval)
     return b;
 }
 
+// 16 bytes from src (any alignment) through two aligned 16-byte loads (jam.hip, prestage_dev.hip): the caller makes sure that both lie
+// inside memory it may read -- a scratch slot with at least 16 bytes of padding behind its payload, or a range it has checked
+static __device__ __forceinline__ uint4 load16_unaligned(const uint8_t *src)
+{
+    const uintptr_t a = (uintptr_t)src;
+    const uint4 *p = reinterpret_cast<const uint4 *>(a & ~(uintptr_t)15);
+    const uint32_t sh = (uint32_t)(a & 15u);
+    const uint4 x = p[0];
+    if (sh == 0) return x;
+    const uint4 y = p[1];
+    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+    const uint32_t q = sh >> 2, r = sh & 3u;
+    uint32_t v[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {               // v[i] = w[q + i] by selects (q <= 3): no indexed register array
+        uint32_t t = w[i];
+        t = q == 1u ? w[i + 1] : t;
+        t = q == 2u ? w[i + 2] : t;
+        t = q == 3u ? w[i + 3] : t;
+        v[i] = t;
+    }
+    uint4 o;
+    o.x = __builtin_amdgcn_alignbyte(v[1], v[0], r);
+    o.y = __builtin_amdgcn_alignbyte(v[2], v[1], r);
+    o.z = __builtin_amdgcn_alignbyte(v[3], v[2], r);
+    o.w = __builtin_amdgcn_alignbyte(v[4], v[3], r);
+    return o;
+}
+
 // ---- primitives implemented in scan.hip / radix.hip -------------------------------------------------
 // scratch requirements are sized by the *_scratch_words helpers; all buffers come from the arena.
 size_t jpk_scan_scratch_words(size_t n);
@@ -227,3 +256,7 @@ int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, cons
 struct JamGatherPiece { const uint8_t *src; uint8_t *dst; uint64_t len; uint64_t word0; const uint8_t *src_lo; const uint8_t *src_hi; };
 // delivers d_pieces[0..n) (len > 0 each, `words` destination words and `bytes` bytes in all) with one launch.  Enqueued.
 int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_t n, uint64_t words, uint64_t bytes);
+// the writer's stage chain on the device (prestage_dev.hip): R -> S2 (k_enc_wrap) into d_mid[b] (jpk_cli_stages_bound - 2 bytes; d_mid ==
+// nullptr: in ctx's arena) -> S4 = end token | Lpx::Encode(S2) (k_enc_lpx) into d_out[b] (jpk_cli_stages_bound bytes); in_len[b] < 0
+// skips block b.  Two launches; synchronises the stream.
+int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out);

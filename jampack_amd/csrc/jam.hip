@@ -47,34 +47,6 @@ __global__ __launch_bounds__(64) void k_jam_walk(const uint8_t *__restrict__ in,
     }
 }
 
-// 16 bytes from src (any alignment) through two aligned 16-byte loads: the slot has at least 16 bytes of padding behind its payload
-__device__ __forceinline__ uint4 load16_unaligned(const uint8_t *src)
-{
-    const uintptr_t a = (uintptr_t)src;
-    const uint4 *p = reinterpret_cast<const uint4 *>(a & ~(uintptr_t)15);
-    const uint32_t sh = (uint32_t)(a & 15u);
-    const uint4 x = p[0];
-    if (sh == 0) return x;
-    const uint4 y = p[1];
-    const uint32_t w[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-    const uint32_t q = sh >> 2, r = sh & 3u;
-    uint32_t v[5];
-#pragma unroll
-    for (int i = 0; i < 5; i++) {               // v[i] = w[q + i] by selects (q <= 3): no indexed register array
-        uint32_t t = w[i];
-        t = q == 1u ? w[i + 1] : t;
-        t = q == 2u ? w[i + 2] : t;
-        t = q == 3u ? w[i + 3] : t;
-        v[i] = t;
-    }
-    uint4 o;
-    o.x = __builtin_amdgcn_alignbyte(v[1], v[0], r);
-    o.y = __builtin_amdgcn_alignbyte(v[2], v[1], r);
-    o.z = __builtin_amdgcn_alignbyte(v[3], v[2], r);
-    o.w = __builtin_amdgcn_alignbyte(v[4], v[3], r);
-    return o;
-}
-
 // byte p (0 <= p - off < 15 + psize) of frame f: header or payload
 __device__ __forceinline__ uint32_t frame_byte(uint64_t rel, uint32_t crc, int32_t psize, int32_t bs, const uint8_t *slot)
 {

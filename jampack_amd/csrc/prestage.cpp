@@ -2,7 +2,9 @@
 // (Jampack::Decomp, jampack.cpp:47-60: Lz77::Decompress, Lpx::Decode, Filters::Decode, Lz77::Decompress), so that
 // frames written by an unmodified `jampack c` decode end to end: rANS decode + inverse BWT on the GPU, these on the
 // host where SURVEY.md section 8f (row 4) puts them -- byte-serial state machines with no data parallelism.
-// Only the decoder side exists here; the encoders carry float heuristics and stay with the reference.
+// The encoder side is the part of the reference's encoders that a VALID stream needs and no more (writing): the stored forms
+// of LZ77 and Filters, and Lpx::Encode, which has no stored form and is deterministic integer code.  The match finders, the dedupe and the
+// filter selection with their float heuristics stay with the reference.
 //
 // Unlike the reference (which trusts its input outside NDEBUG builds, lz77.cpp:697-701) every read and write is
 // bounds checked and a bad stream gives JPK_E_CORRUPT / JPK_E_CAPACITY.
@@ -137,6 +139,33 @@ struct LpxState {
     }
 };
 
+// Lpx::EncodeBlock (lpx.cpp:56-99): the mirror image of the decoder below.  The whole input is known, so prediction, stretch flag and
+// context all come from input bytes; the model walk (LpxState::update) is the decoder's.  r.pos <= i always holds (update stores
+// pos - order), which is the `dist <= i` the decoder checks on its untrusted stream.
+void lpx_encode_part(const uint8_t *in, uint8_t *out, int64_t len)
+{
+    LpxState *st = new LpxState();
+    for (int64_t i = 0; i < len;) {
+        const PrefixRecord &r = st->table[st->order - 1][st->cxt & 0xffu];
+        const uint32_t dist = (uint32_t)i - r.pos;
+        if (r.hits > (uint32_t)r.threshold && dist < LPX_MAX_RECORD && dist <= (uint32_t)i) {
+            uint8_t err;
+            do {
+                out[i] = err = (uint8_t)(in[i - dist] ^ in[i]);
+                st->update((uint32_t)i);
+                st->cxt = (st->cxt << 8) | in[i];
+                i++;
+            } while (err == 0 && i < len);
+        } else {
+            out[i] = in[i];
+            st->update((uint32_t)i);
+            st->cxt = (st->cxt << 8) | in[i];
+            i++;
+        }
+    }
+    delete st;
+}
+
 // Lpx::DecodeBlock (lpx.cpp:101-144): inside a predicted stretch the stream holds prediction XOR byte
 void lpx_decode_part(const uint8_t *in, uint8_t *out, int64_t len)
 {
@@ -174,6 +203,17 @@ extern "C" int jpk_lpx_decode(const uint8_t *in, int32_t len, uint8_t *out)
     const int64_t part = len / 4;
     if (part == 0) { if (len) lpx_decode_part(in, out, len); return JPK_OK; }
     for (int64_t i = 0; i < len; i += part) lpx_decode_part(in + i, out + i, (i + part < len) ? part : len - i);
+    return JPK_OK;
+}
+
+// Lpx::Encode (lpx.cpp:148-158): the same cut into parts of len / 4 bytes as the decoder, each with a fresh model (and the same
+// pass-through as one part for 0 < len < 4, where the reference does not terminate)
+extern "C" int jpk_lpx_encode(const uint8_t *in, int32_t len, uint8_t *out)
+{
+    if (len < 0 || (len > 0 && (!in || !out))) return JPK_E_ARG;
+    const int64_t part = len / 4;
+    if (part == 0) { if (len) lpx_encode_part(in, out, len); return JPK_OK; }
+    for (int64_t i = 0; i < len; i += part) lpx_encode_part(in + i, out + i, (i + part < len) ? part : len - i);
     return JPK_OK;
 }
 
@@ -226,6 +266,59 @@ extern "C" int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *ou
         i += len;
     }
     *out_len = (int32_t)op;
+    return JPK_OK;
+}
+
+// ---- the stage chain of a frame the stock CLI decodes, written without match finding or filter selection (writing) -------
+//   S1 = end token | R          the token is what the reference's own flush writes, WriteToken(MIN_MATCH, MIN_MATCH, 0) (lz77.cpp:620,
+//                               53-70): token byte (4 - 4) << 3 | 4 = 0x04, then EncodeLeb128(0) = 0x80 (utils.cpp:28-31).  Offset 0 makes
+//                               Lz77::Decompress copy the rest through (lz77.cpp:705-711).
+//   S2 = every 64 KiB piece of S1 behind a 00 00 header (type 0, width 0 = raw, filters.cpp:421-426, 480-483); the split is the
+//                               encoder's own (filters.cpp:245): all pieces but the last are full, an exactly full last piece stays one
+//   S3 = Lpx::Encode(S2)        same length
+//   S4 = end token | S3
+// |S2| = n + 2 + 2 P with P = ceil((n + 2) / 65536) pieces (n + 2 >= 2: at least one), |S4| = n + 4 + 2 P.
+// The two bounds a frame must keep, for n <= BlockSize = B, B >= JPK_MIN_BLOCKSIZE = 2^20:
+//   P <= (B + 2 + 65535) / 65536 <= B / 65536 + 1, so |S4| + 480 (the BWT trailer) <= B + B / 32768 + 486;
+//   the reference's stage buffers hold (int)(B * 1.05) >= B + B / 20 - 1 bytes (jampack.cpp:157), and B / 20 - B / 32768 >= 52396 at
+//   B = 2^20 and grows with B, which is above 487: the frame fits them, and with them this library's own 1.05 B + 4096 on the
+//   entropy-decoded size.  At B = JPK_MAX_BLOCKSIZE |S4| = 1048576000 + 4 + 2 * 16001 stays below 2^31 and below JPK_FWD_BWT_LIMIT.
+namespace {
+constexpr int64_t CLI_FBS = 64 << 10;
+constexpr uint8_t CLI_TOKEN[2] = {0x04, 0x80};
+}
+
+extern "C" int64_t jpk_cli_stages_bound(int64_t n)
+{
+    if (n < 0) return JPK_E_ARG;
+    return n + 4 + 2 * ((n + 2 + CLI_FBS - 1) / CLI_FBS);
+}
+
+extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    const int64_t total = jpk_cli_stages_bound(n);
+    if (total > 0x7fffffff) return JPK_E_ARG;
+    if (total > out_cap) return JPK_E_CAPACITY;
+    const int64_t s1 = (int64_t)n + 2, s2 = total - 2;
+    std::vector<uint8_t> buf;
+    try { buf.resize((size_t)s2); } catch (...) { return JPK_E_ALLOC; }
+    int64_t op = 0;
+    for (int64_t i = 0; i < s1;) {                                     // byte i of S1: the token, then in[i - 2]
+        const int64_t len = (i + CLI_FBS < s1) ? CLI_FBS : s1 - i;
+        if (op + 2 + len > s2) return JPK_E_CAPACITY;                  // cannot happen: s2 counts exactly these bytes
+        buf[(size_t)op] = 0; buf[(size_t)op + 1] = 0;
+        op += 2;
+        int64_t k = 0;
+        for (; i + k < 2 && k < len; k++) buf[(size_t)(op + k)] = CLI_TOKEN[i + k];
+        if (len > k) memcpy(buf.data() + op + k, in + (i + k - 2), (size_t)(len - k));
+        op += len;
+        i += len;
+    }
+    out[0] = CLI_TOKEN[0]; out[1] = CLI_TOKEN[1];
+    const int rc = jpk_lpx_encode(buf.data(), (int32_t)s2, out + 2);
+    if (rc != JPK_OK) return rc;
+    *out_len = (int32_t)total;
     return JPK_OK;
 }
 

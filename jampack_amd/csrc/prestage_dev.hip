@@ -3,6 +3,10 @@
 //   k_pre_lz77     Lz77::Decompress (lz77.cpp:678-714)   one workgroup per block: every lane parses the token, all lanes copy
 //   k_pre_lpx      Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
 //   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
+// and the two kernels of the writer of such frames (writing; the stage chain of jpk_cli_stages_encode):
+//   k_enc_wrap     raw block -> S2: the LZ77 end token and the 00 00 header of every 64 KiB filter piece around the unchanged bytes,
+//                  organised by destination like k_jam_pack: a thread owns aligned 16-byte words of the output
+//   k_enc_lpx      Lpx::Encode      (lpx.cpp:56-99, 148-158) one workgroup per part, the mirror image of k_pre_lpx
 // Each is bit-identical to its host form in prestage.cpp (statuses included) and keeps that file's bounds checks: every read is checked
 // against in_len and every write against out_cap before it is made, in 64-bit arithmetic.  No workgroup waits for another one, every
 // loop is bounded by the stream length or the output capacity, and a bad stream sets the block's mail word and ends the workgroup.
@@ -222,6 +226,69 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_lpx(const PreJob *__restrict__ j
     }
 }
 
+// Lpx::Encode, the mirror image of k_pre_lpx: one workgroup per part, one lane runs the model.  In encode the whole input is known, so the
+// chain reads only INPUT bytes -- the prediction in[i - dist], the byte in[i] it is compared with (the stretch goes on while their XOR
+// is 0) and the context -- and the ring holds the last 64 KiB + one tile of input: all lanes load a tile straight into the ring, lane 0
+// walks it and leaves the error bytes in s_out, all lanes write s_out to HBM.  LDS: tables 15 KiB + ring 80 KiB + tile 16 KiB = 111 KiB,
+// as the decoder: one workgroup per CU.  token != 0: the job's output is S3 inside an S4 buffer and part 0 puts the LZ77 end token
+// (04 80, prestage.cpp) into the two bytes in front of it.
+__global__ __launch_bounds__(PRE_TB) void k_enc_lpx(const PreJob *__restrict__ jobs, uint32_t n, uint32_t token)
+{
+    __shared__ PrefixRecord table[3][256];
+    __shared__ uint8_t s_out[LPX_TILE];
+    __shared__ uint8_t ring[LPX_RING];
+    const uint32_t tid = threadIdx.x;
+    const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
+    const uint32_t len = (uint32_t)jb.in_len, part = len / 4u, pi = blockIdx.x - jb.wg0;
+    const uint32_t start = part ? pi * part : 0u;
+    if (start >= len) return;
+    const uint32_t plen = (part && part < len - start) ? part : len - start;
+    const uint8_t *in = jb.in + start;
+    uint8_t *out = jb.out + start;
+    if (token && pi == 0 && tid == 0) { jb.out[-2] = 0x04; jb.out[-1] = 0x80; }
+    for (uint32_t k = tid; k < 3u * 256u; k += PRE_TB) {
+        PrefixRecord r;
+        r.cxt = 0; r.pos = 0; r.hits = 0; r.miss = 0; r.threshold = LPX_MAX_THRESHOLD >> 1;
+        table[k >> 8][k & 255u] = r;
+    }
+    uint32_t cxt = 0, dist = 0;
+    int order = 3;
+    bool run = false;
+    for (uint32_t base = 0; base < plen; base += LPX_TILE) {
+        const uint32_t cnt = plen - base < LPX_TILE ? plen - base : LPX_TILE;
+        const uint32_t rb = base % LPX_RING;
+        for (uint32_t k = tid; k < cnt; k += PRE_TB) {
+            const uint32_t q = rb + k;
+            ring[q >= LPX_RING ? q - LPX_RING : q] = in[base + k];
+        }
+        __syncthreads();                                               // (orders the table set-up and the last tile's s_out reads as well)
+        if (tid == 0) {
+            uint32_t wi = rb;                                          // ring index of position i
+            for (uint32_t k = 0; k < cnt; k++) {
+                const uint32_t i = base + k;
+                if (!run) {
+                    const PrefixRecord *r = &table[order - 1][cxt & 0xffu];
+                    const uint32_t d = i - r->pos;
+                    if (r->hits > (uint32_t)r->threshold && d < LPX_MAX_RECORD && d <= i) { run = true; dist = d; }
+                }
+                const uint8_t c = ring[wi];
+                uint8_t e = c;
+                if (run) {
+                    const uint32_t hi = wi >= dist ? wi - dist : wi + LPX_RING - dist;
+                    e = (uint8_t)(ring[hi] ^ c);
+                    if (e != 0) run = false;
+                }
+                s_out[k] = e;
+                lpx_update(table, cxt, order, i);
+                cxt = (cxt << 8) | c;
+                wi = wi + 1 == LPX_RING ? 0u : wi + 1;
+            }
+        }
+        __syncthreads();
+        for (uint32_t k = tid; k < cnt; k += PRE_TB) out[base + k] = s_out[k];
+    }
+}
+
 // ---- filters -------------------------------------------------------------------------------------------------------------------
 constexpr uint32_t FBS = 64u << 10;
 
@@ -305,6 +372,70 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_filters(const PreJob *__restrict
     }
 }
 
+// ---- the stored forms: raw block -> S2 ----------------------------------------------------------------------------------------------
+constexpr uint32_t WRAP_PIECE = FBS + 2;                              // one filter piece in S2: header + 64 KiB of S1
+constexpr uint32_t WRAP_WORDS = 4;                                    // 16-byte words per thread: a workgroup writes 16 KiB
+
+// byte p of S2 (prestage.cpp: S1 = 04 80 | R, every 64 KiB piece of S1 behind 00 00)
+__device__ __forceinline__ uint32_t wrap_byte(uint32_t p, const uint8_t *__restrict__ in)
+{
+    const uint32_t pj = p / WRAP_PIECE, r = p % WRAP_PIECE;
+    if (r < 2u) return 0u;
+    const uint32_t s1 = pj * FBS + r - 2u;
+    return s1 < 2u ? (s1 == 0u ? 0x04u : 0x80u) : in[s1 - 2u];
+}
+
+// Job: in = R (in_len bytes), out = S2 (out_cap = |S2| bytes), wg0 as for the other kernels; a workgroup owns WRAP_WORDS * PRE_TB
+// consecutive aligned 16-byte words of the job's output (word w = the 16 bytes at base + 16 w, base = out rounded down to 16).  A whole
+// word whose bytes all come from R -- S2[p] = R[p - 2 j - 4] inside piece j, behind its header and behind the token -- moves through two
+// aligned 16-byte loads when both lie inside R; every other word (a header, the token, the ends of R or of S2) is assembled byte by byte,
+// whole words stored once, the partial words at the two ends with byte stores.  Nothing outside [out, out + |S2|) is written.
+__global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const PreJob *__restrict__ jobs, uint32_t n)
+{
+    const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
+    const uint32_t total = (uint32_t)jb.out_cap;
+    const uintptr_t base = (uintptr_t)jb.out & ~(uintptr_t)15, r_lo = (uintptr_t)jb.in, r_hi = r_lo + (uint32_t)jb.in_len;
+    const uint32_t lead = (uint32_t)((uintptr_t)jb.out - base);
+    const uint32_t words = (uint32_t)(((uint64_t)lead + total + 15u) / 16u);
+    const uint64_t w0 = (uint64_t)(blockIdx.x - jb.wg0) * (WRAP_WORDS * PRE_TB) + threadIdx.x;
+#pragma unroll
+    for (uint32_t t = 0; t < WRAP_WORDS; t++) {
+        const uint64_t w = w0 + (uint64_t)t * PRE_TB;
+        if (w >= words) break;
+        const int64_t p0 = (int64_t)(w * 16u) - (int64_t)lead;         // S2 position of the word's first byte (< 0: before the block)
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
+        const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
+        if (whole) {
+            const uint32_t pj = (uint32_t)p0 / WRAP_PIECE, r = (uint32_t)p0 % WRAP_PIECE;
+            if (r >= 2u && r + 16u <= WRAP_PIECE && (pj > 0u || r >= 4u)) {
+                const uint8_t *src = jb.in + ((uint32_t)p0 - 2u * pj - 4u);
+                const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
+                if (a >= r_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= r_hi) {
+                    *reinterpret_cast<uint4 *>(dst) = load16_unaligned(src);
+                    continue;
+                }
+            }
+        }
+        uint32_t b[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t p = p0 + j;
+            b[j] = 0;
+            if (p < 0 || (uint64_t)p >= total) continue;
+            b[j] = wrap_byte((uint32_t)p, jb.in);
+            if (!whole) dst[j] = (uint8_t)b[j];
+        }
+        if (whole) {
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            *reinterpret_cast<uint4 *>(dst) = v;
+        }
+    }
+}
+
 // jobs + mail words of one call in the context's arena
 struct PreCall {
     PreJob *d_jobs = nullptr;
@@ -376,7 +507,17 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
     return status ? JPK_OK : first_status(n, stp);
 }
 
-extern "C" int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
+namespace {
+// workgroups of one block in k_pre_lpx / k_enc_lpx: Lpx::Decode's loop `for (i = 0; i < len; i += part)` with part = len / 4: four parts,
+// more when len is not a multiple of 4 (a fifth, short one; up to seven for len < 8); one part for len < 4
+uint32_t lpx_parts(int32_t len)
+{
+    const uint32_t part = (uint32_t)len / 4u;
+    return part ? ((uint32_t)len + part - 1) / part : (len ? 1u : 0u);
+}
+
+// Lpx::Decode / Lpx::Encode of n blocks, one launch
+int lpx_batch(jpk_ctx *ctx, bool encode, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
 {
     JPK_TRY(pre_enter(ctx));
     if (n < 0 || (n > 0 && (!d_in || !len || !d_out))) return JPK_E_ARG;
@@ -386,22 +527,98 @@ extern "C" int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t 
     for (int b = 0; b < n; b++) {
         if (len[b] < 0 || (len[b] > 0 && (!d_in[b] || !d_out[b]))) return JPK_E_ARG;
         jobs[(size_t)b] = PreJob{d_in[b], d_out[b], len[b], len[b], (uint32_t)wgs, 0u};
-        // Lpx::Decode's loop `for (i = 0; i < len; i += part)` with part = len / 4: four parts, more when len is not a multiple of 4
-        // (a fifth, short one; up to seven for len < 8); one part for len < 4
-        const uint32_t part = (uint32_t)len[b] / 4u;
-        wgs += part ? ((uint32_t)len[b] + part - 1) / part : (len[b] ? 1u : 0u);
+        wgs += lpx_parts(len[b]);
         bytes += (uint32_t)len[b];
     }
     if (wgs > 0x7fffffffull) return JPK_E_ARG;
     if (wgs) {
         PreCall pc;
         JPK_TRY(pre_upload(ctx, jobs, 0, 0, &pc));
-        JPK_LAUNCH(ctx, PROF_PRE_LPX, bytes, k_pre_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n);
+        if (encode) JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_enc_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n, 0u);
+        else JPK_LAUNCH(ctx, PROF_PRE_LPX, bytes, k_pre_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n);
         std::vector<uint32_t> none;
         JPK_TRY(pre_finish(ctx, nullptr, none));
     }
-    if (status) for (int b = 0; b < n; b++) status[b] = JPK_OK;      // any byte string is a valid stream
+    if (status) for (int b = 0; b < n; b++) status[b] = JPK_OK;      // any byte string is a valid stream / a valid input
     return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_blocks_lpx_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
+{
+    return lpx_batch(ctx, false, n, d_in, len, d_out, status);
+}
+
+extern "C" int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
+{
+    return lpx_batch(ctx, true, n, d_in, len, d_out, status);
+}
+
+// The stage chain of jpk_cli_stages_encode for n blocks in HBM with two launches: k_enc_wrap R -> S2 into d_mid[b] (|S4| - 2 bytes; d_mid
+// == nullptr: in the context's arena), k_enc_lpx S2 -> S3 two bytes into d_out[b], with the second end token in front of it.
+// in_len[b] < 0: the block is skipped.  The caller has checked that every |S4| fits its buffer and an int32.
+int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out)
+{
+    std::vector<PreJob> wj((size_t)n), lj((size_t)n);
+    std::vector<size_t> moff((size_t)n, 0);
+    size_t mid_bytes = 0;
+    if (!d_mid)
+        for (int b = 0; b < n; b++)
+            if (in_len[b] >= 0) { moff[(size_t)b] = mid_bytes; mid_bytes += jpk_align((size_t)jpk_cli_stages_bound(in_len[b]) + 64); }
+    Arena plan(ctx, true);
+    plan.get<PreJob>(2 * (size_t)n);
+    plan.get<uint8_t>(mid_bytes);
+    JPK_TRY(jpk_arena_ensure(ctx, plan.need));
+    Arena real(ctx, false);
+    PreJob *d_jobs = real.get<PreJob>(2 * (size_t)n);
+    uint8_t *mids = real.get<uint8_t>(mid_bytes);
+    uint64_t wwg = 0, lwg = 0, bytes = 0;
+    for (int b = 0; b < n; b++) {
+        if (in_len[b] < 0) {
+            wj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)wwg, 0u};
+            lj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)lwg, 0u};
+            continue;
+        }
+        const int32_t s2 = (int32_t)(jpk_cli_stages_bound(in_len[b]) - 2);
+        uint8_t *mid = d_mid ? d_mid[b] : mids + moff[(size_t)b];
+        wj[(size_t)b] = PreJob{d_in[b], mid, in_len[b], s2, (uint32_t)wwg, 0u};
+        lj[(size_t)b] = PreJob{mid, d_out[b] + 2, s2, s2, (uint32_t)lwg, 0u};
+        const uint64_t words = (((uintptr_t)mid & 15u) + (uint64_t)s2 + 15u) / 16u;
+        wwg += (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
+        lwg += lpx_parts(s2);
+        bytes += (uint32_t)s2;
+    }
+    if (wwg > 0x7fffffffull || lwg > 0x7fffffffull) return JPK_E_ARG;
+    if (wwg) {
+        JPK_HIP(hipMemcpyAsync(d_jobs, wj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
+        JPK_HIP(hipMemcpyAsync(d_jobs + n, lj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
+        JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_enc_lpx, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
+    }
+    std::vector<uint32_t> none;
+    return pre_finish(ctx, nullptr, none);
+}
+
+extern "C" int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                                const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    std::vector<int32_t> lens((size_t)n), st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    for (int b = 0; b < n; b++) {
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
+        if (jpk_cli_stages_bound(in_len[b]) > 0x7fffffff) return JPK_E_ARG;
+    }
+    for (int b = 0; b < n; b++) {
+        const int64_t total = jpk_cli_stages_bound(in_len[b]);
+        stp[b] = total > out_cap[b] ? JPK_E_CAPACITY : JPK_OK;        // nothing of a block that does not fit is written
+        lens[(size_t)b] = stp[b] == JPK_OK ? in_len[b] : -1;
+        out_len[b] = stp[b] == JPK_OK ? (int32_t)total : 0;
+    }
+    JPK_TRY(jpk_cli_stages_device(ctx, n, d_in, lens.data(), nullptr, d_out));
+    return status ? JPK_OK : first_status(n, stp);
 }
 
 extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
