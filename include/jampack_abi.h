@@ -202,6 +202,21 @@ JPK_API int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, in
  * (jampack.cpp:157) for every such in_len (the arithmetic is in prestage.cpp). */
 JPK_API int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len);
 
+/* The dedupe of the stock encoder's first LZ77 stage (Jampack::Comp(), jampack.cpp:34-36: Lz->Compress with MatchFinder = 0, lz77.cpp:544-625
+ * "Deduplicate big chunks"): repeats of at least 256 bytes inside the block leave as tokens of Lz77::WriteToken (lz77.cpp:53-70), the rest as
+ * literals, the end token 04 80 in front of the last literals.  The token STREAM is not the reference's -- the matches come from a rule
+ * that runs in parallel (anchors at every 64th byte, a slot table that keeps the smallest position, runs of matching windows, greedy
+ * selection in position order; DESIGN 4.7 "Dedupe") -- but every decoder of the format reads it: jpk_lz77_decompress(S1') == R.
+ * |S1'| <= n + 2, a block without a qualifying repeat gives exactly 04 80 | R, the bytes depend on R alone, and the work is O(n) for every
+ * R.  *out_len = |S1'|; JPK_E_CAPACITY (nothing written, *out_len = 0) when out_cap is below it. */
+JPK_API int jpk_lz77_dedupe(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len);
+/* flags of the _ex forms of the stock-CLI writer.  JPK_CLI_DEDUPE: S1 = jpk_lz77_dedupe(R) instead of 04 80 | R; the rest of the chain is
+ * unchanged (stored filter pieces over S1, Lpx::Encode, stored second LZ77), so out_len depends on the data and jpk_cli_stages_bound /
+ * jpk_jam_cli_compress_bound stay bounds.  flags = 0 is the entry without _ex, byte for byte; any other bit is JPK_E_ARG. */
+#define JPK_CLI_DEDUPE 1
+JPK_API int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
+JPK_API int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
+
 /* ---- device-buffer entry points (all pointers except ctx/out_len are HBM addresses on ctx's device) ---- */
 /* ADDRESSES AND BOUNDS of every jpk_dev_* stage entry and probe (tests/test_gpu_stage_contracts.py, tests/test_gpu_primitives.py):
  *   - a byte buffer (const uint8_t *d_in, uint8_t *d_out, the in-place d_t / d_ranks) may start at ANY address and have any length: the
@@ -320,6 +335,16 @@ JPK_API int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t *co
  *   JPK_E_CAPACITY alone, out_len[b] = 0, and nothing of it is written. */
 JPK_API int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                              const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/*   jpk_lz77_dedupe of n blocks, the bytes and statuses of the host form (kernels k_dd_*): the anchor table, the heads per tile, their
+ *   runs, one selection chain per block, then -- behind ONE host read of the blocks' lengths -- the emit by destination.  A block whose
+ *   out_cap is below its |S1'| reports JPK_E_CAPACITY alone, out_len[b] = 0, and nothing of it is written.  Scratch in ctx's arena: about
+ *   1.2 bytes per input byte (the slot table <= 0.5, the heads 0.5, the tokens 0.125). */
+JPK_API int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                       const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/*   jpk_cli_stages_encode_ex of n blocks: with JPK_CLI_DEDUPE the dedupe launches run in front of k_enc_wrap, and k_enc_wrap / k_enc_lpx take
+ *   every block's length from its result (one host read for all blocks); out_len[b] = the host form's */
+JPK_API int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                                const int32_t *out_cap, int32_t *out_len, int32_t *status, uint32_t flags);
 /* Jampack::Decompress (jampack.cpp:262-336) of an archive written by an unmodified `jampack c` (any -m / -f setting; the frames of
  * jpk_jam_cli_block_read, back to back): the frame walk of jpk_dev_jam_decompress, with an entropy-decoded size of at most
  * 1.05 x BlockSize + 4096 per frame (the reference's stage buffers, jampack.cpp:156), then per pass jpk_dev_blocks_decompress into
@@ -355,6 +380,14 @@ JPK_API int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size);
 JPK_API int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
                                      int32_t in_flight);
 JPK_API int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight);
+/* The same with flags (JPK_CLI_DEDUPE): the frames of jpk_jam_cli_block_write_ex over the slices.  With the dedupe a pass runs the k_dd_*
+ * launches from the raw slices into slot B, reads the pass's S1' lengths on the host -- jpk_dev_blocks_compress wants host lengths: ONE
+ * synchronisation per pass, never one per frame -- and goes on with k_enc_wrap from B into A and k_enc_lpx from A into B at those lengths.
+ * The dedupe's scratch (about 1.2 bytes per input byte of the pass) comes from ctx's arena. */
+JPK_API int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                        int64_t *out_len, int32_t in_flight, uint32_t flags);
+JPK_API int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
+                                    uint32_t flags);
 
 /* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
 /* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the

@@ -79,6 +79,9 @@ _SIGS = {
     "jpk_cli_stages_bound": (C.c_int64, [C.c_int64]),
     "jpk_cli_stages_encode": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_jam_cli_block_write": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, _i32p]),
+    "jpk_lz77_dedupe": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p]),
+    "jpk_cli_stages_encode_ex": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p, C.c_uint32]),
+    "jpk_jam_cli_block_write_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, _i32p, C.c_uint32]),
     "jpk_dev_bwt_forward": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_dev_bwt_inverse": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_dev_bwt_inverse_chains120": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _i32p, C.POINTER(C.c_float)]),
@@ -116,6 +119,10 @@ _SIGS = {
     "jpk_jam_cli_compress_bound": (C.c_int64, [C.c_int64, C.c_int32]),
     "jpk_dev_jam_cli_compress": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]),
     "jpk_jam_cli_compress": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]),
+    "jpk_dev_blocks_lz77_dedupe": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
+    "jpk_dev_blocks_cli_stages_encode_ex": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p, C.c_uint32]),
+    "jpk_dev_jam_cli_compress_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
+    "jpk_jam_cli_compress_ex": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
     "jpk_dev_jam_cli_decompress": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_jam_cli_decompress": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_jam_cli_frames": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(C.c_int64), _i32p]),

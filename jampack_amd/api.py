@@ -285,6 +285,16 @@ class Lz77:
         _chk(lib().jpk_lz77_decompress(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "Lz77::Decompress")
         return out[: n.value]
 
+    def dedupe(self, buf, cap: int | None = None) -> np.ndarray:
+        """jpk_lz77_dedupe: repeats of >= 256 bytes inside the block as tokens of the first LZ77 stage, the rest as literals (at most
+        len + 2 bytes; 04 80 | block when nothing repeats).  Decompress() gives the block back."""
+        t = _np_u8(buf)
+        cap = len(t) + 2 if cap is None else cap
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n = C.c_int32(0)
+        _chk(lib().jpk_lz77_dedupe(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "jpk_lz77_dedupe")
+        return out[: n.value]
+
 
 class Lpx:
     """`class Lpx` (lpx.hpp:31-32); host code."""
@@ -337,24 +347,28 @@ def cli_stages_bound(n: int) -> int:
     return b
 
 
-def cli_stages_encode(block, cap: int | None = None) -> np.ndarray:
-    """jpk_cli_stages_encode: end token | Lpx::Encode(raw filter pieces of (end token | block)) -- what the stock decoder's four
-    pre-stage decoders turn back into `block`; host code."""
+CLI_DEDUPE = 1        # JPK_CLI_DEDUPE
+
+
+def cli_stages_encode(block, cap: int | None = None, dedupe: bool = False) -> np.ndarray:
+    """jpk_cli_stages_encode_ex: end token | Lpx::Encode(raw filter pieces of (end token | block)) -- what the stock decoder's four
+    pre-stage decoders turn back into `block`; host code.  dedupe: Lz77().dedupe(block) in place of (end token | block)."""
     t = _np_u8(block)
     cap = cli_stages_bound(len(t)) if cap is None else cap
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     n = C.c_int32(0)
-    _chk(lib().jpk_cli_stages_encode(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "jpk_cli_stages_encode")
+    _chk(lib().jpk_cli_stages_encode_ex(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n), CLI_DEDUPE if dedupe else 0), "jpk_cli_stages_encode_ex")
     return out[: n.value]
 
 
-def jam_cli_block_write(block, block_size: int, cap: int | None = None) -> np.ndarray:
-    """One frame an unmodified `jampack d` decodes: the header of jam_block_write + block_compress of the stage chain of `block`."""
+def jam_cli_block_write(block, block_size: int, cap: int | None = None, dedupe: bool = False) -> np.ndarray:
+    """One frame an unmodified `jampack d` decodes: the header of jam_block_write + block_compress of the stage chain of `block`
+    (dedupe: with long repeats taken out first, cli_stages_encode)."""
     t = _np_u8(block)
     cap = JAM_HEADER + ans_capacity(cli_stages_bound(len(t)) + TRAILER) if cap is None else cap
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     n = C.c_int32(0)
-    _chk(lib().jpk_jam_cli_block_write(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n)), "jam_cli_block_write")
+    _chk(lib().jpk_jam_cli_block_write_ex(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n), CLI_DEDUPE if dedupe else 0), "jam_cli_block_write")
     return out[: n.value]
 
 
@@ -365,13 +379,14 @@ def jam_cli_compress_bound(n: int, block_size: int = 8 << 20) -> int:
     return b
 
 
-def jam_cli_compress(data, block_size: int = 8 << 20) -> np.ndarray:
-    """The archive an unmodified `jampack d` decodes, made by one jpk_jam_cli_compress call: frames of block_size input bytes, the
-    pre-stages written in their stored forms + Lpx::Encode on the GPU, then the batch engine."""
+def jam_cli_compress(data, block_size: int = 8 << 20, dedupe: bool = False) -> np.ndarray:
+    """The archive an unmodified `jampack d` decodes, made by one jpk_jam_cli_compress_ex call: frames of block_size input bytes, the
+    pre-stages written in their stored forms + Lpx::Encode on the GPU, then the batch engine.  dedupe: repeats of >= 256 bytes inside
+    a block leave as LZ77 tokens in front of the BWT (the k_dd_* kernels)."""
     t = _np_u8(data)
     out = np.empty(max(jam_cli_compress_bound(len(t), block_size), 1), dtype=np.uint8)
     n = C.c_int64(0)
-    _chk(lib().jpk_jam_cli_compress(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0), "jam_cli_compress")
+    _chk(lib().jpk_jam_cli_compress_ex(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0, CLI_DEDUPE if dedupe else 0), "jam_cli_compress")
     return out[: n.value]
 
 
@@ -541,9 +556,16 @@ class Context:
         _chk(lib().jpk_dev_blocks_lpx_encode(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*lens), P(*[_dptr(x) for x in d_outs]), st), "jpk_dev_blocks_lpx_encode")
         return list(st)[:n]
 
-    def blocks_cli_stages_encode(self, d_ins, in_lens, d_outs, out_caps):
-        """jpk_dev_blocks_cli_stages_encode: the stored-form stage chain of independent blocks in two launches -> (out_len list, status list)"""
-        return self._batch(lib().jpk_dev_blocks_cli_stages_encode, "jpk_dev_blocks_cli_stages_encode", d_ins, in_lens, d_outs, out_caps)
+    def blocks_cli_stages_encode(self, d_ins, in_lens, d_outs, out_caps, dedupe: bool = False):
+        """jpk_dev_blocks_cli_stages_encode_ex: the stage chain of independent blocks (two launches; dedupe: the k_dd_* launches and one
+        host read of the lengths in front of them) -> (out_len list, status list)"""
+        fl = CLI_DEDUPE if dedupe else 0
+        fn = lib().jpk_dev_blocks_cli_stages_encode_ex
+        return self._batch(lambda *a: fn(*a, fl), "jpk_dev_blocks_cli_stages_encode_ex", d_ins, in_lens, d_outs, out_caps)
+
+    def blocks_lz77_dedupe(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_lz77_dedupe: Lz77().dedupe of independent blocks -> (out_len list, status list)"""
+        return self._batch(lib().jpk_dev_blocks_lz77_dedupe, "jpk_dev_blocks_lz77_dedupe", d_ins, in_lens, d_outs, out_caps)
 
     def blocks_filters_decode(self, d_ins, in_lens, d_outs, out_caps):
         """jpk_dev_blocks_filters_decode: Filters::Decode of independent blocks in one launch -> (out_len list, status list)"""
@@ -589,10 +611,11 @@ class Context:
         _chk(lib().jpk_dev_jam_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_compress")
         return n.value
 
-    def jam_cli_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0) -> int:
-        """jpk_dev_jam_cli_compress: the archive of d_in[0..in_len) an unmodified `jampack d` decodes, into d_out; returns its length"""
+    def jam_cli_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0, dedupe: bool = False) -> int:
+        """jpk_dev_jam_cli_compress_ex: the archive of d_in[0..in_len) an unmodified `jampack d` decodes, into d_out; returns its length"""
         n = C.c_int64(0)
-        _chk(lib().jpk_dev_jam_cli_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_cli_compress")
+        _chk(lib().jpk_dev_jam_cli_compress_ex(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight,
+                                               CLI_DEDUPE if dedupe else 0), "jpk_dev_jam_cli_compress_ex")
         return n.value
 
     def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):

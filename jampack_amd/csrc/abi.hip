@@ -110,7 +110,8 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
     "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
-    "k_enc_wrap", "k_enc_lpx", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
+    "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit",
+    "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {
@@ -1845,16 +1846,16 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
 
 // The counterpart: crc (jampack.cpp:31), the stage chain of jpk_cli_stages_encode on the host in place of Jampack::Comp()'s four
 // pre-stage encoders (jampack.cpp:36-39), ForwardBwt + Ans::Encode on the GPU, the header of CompWriteBlock (jampack.cpp:122-135).
-extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
+extern "C" int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
 {
-    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
     if (!jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
     if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
     const int32_t cap = (int32_t)jpk_cli_stages_bound(in_len);                       // < 2^31 for in_len <= JPK_MAX_BLOCKSIZE (prestage.cpp)
     static thread_local std::vector<uint8_t> s4;
     try { if (s4.size() < (size_t)cap) s4.resize((size_t)cap); } catch (...) { return JPK_E_ALLOC; }
     int32_t m = 0, n = 0;
-    JPK_TRY(jpk_cli_stages_encode(in, in_len, s4.data(), cap, &m));
+    JPK_TRY(jpk_cli_stages_encode_ex(in, in_len, s4.data(), cap, &m, flags));
     JPK_TRY(jpk_block_compress(s4.data(), m, out + JPK_JAM_HEADER_BYTES, out_cap - JPK_JAM_HEADER_BYTES, &n));
     const uint32_t crc = jpk_checksum_host(in, in_len);
     memcpy(out, "JAM", 3);
@@ -1863,6 +1864,11 @@ extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_
     memcpy(out + 11, &block_size, 4);
     *out_len = n + JPK_JAM_HEADER_BYTES;
     return JPK_OK;
+}
+
+extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    return jpk_jam_cli_block_write_ex(in, in_len, block_size, out, out_cap, out_len, 0u);
 }
 
 // ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
@@ -1875,7 +1881,8 @@ extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_
 // and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
 // The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
 // the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
-// of the raw slices.
+// of the raw slices.  With JPK_CLI_DEDUPE the k_dd_* launches come first (raw slice -> S1' in slot B), the pass's S1' lengths are read
+// on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.
 namespace {
 constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
 
@@ -1968,7 +1975,7 @@ int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (
 // one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
 // of the stock CLI
 int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
-                      int32_t in_flight, bool cli)
+                      int32_t in_flight, bool cli, uint32_t flags)
 {
     const int n = (int)((len + block_size - 1) / block_size);
     std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
@@ -1999,7 +2006,7 @@ int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t bl
     }
     // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
     JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
-    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data()));
+    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
     JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
     for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
     std::vector<JamPackFrame> fr((size_t)n);
@@ -2040,17 +2047,17 @@ int64_t jam_compress_bound(int64_t in_len, int32_t block_size, bool cli)
 }
 
 int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                     int32_t in_flight, bool cli)
+                     int32_t in_flight, bool cli, uint32_t flags = 0u)
 {
     JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out))) return JPK_E_ARG;
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
     if (!jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
     *out_len = 0;
     const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
     int64_t pos = 0;
     for (int64_t o = 0; o < in_len; o += step) {
         int64_t n = 0;
-        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli));
+        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli, flags));
         pos += n;
     }
     *out_len = pos;
@@ -2071,6 +2078,12 @@ extern "C" int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64
                                         int64_t *out_len, int32_t in_flight)
 {
     return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true);
+}
+
+extern "C" int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                           int64_t *out_len, int32_t in_flight, uint32_t flags)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true, flags);
 }
 
 extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
@@ -2146,9 +2159,10 @@ extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames
 }
 
 namespace {
-int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli)
+int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli,
+                      uint32_t flags = 0u)
 {
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out))) return JPK_E_ARG;
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
     if (!jam_block_size_ok(block_size)) return JPK_E_ARG;
     *out_len = 0;
     jpk_ctx *ctx;
@@ -2163,7 +2177,7 @@ int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uin
         JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
         JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
         int64_t n = 0;
-        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli));
+        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli, flags));
         if (n > out_cap - pos) return JPK_E_CAPACITY;
         JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         JPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -2182,6 +2196,12 @@ extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block
 extern "C" int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
 {
     return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true);
+}
+
+extern "C" int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
+                                       uint32_t flags)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true, flags);
 }
 
 extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)

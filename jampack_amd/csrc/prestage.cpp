@@ -3,8 +3,9 @@
 // frames written by an unmodified `jampack c` decode end to end: rANS decode + inverse BWT on the GPU, these on the
 // host where SURVEY.md section 8f (row 4) puts them -- byte-serial state machines with no data parallelism.
 // The encoder side is the part of the reference's encoders that a VALID stream needs and no more (writing): the stored forms
-// of LZ77 and Filters, and Lpx::Encode, which has no stored form and is deterministic integer code.  The match finders, the dedupe and the
-// filter selection with their float heuristics stay with the reference.
+// of LZ77 and Filters, and Lpx::Encode, which has no stored form and is deterministic integer code; and, as an option of the writer, a dedupe of
+// long repeats in the token format of the first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp's, not the reference's hash walk).  The
+// match finders and the filter selection with their float heuristics stay with the reference.
 //
 // Unlike the reference (which trusts its input outside NDEBUG builds, lz77.cpp:697-701) every read and write is
 // bounds checked and a bad stream gives JPK_E_CORRUPT / JPK_E_CAPACITY.
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/jampack_abi.h"
+#include "dedupe.hpp"
 
 namespace {
 
@@ -294,24 +296,23 @@ extern "C" int64_t jpk_cli_stages_bound(int64_t n)
     return n + 4 + 2 * ((n + 2 + CLI_FBS - 1) / CLI_FBS);
 }
 
-extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)
+// S4 of S1 = head | body: the filter pieces, Lpx::Encode, the second end token
+static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
-    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
-    const int64_t total = jpk_cli_stages_bound(n);
+    const int64_t s1 = nhead + nbody, total = s1 + 2 + 2 * ((s1 + CLI_FBS - 1) / CLI_FBS), s2 = total - 2;
     if (total > 0x7fffffff) return JPK_E_ARG;
     if (total > out_cap) return JPK_E_CAPACITY;
-    const int64_t s1 = (int64_t)n + 2, s2 = total - 2;
     std::vector<uint8_t> buf;
     try { buf.resize((size_t)s2); } catch (...) { return JPK_E_ALLOC; }
     int64_t op = 0;
-    for (int64_t i = 0; i < s1;) {                                     // byte i of S1: the token, then in[i - 2]
+    for (int64_t i = 0; i < s1;) {                                     // byte i of S1: head[i], then body[i - nhead]
         const int64_t len = (i + CLI_FBS < s1) ? CLI_FBS : s1 - i;
         if (op + 2 + len > s2) return JPK_E_CAPACITY;                  // cannot happen: s2 counts exactly these bytes
         buf[(size_t)op] = 0; buf[(size_t)op + 1] = 0;
         op += 2;
         int64_t k = 0;
-        for (; i + k < 2 && k < len; k++) buf[(size_t)(op + k)] = CLI_TOKEN[i + k];
-        if (len > k) memcpy(buf.data() + op + k, in + (i + k - 2), (size_t)(len - k));
+        for (; i + k < nhead && k < len; k++) buf[(size_t)(op + k)] = head[i + k];
+        if (len > k) memcpy(buf.data() + op + k, body + (i + k - nhead), (size_t)(len - k));
         op += len;
         i += len;
     }
@@ -320,6 +321,75 @@ extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out,
     if (rc != JPK_OK) return rc;
     *out_len = (int32_t)total;
     return JPK_OK;
+}
+
+// ---- the dedupe: long repeats inside the block as tokens of the first LZ77 stage ("Dedupe"; the rule is dedupe.hpp) ----------
+//   1 anchors     every aligned window q = 0, 64, ... goes into its slot of the table; a slot keeps the smallest q
+//   2 candidates  every position is looked up by its fingerprint (rolled here, doubled in LDS on the device); heads are kept per tile of
+//                 1024 positions, the first dd::TILE_HEADS of a tile
+//   3 runs        dd::extend from every head
+//   4 selection   dd::Select over the runs in position order
+//   5 emit        token headers and literal runs, then 04 80 and the rest
+// Work: steps 1, 2 and 5 touch every byte a constant number of times; a run of step 3 looks at no more than TILE / W + GAP windows and there
+// are at most n / 32 heads (DESIGN has the arithmetic).
+extern "C" int jpk_lz77_dedupe(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    *out_len = 0;
+    const uint32_t N = (uint32_t)n;
+    const int bits = dd::table_bits(N);
+    std::vector<uint32_t> table;
+    std::vector<dd::Tok> toks;
+    try { table.assign((size_t)1 << bits, dd::EMPTY); toks.resize(dd::max_toks(N)); } catch (...) { return JPK_E_ALLOC; }
+    for (uint32_t q = 0; (uint64_t)q + dd::W <= N; q += dd::W) {
+        uint32_t &t = table[dd::slot(dd::fp_at(in, q), bits)];
+        if (q < t) t = q;
+    }
+    dd::Select sel(toks.data(), true);
+    if (N >= 2 * dd::W) {
+        uint32_t top = 1;                                              // MUL^63: what the byte that leaves the window carries
+        for (uint32_t i = 0; i + 1 < dd::W; i++) top *= dd::MUL;
+        uint32_t ring[256] = {0};                                      // cand() of the last positions (0 in front of position 64)
+        uint32_t fp = dd::fp_at(in, dd::W), tile = 0, kept = 0;
+        for (uint32_t x = dd::W;; x++) {                               // x runs one window ahead of the position p it decides
+            const uint32_t dx = dd::cand_fp(in, N, table.data(), bits, x, fp);
+            ring[x & 255u] = dx;
+            const uint32_t p = x - dd::W, d = ring[p & 255u];
+            if (p >= dd::W && dd::is_head(p, ring[(p - dd::W) & 255u], d, dx)) {
+                if (p / dd::TILE != tile) { tile = p / dd::TILE; kept = 0; }
+                if (kept < dd::TILE_HEADS) { kept++; sel.add(dd::extend(in, N, table.data(), bits, p, d)); }
+            }
+            if ((uint64_t)x + dd::W >= N) break;                       // x was the last whole window
+            fp = (fp - (in[x] + 1u) * top) * dd::MUL + in[x + dd::W] + 1u;
+        }
+    }
+    const uint32_t total = sel.finish(N);
+    if ((int64_t)total > out_cap) return JPK_E_CAPACITY;
+    for (uint32_t i = 0; i < sel.ntok; i++) {
+        const dd::Tok &t = toks[i];
+        memcpy(out + t.out_off, t.hdr, t.hlen);
+        if (t.lit) memcpy(out + t.out_off + t.hlen, in + t.lit_src, t.lit);
+    }
+    *out_len = (int32_t)total;
+    return JPK_OK;
+}
+
+extern "C" int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
+{
+    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (jpk_cli_stages_bound(n) > 0x7fffffff) return JPK_E_ARG;
+    if (!(flags & JPK_CLI_DEDUPE)) return cli_stages_from(CLI_TOKEN, 2, in, n, out, out_cap, out_len);
+    std::vector<uint8_t> s1;
+    try { s1.resize((size_t)n + 2); } catch (...) { return JPK_E_ALLOC; }
+    int32_t m = 0;
+    const int rc = jpk_lz77_dedupe(in, n, s1.data(), n + 2, &m);       // |S1'| <= n + 2: every token pays for itself
+    if (rc != JPK_OK) return rc;
+    return cli_stages_from(nullptr, 0, s1.data(), m, out, out_cap, out_len);
+}
+
+extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    return jpk_cli_stages_encode_ex(in, n, out, out_cap, out_len, 0u);
 }
 
 // Checksum::IntegrityCheck on the host (checksum.cpp:12-36), for buffers that are already there

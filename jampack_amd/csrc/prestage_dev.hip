@@ -7,12 +7,20 @@
 //   k_enc_wrap     raw block -> S2: the LZ77 end token and the 00 00 header of every 64 KiB filter piece around the unchanged bytes,
 //                  organised by destination like k_jam_pack: a thread owns aligned 16-byte words of the output
 //   k_enc_lpx      Lpx::Encode      (lpx.cpp:56-99, 148-158) one workgroup per part, the mirror image of k_pre_lpx
+// and the dedupe of the writer's first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp, shared with the host form):
+//   k_dd_anchor    every aligned 64-byte window into its slot of the block's table, atomicMin on the position
+//   k_dd_cand      one workgroup per tile of 1024 positions: fingerprints of all positions by six doubling steps in LDS, the candidate offset
+//                  of every position (halo of one window on either side), the tile's heads compacted in position order
+//   k_dd_extend    one thread per head: its run
+//   k_dd_select    one workgroup per block: the greedy chain over the runs, token records with their output offsets
+//   k_dd_emit      token headers and literal runs by destination, as k_enc_wrap
 // Each is bit-identical to its host form in prestage.cpp (statuses included) and keeps that file's bounds checks: every read is checked
 // against in_len and every write against out_cap before it is made, in 64-bit arithmetic.  No workgroup waits for another one, every
 // loop is bounded by the stream length or the output capacity, and a bad stream sets the block's mail word and ends the workgroup.
 #include <vector>
 
 #include "common.hpp"
+#include "dedupe.hpp"
 
 namespace {
 
@@ -376,12 +384,13 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_filters(const PreJob *__restrict
 constexpr uint32_t WRAP_PIECE = FBS + 2;                              // one filter piece in S2: header + 64 KiB of S1
 constexpr uint32_t WRAP_WORDS = 4;                                    // 16-byte words per thread: a workgroup writes 16 KiB
 
-// byte p of S2 (prestage.cpp: S1 = 04 80 | R, every 64 KiB piece of S1 behind 00 00)
-__device__ __forceinline__ uint32_t wrap_byte(uint32_t p, const uint8_t *__restrict__ in)
+// byte p of S2 (prestage.cpp: S1 = 04 80 | R, every 64 KiB piece of S1 behind 00 00); TOK = false: `in` is S1 itself (the dedupe wrote it)
+template <bool TOK> __device__ __forceinline__ uint32_t wrap_byte(uint32_t p, const uint8_t *__restrict__ in)
 {
     const uint32_t pj = p / WRAP_PIECE, r = p % WRAP_PIECE;
     if (r < 2u) return 0u;
     const uint32_t s1 = pj * FBS + r - 2u;
+    if (!TOK) return in[s1];
     return s1 < 2u ? (s1 == 0u ? 0x04u : 0x80u) : in[s1 - 2u];
 }
 
@@ -390,7 +399,7 @@ __device__ __forceinline__ uint32_t wrap_byte(uint32_t p, const uint8_t *__restr
 // word whose bytes all come from R -- S2[p] = R[p - 2 j - 4] inside piece j, behind its header and behind the token -- moves through two
 // aligned 16-byte loads when both lie inside R; every other word (a header, the token, the ends of R or of S2) is assembled byte by byte,
 // whole words stored once, the partial words at the two ends with byte stores.  Nothing outside [out, out + |S2|) is written.
-__global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const PreJob *__restrict__ jobs, uint32_t n)
+template <bool TOK> __global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const PreJob *__restrict__ jobs, uint32_t n)
 {
     const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
     const uint32_t total = (uint32_t)jb.out_cap;
@@ -407,8 +416,8 @@ __global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const PreJob *__restrict__ 
         const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
         if (whole) {
             const uint32_t pj = (uint32_t)p0 / WRAP_PIECE, r = (uint32_t)p0 % WRAP_PIECE;
-            if (r >= 2u && r + 16u <= WRAP_PIECE && (pj > 0u || r >= 4u)) {
-                const uint8_t *src = jb.in + ((uint32_t)p0 - 2u * pj - 4u);
+            if (r >= 2u && r + 16u <= WRAP_PIECE && (!TOK || pj > 0u || r >= 4u)) {
+                const uint8_t *src = jb.in + ((uint32_t)p0 - 2u * pj - (TOK ? 4u : 2u));
                 const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
                 if (a >= r_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= r_hi) {
                     *reinterpret_cast<uint4 *>(dst) = load16_unaligned(src);
@@ -422,7 +431,192 @@ __global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const PreJob *__restrict__ 
             const int64_t p = p0 + j;
             b[j] = 0;
             if (p < 0 || (uint64_t)p >= total) continue;
-            b[j] = wrap_byte((uint32_t)p, jb.in);
+            b[j] = wrap_byte<TOK>((uint32_t)p, jb.in);
+            if (!whole) dst[j] = (uint8_t)b[j];
+        }
+        if (whole) {
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            *reinterpret_cast<uint4 *>(dst) = v;
+        }
+    }
+}
+
+// ---- the dedupe ------------------------------------------------------------------------------------------------------------------
+// One block of a batch.  Every k_dd_* grid is (workgroups of the largest block, blocks): a workgroup past its block's end leaves at once.
+struct DdJob {
+    const uint8_t *in; uint8_t *out; uint32_t *table; uint4 *heads; uint32_t *cnt; dd::Tok *toks;
+    uint32_t n; int32_t bits; uint32_t total; uint32_t ntok;        // total, ntok: set for k_dd_emit (total == 0: the block is skipped)
+};
+constexpr uint32_t DD_HALO = dd::W;                                   // candidate offsets of one window on either side of the tile
+constexpr uint32_t DD_NP = dd::TILE + 2 * DD_HALO;                    // positions whose offset a tile computes
+constexpr uint32_t DD_NH = DD_NP + dd::W;                             // fingerprint cells (the last W - 1 feed the doubling only)
+
+__global__ __launch_bounds__(PRE_TB) void k_dd_anchor(const DdJob *__restrict__ jobs)
+{
+    const DdJob jb = jobs[blockIdx.y];
+    const uint64_t q = ((uint64_t)blockIdx.x * PRE_TB + threadIdx.x) * dd::W;
+    if (q + dd::W > jb.n) return;
+    atomicMin(&jb.table[dd::slot(dd::fp_at(jb.in, (uint32_t)q), jb.bits)], (uint32_t)q);
+}
+
+// heads[tile * TILE_HEADS + k] = (p, d, 0, 0) for the tile's first TILE_HEADS heads in position order, cnt[tile] = their number
+__global__ __launch_bounds__(PRE_TB) void k_dd_cand(const DdJob *__restrict__ jobs)
+{
+    __shared__ uint32_t ha[DD_NH], hb[DD_NH];
+    __shared__ uint32_t wsum[PRE_TB / 64];
+    const DdJob jb = jobs[blockIdx.y];
+    const uint32_t tid = threadIdx.x, n = jb.n;
+    const uint64_t t0 = (uint64_t)blockIdx.x * dd::TILE;
+    if (t0 >= n) return;
+    const int64_t g0 = (int64_t)t0 - DD_HALO;                          // cell i stands for position g0 + i
+    for (uint32_t i = tid; i < DD_NH; i += PRE_TB) {
+        const int64_t g = g0 + i;
+        ha[i] = (g >= 0 && g < (int64_t)n) ? (uint32_t)jb.in[g] + 1u : 0u;
+    }
+    __syncthreads();
+    uint32_t *src = ha, *dst = hb;
+    uint32_t mul = dd::MUL;
+#pragma unroll
+    for (uint32_t k = 1; k < dd::W; k <<= 1) {                         // h2k(p) = hk(p) MUL^k + hk(p + k)
+        for (uint32_t i = tid; i + k < DD_NH; i += PRE_TB) dst[i] = src[i] * mul + src[i + k];
+        __syncthreads();
+        uint32_t *t = src; src = dst; dst = t;
+        mul *= mul;
+    }
+    // src[i] = fp(g0 + i) for i < DD_NP (every cell it was summed from exists); dst receives the candidate offsets
+    for (uint32_t i = tid; i < DD_NP; i += PRE_TB) {
+        const int64_t p = g0 + i;
+        dst[i] = (p >= (int64_t)dd::W && p + (int64_t)dd::W <= (int64_t)n) ? dd::cand_fp(jb.in, n, jb.table, jb.bits, (uint32_t)p, src[i]) : 0u;
+    }
+    __syncthreads();
+    // thread t owns positions t0 + 4 t .. + 3: flags, an exclusive scan over the workgroup, the first TILE_HEADS are written
+    uint32_t flag[4], mine = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t i = DD_HALO + 4u * tid + k;
+        flag[k] = dd::is_head((uint32_t)(t0 + 4u * tid + k), dst[i - dd::W], dst[i], dst[i + dd::W]) ? 1u : 0u;
+        mine += flag[k];
+    }
+    uint32_t incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = (uint32_t)__shfl_up((int)incl, o, 64);
+        if ((tid & 63u) >= (uint32_t)o) incl += v;
+    }
+    if ((tid & 63u) == 63u) wsum[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t base = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < PRE_TB / 64; w++) { if (w < (tid >> 6)) base += wsum[w]; all += wsum[w]; }
+    uint32_t at = base + incl - mine;
+    uint4 *heads = jb.heads + (size_t)blockIdx.x * dd::TILE_HEADS;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        if (flag[k]) {
+            if (at < dd::TILE_HEADS) heads[at] = make_uint4((uint32_t)(t0 + 4u * tid + k), dst[DD_HALO + 4u * tid + k], 0u, 0u);
+            at++;
+        }
+    }
+    if (tid == 0) jb.cnt[blockIdx.x] = all < dd::TILE_HEADS ? all : dd::TILE_HEADS;
+}
+
+// heads[i] = (p, d, 0, 0) -> (s, d, e, 0)
+__global__ __launch_bounds__(PRE_TB) void k_dd_extend(const DdJob *__restrict__ jobs)
+{
+    const DdJob jb = jobs[blockIdx.y];
+    const uint64_t i = (uint64_t)blockIdx.x * PRE_TB + threadIdx.x;
+    const uint64_t tile = i / dd::TILE_HEADS;
+    if (tile >= dd::tiles(jb.n) || (uint32_t)(i % dd::TILE_HEADS) >= jb.cnt[tile]) return;
+    const uint4 h = jb.heads[i];
+    const dd::Run r = dd::extend(jb.in, jb.n, jb.table, jb.bits, h.x, h.y);
+    jb.heads[i] = make_uint4(r.s, r.d, r.e, 0u);
+}
+
+// One workgroup per block: all threads bring the runs of DD_SEL_TILES tiles into LDS, thread 0 walks them in order (dd::Select).
+// mail[2 b] = |S1'|, mail[2 b + 1] = token records (the end token included).
+constexpr uint32_t DD_SEL_TILES = PRE_TB / dd::TILE_HEADS;
+__global__ __launch_bounds__(PRE_TB) void k_dd_select(const DdJob *__restrict__ jobs, uint32_t *__restrict__ mail)
+{
+    __shared__ uint4 rec[PRE_TB];
+    __shared__ uint32_t scnt[DD_SEL_TILES];
+    const DdJob jb = jobs[blockIdx.x];
+    const uint32_t tid = threadIdx.x, ntiles = dd::tiles(jb.n);
+    dd::Select sel(jb.toks, true);
+    for (uint32_t tb = 0; tb < ntiles; tb += DD_SEL_TILES) {
+        const uint32_t tile = tb + tid / dd::TILE_HEADS;
+        if (tid < DD_SEL_TILES) scnt[tid] = tb + tid < ntiles ? jb.cnt[tb + tid] : 0u;
+        if (tile < ntiles) rec[tid] = jb.heads[(size_t)tb * dd::TILE_HEADS + tid];
+        __syncthreads();
+        if (tid == 0) {
+            for (uint32_t t = 0; t < DD_SEL_TILES; t++)
+                for (uint32_t k = 0; k < scnt[t]; k++) {
+                    const uint4 v = rec[t * dd::TILE_HEADS + k];
+                    dd::Run r;
+                    r.s = v.x; r.d = v.y; r.e = v.z;
+                    sel.add(r);
+                }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        mail[2 * (size_t)blockIdx.x] = sel.finish(jb.n);
+        mail[2 * (size_t)blockIdx.x + 1] = sel.ntok;
+    }
+}
+
+// byte p of S1' behind token record i (the last one with out_off <= p)
+__device__ __forceinline__ uint32_t dd_byte(const DdJob &jb, const dd::Tok &t, uint32_t p)
+{
+    const uint32_t r = p - t.out_off;
+    return r < t.hlen ? t.hdr[r] : jb.in[t.lit_src + (r - t.hlen)];
+}
+
+// A workgroup owns WRAP_WORDS * PRE_TB aligned 16-byte words of the block's output, as k_enc_wrap.  A whole word inside one literal run
+// moves through two aligned loads when both lie inside the block; every other word is assembled byte by byte.  Nothing outside
+// [out, out + total) is written.
+__global__ __launch_bounds__(PRE_TB) void k_dd_emit(const DdJob *__restrict__ jobs)
+{
+    const DdJob jb = jobs[blockIdx.y];
+    const uint32_t total = jb.total;
+    if (total == 0u) return;
+    const uintptr_t base = (uintptr_t)jb.out & ~(uintptr_t)15, r_lo = (uintptr_t)jb.in, r_hi = r_lo + jb.n;
+    const uint32_t lead = (uint32_t)((uintptr_t)jb.out - base);
+    const uint64_t words = ((uint64_t)lead + total + 15u) / 16u;
+    const uint64_t w0 = (uint64_t)blockIdx.x * (WRAP_WORDS * PRE_TB) + threadIdx.x;
+#pragma unroll 1
+    for (uint32_t t = 0; t < WRAP_WORDS; t++) {
+        const uint64_t w = w0 + (uint64_t)t * PRE_TB;
+        if (w >= words) break;
+        const int64_t p0 = (int64_t)(w * 16u) - (int64_t)lead;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
+        const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
+        const uint32_t first = p0 < 0 ? 0u : (uint32_t)p0;
+        uint32_t lo = 0, hi = jb.ntok;                                 // the last record with out_off <= first (record 0 starts at 0)
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (jb.toks[mid].out_off <= first) lo = mid; else hi = mid; }
+        dd::Tok tk = jb.toks[lo];
+        if (whole) {
+            const uint32_t r = first - tk.out_off;
+            if (r >= tk.hlen && (uint64_t)(r - tk.hlen) + 16u <= tk.lit) {
+                const uint8_t *src = jb.in + tk.lit_src + (r - tk.hlen);
+                const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
+                if (a >= r_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= r_hi) {
+                    *reinterpret_cast<uint4 *>(dst) = load16_unaligned(src);
+                    continue;
+                }
+            }
+        }
+        uint32_t b[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t p = p0 + j;
+            b[j] = 0;
+            if (p < 0 || (uint64_t)p >= total) continue;
+            while (lo + 1 < jb.ntok && (uint64_t)p >= (uint64_t)tk.out_off + tk.hlen + tk.lit) tk = jb.toks[++lo];
+            b[j] = dd_byte(jb, tk, (uint32_t)p);
             if (!whole) dst[j] = (uint8_t)b[j];
         }
         if (whole) {
@@ -478,6 +672,95 @@ int first_status(int32_t n, const int32_t *st)
     return JPK_OK;
 }
 
+// The dedupe of n blocks in two halves around its one host read.  dd_find: table, heads, runs and selection of every block (in_len[b] < 0:
+// skipped); s1_len[b] = |S1'|.  dd_emit: writes S1' of every block with outs[b] != nullptr.  The scratch lives in ctx's arena from dd_find
+// until dd_emit has been enqueued; both synchronise the stream.
+constexpr int DD_GRID_Y = 32768;
+struct DdCall {
+    std::vector<DdJob> jobs;
+    DdJob *d_jobs = nullptr;
+    uint32_t max_n = 0;
+    uint64_t bytes = 0;
+};
+
+int dd_find(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, DdCall *dc, int32_t *s1_len)
+{
+    dc->jobs.assign((size_t)n, DdJob{});
+    size_t table_words = 0, head_recs = 0, cnt_words = 0, tok_recs = 0;
+    for (int b = 0; b < n; b++) {
+        const uint32_t len = in_len[b] < 0 ? 0u : (uint32_t)in_len[b];
+        table_words += (size_t)1 << dd::table_bits(len);
+        head_recs += (size_t)dd::tiles(len) * dd::TILE_HEADS;
+        cnt_words += jpk_align((size_t)dd::tiles(len), 4);
+        tok_recs += dd::max_toks(len);
+        if (len > dc->max_n) dc->max_n = len;
+        dc->bytes += len;
+    }
+    Arena plan(ctx, true);
+    plan.get<DdJob>((size_t)n);
+    plan.get<uint32_t>(2 * (size_t)n);
+    plan.get<uint32_t>(table_words);
+    plan.get<uint4>(head_recs);
+    plan.get<uint32_t>(cnt_words);
+    plan.get<dd::Tok>(tok_recs);
+    JPK_TRY(jpk_arena_ensure(ctx, plan.need));
+    Arena real(ctx, false);
+    dc->d_jobs = real.get<DdJob>((size_t)n);
+    uint32_t *d_mail = real.get<uint32_t>(2 * (size_t)n);
+    uint32_t *tables = real.get<uint32_t>(table_words);
+    uint4 *heads = real.get<uint4>(head_recs);
+    uint32_t *cnts = real.get<uint32_t>(cnt_words);
+    dd::Tok *toks = real.get<dd::Tok>(tok_recs);
+    size_t to = 0, ho = 0, co = 0, ko = 0;
+    for (int b = 0; b < n; b++) {
+        const uint32_t len = in_len[b] < 0 ? 0u : (uint32_t)in_len[b];
+        DdJob &j = dc->jobs[(size_t)b];
+        j.in = len ? d_in[b] : nullptr; j.out = nullptr;
+        j.table = tables + to; j.heads = heads + ho; j.cnt = cnts + co; j.toks = toks + ko;
+        j.n = len; j.bits = dd::table_bits(len); j.total = 0; j.ntok = 0;
+        to += (size_t)1 << j.bits; ho += (size_t)dd::tiles(len) * dd::TILE_HEADS; co += jpk_align((size_t)dd::tiles(len), 4); ko += dd::max_toks(len);
+    }
+    JPK_HIP(hipMemcpyAsync(dc->d_jobs, dc->jobs.data(), (size_t)n * sizeof(DdJob), hipMemcpyHostToDevice, ctx->stream));
+    JPK_HIP(hipMemsetAsync(tables, 0xFF, table_words * 4, ctx->stream));
+    const unsigned ntiles = dd::tiles(dc->max_n);
+    for (int b0 = 0; b0 < n; b0 += DD_GRID_Y) {
+        const unsigned nb = (unsigned)std::min(DD_GRID_Y, n - b0);
+        const DdJob *jobs = dc->d_jobs + b0;
+        if (ntiles) {
+            JPK_LAUNCH(ctx, PROF_DD_ANCHOR, dc->bytes, k_dd_anchor, dim3(jpk_grid(dd::anchors(dc->max_n) + 1, PRE_TB), nb), dim3(PRE_TB), jobs);
+            JPK_LAUNCH(ctx, PROF_DD_CAND, dc->bytes, k_dd_cand, dim3(ntiles, nb), dim3(PRE_TB), jobs);
+            JPK_LAUNCH(ctx, PROF_DD_EXTEND, dc->bytes, k_dd_extend, dim3(jpk_grid((size_t)ntiles * dd::TILE_HEADS, PRE_TB), nb), dim3(PRE_TB), jobs);
+        }
+        JPK_LAUNCH(ctx, PROF_DD_SELECT, dc->bytes, k_dd_select, dim3(nb), dim3(PRE_TB), jobs, d_mail + 2 * (size_t)b0);
+    }
+    std::vector<uint32_t> mail(2 * (size_t)n);
+    JPK_TRY(pre_finish(ctx, d_mail, mail));
+    for (int b = 0; b < n; b++) {
+        s1_len[b] = (int32_t)mail[2 * (size_t)b];
+        dc->jobs[(size_t)b].ntok = mail[2 * (size_t)b + 1];
+    }
+    return JPK_OK;
+}
+
+int dd_emit(jpk_ctx *ctx, int n, DdCall *dc, uint8_t *const *outs, const int32_t *s1_len)
+{
+    uint64_t max_words = 0;
+    for (int b = 0; b < n; b++) {
+        DdJob &j = dc->jobs[(size_t)b];
+        j.out = outs[b];
+        j.total = outs[b] ? (uint32_t)s1_len[b] : 0u;
+        if (j.total) max_words = std::max<uint64_t>(max_words, (((uintptr_t)j.out & 15u) + (uint64_t)j.total + 15u) / 16u);
+    }
+    if (max_words) {
+        JPK_HIP(hipMemcpyAsync(dc->d_jobs, dc->jobs.data(), (size_t)n * sizeof(DdJob), hipMemcpyHostToDevice, ctx->stream));
+        for (int b0 = 0; b0 < n; b0 += DD_GRID_Y)
+            JPK_LAUNCH(ctx, PROF_DD_EMIT, dc->bytes, k_dd_emit, dim3(jpk_grid(max_words, WRAP_WORDS * PRE_TB), (unsigned)std::min(DD_GRID_Y, n - b0)), dim3(PRE_TB),
+                       dc->d_jobs + b0);
+    }
+    std::vector<uint32_t> none;
+    return pre_finish(ctx, nullptr, none);
+}
+
 }  // namespace
 
 extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
@@ -504,6 +787,28 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
         stp[b] = (int32_t)mail[2 * (size_t)b];
         out_len[b] = stp[b] == JPK_OK ? (int32_t)mail[2 * (size_t)b + 1] : 0;
     }
+    return status ? JPK_OK : first_status(n, stp);
+}
+
+extern "C" int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                          const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    for (int b = 0; b < n; b++)
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
+    JPK_TRY(pre_enter(ctx));
+    if (n == 0) return JPK_OK;
+    DdCall dc;
+    std::vector<int32_t> s1((size_t)n), st_local((size_t)n);
+    std::vector<uint8_t *> outs((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    JPK_TRY(dd_find(ctx, n, d_in, in_len, &dc, s1.data()));
+    for (int b = 0; b < n; b++) {
+        stp[b] = s1[(size_t)b] > out_cap[b] ? JPK_E_CAPACITY : JPK_OK;   // nothing of a block that does not fit is written
+        outs[(size_t)b] = stp[b] == JPK_OK ? d_out[b] : nullptr;
+        out_len[b] = stp[b] == JPK_OK ? s1[(size_t)b] : 0;
+    }
+    JPK_TRY(dd_emit(ctx, n, &dc, outs.data(), s1.data()));
     return status ? JPK_OK : first_status(n, stp);
 }
 
@@ -554,11 +859,30 @@ extern "C" int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t 
     return lpx_batch(ctx, true, n, d_in, len, d_out, status);
 }
 
-// The stage chain of jpk_cli_stages_encode for n blocks in HBM with two launches: k_enc_wrap R -> S2 into d_mid[b] (|S4| - 2 bytes; d_mid
+// The stage chain of jpk_cli_stages_encode_ex for n blocks in HBM: k_enc_wrap R -> S2 into d_mid[b] (jpk_cli_stages_bound - 2 bytes; d_mid
 // == nullptr: in the context's arena), k_enc_lpx S2 -> S3 two bytes into d_out[b], with the second end token in front of it.
-// in_len[b] < 0: the block is skipped.  The caller has checked that every |S4| fits its buffer and an int32.
-int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out)
+// in_len[b] < 0: the block is skipped.  The caller has checked that every jpk_cli_stages_bound fits its buffer and an int32.
+// flags & JPK_CLI_DEDUPE: dd_find and dd_emit first, S1' into d_out[b] (|S1'| < |S4|: it fits), and k_enc_wrap reads S1' from there at the
+// length the host has read; k_enc_lpx overwrites it behind k_enc_wrap in stream order.  s4_len[b] (nullable) = |S4|.
+namespace {
+int64_t s4_of_s1(int64_t s1) { return s1 + 2 + 2 * ((s1 + FBS - 1) / FBS); }
+
+// found != nullptr: dd_find has run for these blocks (its scratch is still in the arena) and found_s1[] holds its lengths
+int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out, uint32_t flags,
+                   int32_t *s4_len, DdCall *found, const int32_t *found_s1)
 {
+    const bool dedupe = (flags & JPK_CLI_DEDUPE) != 0;
+    std::vector<int32_t> s1((size_t)n);
+    for (int b = 0; b < n; b++) s1[(size_t)b] = in_len[b] < 0 ? -1 : in_len[b] + 2;
+    if (dedupe) {
+        DdCall own;
+        std::vector<uint8_t *> outs((size_t)n);
+        for (int b = 0; b < n; b++) outs[(size_t)b] = in_len[b] < 0 ? nullptr : d_out[b];
+        if (found) for (int b = 0; b < n; b++) s1[(size_t)b] = found_s1[b];
+        else JPK_TRY(dd_find(ctx, n, d_in, in_len, &own, s1.data()));
+        for (int b = 0; b < n; b++) if (in_len[b] < 0) s1[(size_t)b] = -1;
+        JPK_TRY(dd_emit(ctx, n, found ? found : &own, outs.data(), s1.data()));
+    }
     std::vector<PreJob> wj((size_t)n), lj((size_t)n);
     std::vector<size_t> moff((size_t)n, 0);
     size_t mid_bytes = 0;
@@ -574,14 +898,15 @@ int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const
     uint8_t *mids = real.get<uint8_t>(mid_bytes);
     uint64_t wwg = 0, lwg = 0, bytes = 0;
     for (int b = 0; b < n; b++) {
+        if (s4_len) s4_len[b] = in_len[b] < 0 ? 0 : (int32_t)s4_of_s1(s1[(size_t)b]);
         if (in_len[b] < 0) {
             wj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)wwg, 0u};
             lj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)lwg, 0u};
             continue;
         }
-        const int32_t s2 = (int32_t)(jpk_cli_stages_bound(in_len[b]) - 2);
+        const int32_t s2 = (int32_t)(s4_of_s1(s1[(size_t)b]) - 2);
         uint8_t *mid = d_mid ? d_mid[b] : mids + moff[(size_t)b];
-        wj[(size_t)b] = PreJob{d_in[b], mid, in_len[b], s2, (uint32_t)wwg, 0u};
+        wj[(size_t)b] = dedupe ? PreJob{d_out[b], mid, s1[(size_t)b], s2, (uint32_t)wwg, 0u} : PreJob{d_in[b], mid, in_len[b], s2, (uint32_t)wwg, 0u};
         lj[(size_t)b] = PreJob{mid, d_out[b] + 2, s2, s2, (uint32_t)lwg, 0u};
         const uint64_t words = (((uintptr_t)mid & 15u) + (uint64_t)s2 + 15u) / 16u;
         wwg += (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
@@ -592,33 +917,56 @@ int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const
     if (wwg) {
         JPK_HIP(hipMemcpyAsync(d_jobs, wj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
         JPK_HIP(hipMemcpyAsync(d_jobs + n, lj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
-        JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        if (dedupe) JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        else JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_enc_lpx, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
     }
     std::vector<uint32_t> none;
     return pre_finish(ctx, nullptr, none);
 }
+}  // namespace
 
-extern "C" int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
-                                                const int32_t *out_cap, int32_t *out_len, int32_t *status)
+int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out,
+                          uint32_t flags, int32_t *s4_len)
 {
-    JPK_TRY(pre_enter(ctx));
-    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
-    if (n == 0) return JPK_OK;
-    std::vector<int32_t> lens((size_t)n), st_local((size_t)n);
-    int32_t *stp = status ? status : st_local.data();
+    return cli_stages_run(ctx, n, d_in, in_len, d_mid, d_out, flags, s4_len, nullptr, nullptr);
+}
+
+// With the dedupe a block's |S4| is known when its S1' is: dd_find for all blocks, the capacity answer, then the rest for those that fit
+extern "C" int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                                   const int32_t *out_cap, int32_t *out_len, int32_t *status, uint32_t flags)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
     for (int b = 0; b < n; b++) {
         if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
         if (jpk_cli_stages_bound(in_len[b]) > 0x7fffffff) return JPK_E_ARG;
     }
+    JPK_TRY(pre_enter(ctx));
+    if (n == 0) return JPK_OK;
+    std::vector<int32_t> lens((size_t)n), st_local((size_t)n), s1((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    DdCall dc;
+    const bool dedupe = (flags & JPK_CLI_DEDUPE) != 0;
+    if (dedupe) {
+        // the lengths alone first: a block that does not fit must stay unwritten, and S1' is staged in its own output buffer
+        JPK_TRY(dd_find(ctx, n, d_in, in_len, &dc, s1.data()));
+    } else {
+        for (int b = 0; b < n; b++) s1[(size_t)b] = in_len[b] + 2;
+    }
     for (int b = 0; b < n; b++) {
-        const int64_t total = jpk_cli_stages_bound(in_len[b]);
+        const int64_t total = s4_of_s1(s1[(size_t)b]);
         stp[b] = total > out_cap[b] ? JPK_E_CAPACITY : JPK_OK;        // nothing of a block that does not fit is written
         lens[(size_t)b] = stp[b] == JPK_OK ? in_len[b] : -1;
         out_len[b] = stp[b] == JPK_OK ? (int32_t)total : 0;
     }
-    JPK_TRY(jpk_cli_stages_device(ctx, n, d_in, lens.data(), nullptr, d_out));
+    JPK_TRY(cli_stages_run(ctx, n, d_in, lens.data(), nullptr, d_out, flags, nullptr, dedupe ? &dc : nullptr, s1.data()));
     return status ? JPK_OK : first_status(n, stp);
+}
+
+extern "C" int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                                const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    return jpk_dev_blocks_cli_stages_encode_ex(ctx, n, d_in, in_len, d_out, out_cap, out_len, status, 0u);
 }
 
 extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
