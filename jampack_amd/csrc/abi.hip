@@ -1,6 +1,7 @@
 // abi.hip -- C ABI of libjampack_amd.so (include/jampack_abi.h): contexts, HBM arena, PCIe staging for the
-// host-buffer (drop-in) entry points, and the fused block pipeline.  No CPU fallback: without a gfx950 device
-// every entry point returns JPK_E_NODEVICE.
+// host-buffer (drop-in) entry points, the fused block pipeline, the batch and multi-GPU engines and the single
+// .jam frames.  Whole .jam archives and their range reads are in jam_archive.hip.  No CPU fallback: without a
+// gfx950 device every entry point returns JPK_E_NODEVICE.
 #include <chrono>
 #include <atomic>
 #include <algorithm>
@@ -48,7 +49,7 @@ int jpk_arena_ensure(jpk_ctx *ctx, size_t bytes)
     return JPK_OK;
 }
 
-static int buf_ensure(jpk_ctx *ctx, uint8_t **p, size_t *cap, size_t bytes)
+int jpk_buf_ensure(jpk_ctx *ctx, uint8_t **p, size_t *cap, size_t bytes)
 {
     if (bytes <= *cap) return JPK_OK;
     JPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -61,8 +62,8 @@ static int buf_ensure(jpk_ctx *ctx, uint8_t **p, size_t *cap, size_t bytes)
 
 int jpk_stage_ensure(jpk_ctx *ctx, size_t in_bytes, size_t out_bytes)
 {
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, in_bytes));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, out_bytes));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, in_bytes));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, out_bytes));
     return JPK_OK;
 }
 
@@ -326,10 +327,6 @@ extern "C" int jpk_debug_enc_groups(int device, int32_t nch)
     return jpk_enc_groups_for(g_compress_inflight[device].load(std::memory_order_relaxed) + 1, (uint32_t)nch);
 }
 
-#define JPK_ENTER(ctx)                         \
-    if (!(ctx)) return JPK_E_ARG;              \
-    JPK_HIP(hipSetDevice((ctx)->device))
-
 extern "C" int jpk_dev_bwt_forward(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, uint8_t *d_out, int32_t out_cap, int32_t *out_len)
 {
     JPK_ENTER(ctx);
@@ -403,7 +400,7 @@ extern "C" int jpk_dev_block_compress(jpk_ctx *ctx, const uint8_t *d_in, int32_t
     if (!d_out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
     if ((uint32_t)in_len >= JPK_FWD_BWT_LIMIT) return JPK_E_ARG;      // before anything is allocated for it (jpk_fwd_bwt_device)
     const size_t mid = (size_t)in_len + JPK_TRAILER_BYTES;
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, mid));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, mid));
     if (in_len < JPK_BWT_UNITS) JPK_HIP(hipMemsetAsync(ctx->stage_out, 0, mid, ctx->stream));   // untouched trailer: defined bytes
     int rc = jpk_fwd_bwt_device(ctx, d_in, in_len, ctx->stage_out);
     if (rc == JPK_OK) rc = jpk_ans_encode_device(ctx, ctx->stage_out, (int32_t)mid, d_out, out_cap, out_len);    // synchronises the stream
@@ -416,7 +413,7 @@ extern "C" int jpk_dev_block_decompress(jpk_ctx *ctx, const uint8_t *d_in, int32
     JPK_ENTER(ctx);
     if (!d_out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
     const size_t mid_cap = (size_t)out_cap + JPK_TRAILER_BYTES;
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, mid_cap));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_out, &ctx->stage_out_cap, mid_cap));
     int32_t mid = 0;
     JPK_TRY(jpk_ans_decode_device(ctx, d_in, in_len, ctx->stage_out, (int32_t)(mid_cap > 0x7fffffff ? 0x7fffffff : mid_cap), &mid));
     if (mid < JPK_TRAILER_BYTES) return JPK_E_CORRUPT;
@@ -679,8 +676,32 @@ extern "C" int jpk_dev_checksum(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_le
     return jpk_read_mail(ctx, crc, 1);
 }
 
-namespace {
-bool jam_block_size_ok(int32_t bs) { return bs >= JPK_MIN_BLOCKSIZE && bs <= JPK_MAX_BLOCKSIZE; }
+extern "C" int jpk_dev_checksums(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint32_t *crc)
+{
+    JPK_ENTER(ctx);
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !crc))) return JPK_E_ARG;
+    for (int i = 0; i < n; i++) if (in_len[i] < 0 || (in_len[i] > 0 && !d_in[i])) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)n * 4));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    JPK_TRY(jpk_checksums_device(ctx, n, d_in, in_len, d_crc));
+    JPK_HIP(hipMemcpyAsync(crc, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    return JPK_OK;
+}
+
+bool jpk_jam_block_size_ok(int32_t bs) { return bs >= JPK_MIN_BLOCKSIZE && bs <= JPK_MAX_BLOCKSIZE; }
+
+// DecompReadBlock's header checks (jampack.cpp:140-163) on the 15 header bytes at h, with `avail` bytes from h to the end of the input
+bool jpk_jam_header_parse(const uint8_t *h, int64_t avail, uint32_t *crc, int32_t *psize, int32_t *block_size)
+{
+    if (avail < JPK_JAM_HEADER_BYTES) return false;
+    memcpy(crc, h + 3, 4);
+    memcpy(psize, h + 7, 4);
+    memcpy(block_size, h + 11, 4);
+    // "Refusing to read from corrupt header!", jampack.cpp:150 -- and the payload fits in what is left
+    return memcmp(h, "JAM", 3) == 0 && jpk_jam_block_size_ok(*block_size) && *psize >= 0 && *psize <= JPK_MAX_BLOCKSIZE &&
+           (int64_t)*psize <= avail - JPK_JAM_HEADER_BYTES;
 }
 
 extern "C" int jpk_dev_jam_block_write(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, int32_t block_size, uint8_t *d_out, int32_t out_cap,
@@ -688,7 +709,7 @@ extern "C" int jpk_dev_jam_block_write(jpk_ctx *ctx, const uint8_t *d_in, int32_
 {
     JPK_ENTER(ctx);
     if (!d_out || !out_len || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
-    if (!jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
+    if (!jpk_jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
     if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
     uint32_t crc = 0;
     JPK_TRY(jpk_dev_checksum(ctx, d_in, in_len, &crc));
@@ -716,12 +737,7 @@ extern "C" int jpk_dev_jam_block_read(jpk_ctx *ctx, const uint8_t *d_in, int32_t
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     uint32_t crc;
     int32_t csize, block_size;
-    memcpy(&crc, h + 3, 4);
-    memcpy(&csize, h + 7, 4);
-    memcpy(&block_size, h + 11, 4);
-    // DecompReadBlock, jampack.cpp:150: "Refusing to read from corrupt header!"
-    if (memcmp(h, "JAM", 3) != 0 || !jam_block_size_ok(block_size) || csize < 0 || csize > JPK_MAX_BLOCKSIZE) return JPK_E_CORRUPT;
-    if ((int64_t)csize + JPK_JAM_HEADER_BYTES > in_len) return JPK_E_CORRUPT;
+    if (!jpk_jam_header_parse(h, in_len, &crc, &csize, &block_size)) return JPK_E_CORRUPT;
     int32_t n = 0;
     JPK_TRY(jpk_dev_block_decompress(ctx, d_in + JPK_JAM_HEADER_BYTES, csize, d_out, out_cap, &n));
     uint32_t got = 0;
@@ -782,8 +798,9 @@ struct TlsCtx {
     }
 };
 thread_local TlsCtx tls;
+}  // namespace
 
-int tls_ctx(jpk_ctx **out)
+int jpk_tls_ctx(jpk_ctx **out)
 {
     CtxPool &p = pool();
     std::lock_guard<std::mutex> g(p.mu);
@@ -806,7 +823,14 @@ int tls_ctx(jpk_ctx **out)
     *out = c;
     return JPK_OK;
 }
-}  // namespace
+
+// the opening of the host-buffer entries: the calling thread's context, its device current, stage_in of at least stage_in_bytes
+int jpk_host_enter(jpk_ctx **ctx, size_t stage_in_bytes)
+{
+    JPK_TRY(jpk_tls_ctx(ctx));
+    JPK_HIP(hipSetDevice((*ctx)->device));
+    return jpk_buf_ensure(*ctx, &(*ctx)->stage_in, &(*ctx)->stage_in_cap, stage_in_bytes);
+}
 
 // ---- jpk_dev_blocks_compress: blocks in flight inside the library ---------------------------------------------------------
 namespace {
@@ -911,7 +935,7 @@ int group_compress(jpk_ctx *c, int nb, const uint8_t *const *d_in, const int32_t
     (void)nlen_total;
     size_t stage_bytes, arena_bytes;
     group_needs(nb, in_len, &stage_bytes, &arena_bytes);
-    JPK_TRY(buf_ensure(c, &c->stage_out, &c->stage_out_cap, stage_bytes));
+    JPK_TRY(jpk_buf_ensure(c, &c->stage_out, &c->stage_out_cap, stage_bytes));
     JPK_TRY(jpk_arena_ensure(c, arena_bytes));
     std::vector<uint8_t *> img((size_t)nb);
     for (int b = 0; b < nb; b++) {
@@ -1008,7 +1032,7 @@ int blocks_compress_body(jpk_ctx *ctx, int32_t nblocks, const uint8_t *const *d_
     auto work = [&](jpk_ctx *c) {
         if (hipSetDevice(c->device) != hipSuccess) return;                  // a fresh thread starts on device 0
         if (c != ctx && hipStreamWaitEvent(c->stream, ctx->ev_batch, 0) != hipSuccess) return;   // leaves its share to the others
-        if (max_arena && (buf_ensure(c, &c->stage_out, &c->stage_out_cap, max_stage) != JPK_OK || jpk_arena_ensure(c, max_arena) != JPK_OK)) {
+        if (max_arena && (jpk_buf_ensure(c, &c->stage_out, &c->stage_out_cap, max_stage) != JPK_OK || jpk_arena_ensure(c, max_arena) != JPK_OK)) {
             // no room for the largest group on this context: the groups say so themselves when they get here (single blocks may still fit)
         }
         for (;;) {
@@ -1181,7 +1205,12 @@ struct DeviceRestore {
     DeviceRestore() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
     ~DeviceRestore() { if (dev >= 0) (void)hipSetDevice(dev); }
 };
-size_t multi_comp_cap(int32_t len) { return (size_t)((int64_t)(len + JPK_TRAILER_BYTES) * 5 / 4) + 4096 + 1400 * ((size_t)(len + JPK_TRAILER_BYTES) / JPK_ANS_CHUNK + 1); }
+}  // namespace
+
+// the output slot that always holds the compressed form of a block of len bytes
+size_t jpk_multi_comp_cap(int32_t len) { return (size_t)((int64_t)(len + JPK_TRAILER_BYTES) * 5 / 4) + 4096 + 1400 * ((size_t)(len + JPK_TRAILER_BYTES) / JPK_ANS_CHUNK + 1); }
+
+namespace {
 
 // compress: in[b] host blocks of in_len[b] bytes -> compressed blocks; decompress: in[b] host compressed blocks, raw_len[b] = the
 // block's decompressed size.  Either way block b runs on devices[b mod G] through the library's batch entry on that device
@@ -1218,7 +1247,7 @@ int multi_run(bool compress, uint64_t device_mask, int32_t nblocks, const uint8_
     struct Dev { jpk_ctx *c = nullptr; MultiSlab *slab = nullptr; std::vector<int> blocks; std::vector<size_t> ioff, ooff; int rc = JPK_OK; };
     std::vector<Dev> dv((size_t)G);
     for (int b = 0; b < nblocks; b++) dv[(size_t)(b % G)].blocks.push_back(b);
-    auto cap_of = [&](int b) { return compress ? multi_comp_cap(in_len[b]) : (size_t)raw_len[b]; };
+    auto cap_of = [&](int b) { return compress ? jpk_multi_comp_cap(in_len[b]) : (size_t)raw_len[b]; };
     auto work = [&](int g) {
         Dev &D = dv[(size_t)g];
         if (D.blocks.empty()) return;
@@ -1415,7 +1444,7 @@ extern "C" int jpk_init_devices(int32_t *devices, int32_t cap)
 extern "C" int jpk_thread_device(void)
 {
     jpk_ctx *ctx;
-    int rc = tls_ctx(&ctx);
+    int rc = jpk_tls_ctx(&ctx);
     return rc == JPK_OK ? ctx->device : rc;
 }
 
@@ -1472,19 +1501,15 @@ extern "C" int jpk_release_idle(void)
 }
 
 namespace {
-typedef int (*dev_fn)(jpk_ctx *, const uint8_t *, int32_t, uint8_t *, int32_t, int32_t *);
-
-// H2D -> device entry -> D2H.  prefill_out: copy the caller's out bytes to the device first (used where the
-// reference leaves part of the output untouched).
-int staged(dev_fn fn, const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, bool prefill_out)
+// H2D -> device entry fn(ctx, d_in, in_len, d_out, out_cap, &out_len) -> D2H.  prefill_out: copy the caller's out bytes to the device
+// first (used where the reference leaves part of the output untouched).
+template <class Fn> int staged(Fn fn, const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, bool prefill_out)
 {
     if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
     jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)in_len + 64));
+    JPK_TRY(jpk_host_enter(&ctx, (size_t)in_len + 64));
     // the fused entry points use stage_out as their intermediate, so the host-visible result gets its own buffer
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)out_cap + 64));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)out_cap + 64));
     uint8_t *d_res = ctx->stage_res;
     if (in_len) JPK_HIP(hipMemcpyAsync(ctx->stage_in, in, (size_t)in_len, hipMemcpyHostToDevice, ctx->stream));
     if (prefill_out && out_cap) JPK_HIP(hipMemcpyAsync(d_res, out, (size_t)out_cap, hipMemcpyHostToDevice, ctx->stream));
@@ -1578,14 +1603,14 @@ extern "C" int jpk_ans_decode(const uint8_t *in, int32_t in_len, uint8_t *out, i
     if (combine_grace_us() < 0) return staged(jpk_dev_ans_decode, in, in_len, out, out_cap, out_len, false);
     if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
     jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
+    JPK_TRY(jpk_tls_ctx(&ctx));
     JPK_HIP(hipSetDevice(ctx->device));
     if (ctx->device < 0 || ctx->device >= 64 || in_len == 0) return staged(jpk_dev_ans_decode, in, in_len, out, out_cap, out_len, false);
     Combiner &cb = combiner(ctx->device);
     cb.arriving.fetch_add(1);
     struct Arrived { Combiner &c; bool in = true; ~Arrived() { if (in) c.arriving.fetch_sub(1); } void submitted() { if (in) { c.arriving.fetch_sub(1); in = false; } } } arrived{cb};
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)in_len + 64));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)out_cap + 64));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)in_len + 64));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)out_cap + 64));
     JPK_HIP(hipMemcpyAsync(ctx->stage_in, in, (size_t)in_len, hipMemcpyHostToDevice, ctx->stream));
     JPK_HIP(hipEventRecord(ctx->ev_batch, ctx->stream));
     DecReq req;
@@ -1738,9 +1763,7 @@ extern "C" int jpk_rank_encode(uint8_t *t, int32_t *freq256, int32_t len)
 {
     if (!freq256 || len < 0 || (len > 0 && !t)) return JPK_E_ARG;
     jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 2048));
+    JPK_TRY(jpk_host_enter(&ctx, (size_t)len + 2048));
     uint8_t *d_t = ctx->stage_in + 1024;
     int32_t *d_f = (int32_t *)ctx->stage_in;
     if (len) JPK_HIP(hipMemcpyAsync(d_t, t, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
@@ -1755,9 +1778,7 @@ extern "C" int jpk_rank_decode(uint8_t *ranks, const int32_t *freq256, int32_t l
 {
     if (!freq256 || len < 0 || (len > 0 && !ranks)) return JPK_E_ARG;
     jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 2048));
+    JPK_TRY(jpk_host_enter(&ctx, (size_t)len + 2048));
     uint8_t *d_t = ctx->stage_in + 1024;
     int32_t *d_f = (int32_t *)ctx->stage_in;
     if (len) JPK_HIP(hipMemcpyAsync(d_t, ranks, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
@@ -1772,30 +1793,17 @@ extern "C" int jpk_checksum(const uint8_t *in, int32_t in_len, uint32_t *crc)
 {
     if (!crc || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
     jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)in_len + 64));
+    JPK_TRY(jpk_host_enter(&ctx, (size_t)in_len + 64));
     if (in_len) JPK_HIP(hipMemcpyAsync(ctx->stage_in, in, (size_t)in_len, hipMemcpyHostToDevice, ctx->stream));
     return jpk_dev_checksum(ctx, ctx->stage_in, in_len, crc);
 }
 
-namespace {
-thread_local int32_t tls_block_size = 0;
-thread_local int32_t tls_consumed = 0;
-int jam_write_tramp(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, uint8_t *d_out, int32_t out_cap, int32_t *out_len)
-{
-    return jpk_dev_jam_block_write(ctx, d_in, in_len, tls_block_size, d_out, out_cap, out_len);
-}
-int jam_read_tramp(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, uint8_t *d_out, int32_t out_cap, int32_t *out_len)
-{
-    return jpk_dev_jam_block_read(ctx, d_in, in_len, d_out, out_cap, out_len, &tls_consumed);
-}
-}  // namespace
-
 extern "C" int jpk_jam_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
-    tls_block_size = block_size;
-    return staged(jam_write_tramp, in, in_len, out, out_cap, out_len, false);
+    auto write = [block_size](jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint8_t *d_out, int32_t cap, int32_t *n) {
+        return jpk_dev_jam_block_write(ctx, d_in, len, block_size, d_out, cap, n);
+    };
+    return staged(write, in, in_len, out, out_cap, out_len, false);
 }
 
 extern "C" int jpk_jam_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed)
@@ -1806,9 +1814,12 @@ extern "C" int jpk_jam_block_read(const uint8_t *in, int32_t in_len, uint8_t *ou
         if (csize < 0 || csize > JPK_MAX_BLOCKSIZE || (int64_t)csize + JPK_JAM_HEADER_BYTES > in_len) return JPK_E_CORRUPT;
         in_len = csize + JPK_JAM_HEADER_BYTES;
     }
-    tls_consumed = 0;
-    int rc = staged(jam_read_tramp, in, in_len, out, out_cap, out_len, false);
-    if (rc == JPK_OK && consumed) *consumed = tls_consumed;
+    int32_t used = 0;
+    auto read = [&used](jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint8_t *d_out, int32_t cap, int32_t *n) {
+        return jpk_dev_jam_block_read(ctx, d_in, len, d_out, cap, n, &used);
+    };
+    const int rc = staged(read, in, in_len, out, out_cap, out_len, false);
+    if (rc == JPK_OK && consumed) *consumed = used;
     return rc;
 }
 
@@ -1817,14 +1828,9 @@ extern "C" int jpk_jam_block_read(const uint8_t *in, int32_t in_len, uint8_t *ou
 extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed)
 {
     if (!in || !out || !out_len || in_len < 0 || out_cap < 0) return JPK_E_ARG;
-    if (in_len < JPK_JAM_HEADER_BYTES) return JPK_E_CORRUPT;
     uint32_t crc;
     int32_t csize, block_size;
-    memcpy(&crc, in + 3, 4);
-    memcpy(&csize, in + 7, 4);
-    memcpy(&block_size, in + 11, 4);
-    if (memcmp(in, "JAM", 3) != 0 || !jam_block_size_ok(block_size) || csize < 0 || csize > JPK_MAX_BLOCKSIZE) return JPK_E_CORRUPT;
-    if ((int64_t)csize + JPK_JAM_HEADER_BYTES > in_len) return JPK_E_CORRUPT;
+    if (!jpk_jam_header_parse(in, in_len, &crc, &csize, &block_size)) return JPK_E_CORRUPT;
     const int64_t cap64 = (int64_t)((double)block_size * 1.05) + 4096;             // the reference's stage buffers, jampack.cpp:156
     if (cap64 > 0x7fffffff) return JPK_E_ARG;
     const int32_t cap = (int32_t)cap64;
@@ -1849,7 +1855,7 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
 extern "C" int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
 {
     if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
-    if (!jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
+    if (!jpk_jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
     if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
     const int32_t cap = (int32_t)jpk_cli_stages_bound(in_len);                       // < 2^31 for in_len <= JPK_MAX_BLOCKSIZE (prestage.cpp)
     static thread_local std::vector<uint8_t> s4;
@@ -1869,880 +1875,4 @@ extern "C" int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int
 extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
     return jpk_jam_cli_block_write_ex(in, in_len, block_size, out, out_cap, out_len, 0u);
-}
-
-// ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
-// Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
-// in ctx->jam_scratch, the frame offsets on the host (64-bit), one k_jam_pack launch that writes the frames.  Decompress: the frame
-// walk (k_jam_walk, one launch + one read-back per JPK_JAM_PASS_FRAMES frames) and the decoded sizes (pass 1 of the batch decoder)
-// over the whole archive first -- that is what makes the capacity answer exact and leaves d_out untouched when it is too small --
-// then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out (its payload read in place in the archive),
-// one batched checksum of the outputs, and the comparison with the header crcs.  A pass holds at most JPK_JAM_PASS_FRAMES frames
-// and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
-// The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
-// the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
-// of the raw slices.  With JPK_CLI_DEDUPE the k_dd_* launches come first (raw slice -> S1' in slot B), the pass's S1' lengths are read
-// on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.
-namespace {
-constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
-
-int jam_pass_frames(int32_t block_size)
-{
-    const uint64_t k = JAM_PASS_RAW / (uint64_t)block_size;
-    return k < (uint64_t)JPK_JAM_PASS_FRAMES ? (int)k : JPK_JAM_PASS_FRAMES;
-}
-
-// one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
-struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
-
-// the checks of the frame walk beyond its header (k_jam_walk / jam_walk_host): the payload declares at least the BWT trailer and at
-// most BlockSize raw bytes (the reference decodes into buffers of 1.05 x BlockSize, jampack.cpp:156-159)
-bool jam_decoded_ok(int64_t decoded, int32_t block_size) { return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= block_size; }
-// ... and for a frame of the stock CLI, whose entropy-decoded bytes are the output of its pre-stages (filter headers and LZ tokens add
-// bytes): at most the reference's stage buffers, 1.05 x BlockSize + 4096 (jampack.cpp:156), as jpk_jam_cli_block_read has them
-int32_t jam_cli_cap(int32_t block_size) { return (int32_t)((int64_t)((double)block_size * 1.05) + 4096); }
-bool jam_cli_decoded_ok(int64_t decoded, int32_t block_size) { return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= jam_cli_cap(block_size); }
-
-// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); cli: frames of the
-// stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders)
-void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
-{
-    *bad = -1;
-    int64_t o = 0;
-    while (o < in_len) {
-        const int32_t k = (int32_t)fr.size();
-        if (in_len - o < JPK_JAM_HEADER_BYTES) { *bad = k; return; }       // 1..14 trailing bytes
-        JamFrame f;
-        memcpy(&f.crc, in + o + 3, 4);
-        memcpy(&f.psize, in + o + 7, 4);
-        memcpy(&f.block_size, in + o + 11, 4);
-        // DecompReadBlock, jampack.cpp:140-163
-        if (memcmp(in + o, "JAM", 3) != 0 || !jam_block_size_ok(f.block_size) || f.psize < 0 || f.psize > JPK_MAX_BLOCKSIZE ||
-            (int64_t)f.psize > in_len - o - JPK_JAM_HEADER_BYTES) { *bad = k; return; }
-        f.payload_off = o + JPK_JAM_HEADER_BYTES;
-        int64_t decoded = 0;
-        if (jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK ||
-            !(cli ? jam_cli_decoded_ok(decoded, f.block_size) : jam_decoded_ok(decoded, f.block_size))) { *bad = k; return; }
-        f.raw = decoded - JPK_TRAILER_BYTES;
-        fr.push_back(f);
-        o = f.payload_off + f.psize;
-    }
-}
-
-// the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
-int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
-{
-    *bad = -1;
-    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
-    JamWalkFrame *d_tab = reinterpret_cast<JamWalkFrame *>(ctx->jam_scratch);
-    std::vector<JamWalkFrame> h(JPK_JAM_PASS_FRAMES);
-    std::vector<const uint8_t *> ins;
-    std::vector<int32_t> lens, st;
-    std::vector<int64_t> dec;
-    uint64_t o = 0;
-    while (o < (uint64_t)in_len) {
-        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail));
-        JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
-        uint32_t m[4];
-        JPK_TRY(jpk_read_mail(ctx, m, 4));                   // synchronises: the table is on the host too
-        const int n = (int)m[0];
-        ins.resize((size_t)n); lens.resize((size_t)n); st.resize((size_t)n); dec.resize((size_t)n);
-        for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
-        JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
-        for (int i = 0; i < n; i++) {
-            if (st[i] != JPK_OK || !(cli ? jam_cli_decoded_ok(dec[i], h[i].block_size) : jam_decoded_ok(dec[i], h[i].block_size))) { *bad = (int32_t)fr.size(); return JPK_OK; }
-            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, h[i].block_size, dec[i] - JPK_TRAILER_BYTES});
-        }
-        if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
-        o = ((uint64_t)m[3] << 32) | m[2];
-    }
-    return JPK_OK;
-}
-
-// frames [k, e) of fr form the pass that starts at frame k: at most JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW raw bytes (one at least)
-size_t jam_pass_end(const std::vector<JamFrame> &fr, size_t k)
-{
-    size_t e = k;
-    uint64_t raw = 0;
-    while (e < fr.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || raw + (uint64_t)fr[e].raw <= JAM_PASS_RAW)) raw += (uint64_t)fr[e++].raw;
-    return e;
-}
-
-// what the batch compress is given for a raw slice of len bytes: the slice, or its S4 (cli; prestage.cpp) -- and the payload it can give
-int32_t jam_bwt_len(int32_t len, bool cli) { return cli ? (int32_t)jpk_cli_stages_bound(len) : len; }
-int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (int64_t)multi_comp_cap(jam_bwt_len(len, cli)); }
-
-// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
-// of the stock CLI
-int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
-                      int32_t in_flight, bool cli, uint32_t flags)
-{
-    const int n = (int)((len + block_size - 1) / block_size);
-    std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
-    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n);
-    std::vector<int32_t> lens((size_t)n), blens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
-    const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
-    size_t need = o_slots;
-    for (int i = 0; i < n; i++) {
-        ins[i] = d_in + (int64_t)i * block_size;
-        lens[i] = (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size);
-        blens[i] = jam_bwt_len(lens[i], cli);
-        caps[i] = (int32_t)multi_comp_cap(blens[i]);
-        need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
-        if (cli) need += 2 * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
-    }
-    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(ctx->jam_scratch + o_frames);
-    size_t off = o_slots;
-    for (int i = 0; i < n; i++) {
-        slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64);
-        bwt_in[i] = ins[i];
-        if (cli) {
-            sa[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
-            sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
-            bwt_in[i] = sb[i];
-        }
-    }
-    // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
-    JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
-    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
-    JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
-    for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
-    std::vector<JamPackFrame> fr((size_t)n);
-    uint64_t pos = 0;
-    for (int i = 0; i < n; i++) {
-        fr[i].slot = slots[i]; fr[i].off = pos; fr[i].psize = outl[i]; fr[i].pad = 0;
-        pos += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)outl[i];
-    }
-    if ((int64_t)pos > out_room) return JPK_E_CAPACITY;
-    JPK_HIP(hipMemcpyAsync(d_frames, fr.data(), (size_t)n * sizeof(JamPackFrame), hipMemcpyHostToDevice, ctx->stream));
-    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, block_size, d_out, pos));
-    JPK_HIP(hipStreamSynchronize(ctx->stream));
-    *pass_len = (int64_t)pos;
-    return JPK_OK;
-}
-}  // namespace
-
-extern "C" int jpk_dev_checksums(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint32_t *crc)
-{
-    JPK_ENTER(ctx);
-    if (n < 0 || (n > 0 && (!d_in || !in_len || !crc))) return JPK_E_ARG;
-    for (int i = 0; i < n; i++) if (in_len[i] < 0 || (in_len[i] > 0 && !d_in[i])) return JPK_E_ARG;
-    if (n == 0) return JPK_OK;
-    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)n * 4));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    JPK_TRY(jpk_checksums_device(ctx, n, d_in, in_len, d_crc));
-    JPK_HIP(hipMemcpyAsync(crc, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    JPK_HIP(hipStreamSynchronize(ctx->stream));
-    return JPK_OK;
-}
-
-namespace {
-int64_t jam_compress_bound(int64_t in_len, int32_t block_size, bool cli)
-{
-    if (in_len < 0 || !jam_block_size_ok(block_size)) return JPK_E_ARG;
-    const int64_t full = in_len / block_size, rest = in_len % block_size;
-    return full * jam_frame_bound(block_size, cli) + (rest ? jam_frame_bound((int32_t)rest, cli) : 0);
-}
-
-int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                     int32_t in_flight, bool cli, uint32_t flags = 0u)
-{
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
-    if (!jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
-    *out_len = 0;
-    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
-    int64_t pos = 0;
-    for (int64_t o = 0; o < in_len; o += step) {
-        int64_t n = 0;
-        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli, flags));
-        pos += n;
-    }
-    *out_len = pos;
-    return JPK_OK;
-}
-}  // namespace
-
-extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, false); }
-extern "C" int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, true); }
-
-extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                    int32_t in_flight)
-{
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, false);
-}
-
-extern "C" int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
-                                        int64_t *out_len, int32_t in_flight)
-{
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true);
-}
-
-extern "C" int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
-                                           int64_t *out_len, int32_t in_flight, uint32_t flags)
-{
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true, flags);
-}
-
-extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
-                                      int32_t *bad_frame)
-{
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    *out_len = 0;
-    if (frames) *frames = 0;
-    if (bad_frame) *bad_frame = -1;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
-    int64_t need = 0;
-    for (const JamFrame &f : fr) need += f.raw;
-    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }         // the size query (out_cap = 0) ends here
-    JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * 4));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k);
-        const int n = (int)(e - k);
-        std::vector<const uint8_t *> ins((size_t)n);
-        std::vector<uint8_t *> outs((size_t)n);
-        std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
-        std::vector<uint32_t> crc((size_t)n);
-        int64_t o = pos;
-        for (int i = 0; i < n; i++) {
-            const JamFrame &f = fr[k + i];
-            ins[i] = d_in + f.payload_off; lens[i] = f.psize;
-            outs[i] = d_out + o; caps[i] = (int32_t)f.raw;
-            o += f.raw;
-        }
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
-        int fail = n, rc = JPK_OK;
-        for (int i = 0; i < n && fail == n; i++) if (st[i] != JPK_OK || outl[i] != caps[i]) { fail = i; rc = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; }
-        if (fail > 0) {
-            JPK_TRY(jpk_checksums_device(ctx, fail, outs.data(), caps.data(), d_crc));
-            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, (size_t)fail * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-            for (int i = 0; i < fail; i++) if (crc[i] != fr[k + i].crc) { fail = i; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
-        }
-        for (int i = 0; i < fail; i++) pos += caps[i];
-        if (fail < n) {
-            *out_len = pos;
-            if (frames) *frames = (int32_t)(k + fail);
-            if (bad_frame) *bad_frame = (int32_t)(k + fail);
-            return rc;
-        }
-        k = e;
-    }
-    *out_len = pos;
-    if (frames) *frames = (int32_t)fr.size();
-    if (bad >= 0) {
-        if (bad_frame) *bad_frame = bad;
-        return JPK_E_CORRUPT;
-    }
-    return JPK_OK;
-}
-
-extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame)
-{
-    if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad);
-    int64_t raw = 0;
-    for (const JamFrame &f : fr) raw += f.raw;
-    if (frames) *frames = (int32_t)fr.size();
-    if (raw_len) *raw_len = raw;
-    if (bad_frame) *bad_frame = bad;
-    return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
-}
-
-namespace {
-int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli,
-                      uint32_t flags = 0u)
-{
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
-    if (!jam_block_size_ok(block_size)) return JPK_E_ARG;
-    *out_len = 0;
-    jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    // staged one pass at a time: the device call makes the same passes, so the frames are those of one call over the whole input
-    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
-    int64_t pos = 0;
-    for (int64_t o = 0; o < in_len; o += step) {
-        const int64_t len = std::min(step, in_len - o), bound = jam_compress_bound(len, block_size, cli);
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 64));
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
-        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
-        int64_t n = 0;
-        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli, flags));
-        if (n > out_cap - pos) return JPK_E_CAPACITY;
-        JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        JPK_HIP(hipStreamSynchronize(ctx->stream));
-        pos += n;
-    }
-    *out_len = pos;
-    return JPK_OK;
-}
-}  // namespace
-
-extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
-{
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, false);
-}
-
-extern "C" int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
-{
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true);
-}
-
-extern "C" int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
-                                       uint32_t flags)
-{
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true, flags);
-}
-
-extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
-{
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
-    *out_len = 0;
-    if (frames) *frames = 0;
-    if (bad_frame) *bad_frame = -1;
-    jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad);
-    int64_t need = 0;
-    for (const JamFrame &f : fr) need += f.raw;
-    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }
-    // staged one pass at a time: the pass's frames are an archive of their own for the device call
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k);
-        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
-        int64_t raw = 0;
-        for (size_t i = k; i < e; i++) raw += fr[i].raw;
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)raw + 64));
-        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
-        int64_t n = 0;
-        int32_t nf = 0, bf = -1;
-        const int rc = jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, raw, &n, &nf, &bf);
-        if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        JPK_HIP(hipStreamSynchronize(ctx->stream));
-        if (rc != JPK_OK) {
-            if (rc == JPK_E_CORRUPT) *out_len = pos + n;
-            if (frames) *frames = (int32_t)k + nf;
-            if (bad_frame && bf >= 0) *bad_frame = (int32_t)k + bf;
-            return rc;
-        }
-        pos += n;
-        k = e;
-    }
-    *out_len = pos;
-    if (frames) *frames = (int32_t)fr.size();
-    if (bad >= 0) {
-        if (bad_frame) *bad_frame = bad;
-        return JPK_E_CORRUPT;
-    }
-    return JPK_OK;
-}
-
-// ---- whole archives of the stock CLI: every frame through the four pre-stage decoders on the device (prestage_dev.hip) -------------
-// Per pass: jpk_dev_blocks_decompress into slot A of every frame, then Lz77 A -> B, Lpx B -> A, Filters A -> B, Lz77 B -> A (the
-// order of Jampack::Decomp(), jampack.cpp:51-57), one batched checksum of the A slots against the header crcs, one k_jam_gather
-// launch that packs the verified frames back to back into d_out.  A frame's raw size is known only behind its last stage; every stage
-// works on the frames in front of the first one that has failed so far, which is where the call stops.
-namespace {
-// frames [k, e) of fr form the pass that starts at frame k: at most JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW bytes of BlockSize
-size_t jam_cli_pass_end(const std::vector<JamFrame> &fr, size_t k)
-{
-    size_t e = k;
-    uint64_t sum = 0;
-    while (e < fr.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || sum + (uint64_t)fr[e].block_size <= JAM_PASS_RAW)) sum += (uint64_t)fr[e++].block_size;
-    return e;
-}
-
-// the first block of st[0..m) that failed (*rc = its status), m when none did.  A stage that runs out of its slot (1.05 x BlockSize +
-// 4096, or BlockSize behind the last stage) met a bad frame: JPK_E_CAPACITY is kept for the caller's out_cap.
-int jam_cli_cut(const std::vector<int32_t> &st, int m, int *rc)
-{
-    for (int i = 0; i < m; i++) if (st[(size_t)i] != JPK_OK) { *rc = st[(size_t)i] == JPK_E_CAPACITY ? JPK_E_CORRUPT : st[(size_t)i]; return i; }
-    return m;
-}
-}  // namespace
-
-extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                          int32_t *frames, int32_t *bad_frame)
-{
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    *out_len = 0;
-    if (frames) *frames = 0;
-    if (bad_frame) *bad_frame = -1;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, true));
-    int64_t raw_bound = 0;
-    for (const JamFrame &f : fr) raw_bound += f.block_size;
-    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_cli_pass_end(fr, k);
-        const int n = (int)(e - k);
-        std::vector<const uint8_t *> ins((size_t)n), a_in((size_t)n), b_in((size_t)n);
-        std::vector<uint8_t *> a((size_t)n), b((size_t)n);
-        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), l0((size_t)n), l1((size_t)n), l3((size_t)n), raw((size_t)n), st((size_t)n);
-        std::vector<size_t> slot((size_t)n);
-        size_t need = o_slots;
-        for (int i = 0; i < n; i++) {
-            const JamFrame &f = fr[k + i];
-            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size;
-            caps[i] = jam_cli_cap(f.block_size);
-            slot[i] = jpk_align((size_t)caps[i] + 64);           // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
-            need += 2 * slot[i];
-        }
-        JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
-        size_t off = o_slots;
-        for (int i = 0; i < n; i++) {
-            a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i];
-            a_in[i] = a[i]; b_in[i] = b[i];
-        }
-        int rc = JPK_OK;
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), a.data(), caps.data(), l0.data(), st.data()));   // Ans::Decode + InverseBwt
-        int m = jam_cli_cut(st, n, &rc);
-        if (m) {
-            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, a_in.data(), l0.data(), b.data(), caps.data(), l1.data(), st.data()));   // Lz->Decompress
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, b_in.data(), l1.data(), a.data(), st.data()));                             // LocalModel->Decode
-        if (m) {
-            JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, a_in.data(), l1.data(), b.data(), caps.data(), l3.data(), st.data()));    // Filter->Decode
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) {
-            // Lz->Decompress; a frame that decodes to more than its BlockSize is a bad frame
-            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, b_in.data(), l3.data(), a.data(), bsz.data(), raw.data(), st.data()));
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) {
-            std::vector<uint32_t> crc((size_t)m);
-            JPK_TRY(jpk_checksums_device(ctx, m, a_in.data(), raw.data(), d_crc));
-            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-            for (int i = 0; i < m; i++) if (crc[i] != fr[k + i].crc) { m = i; rc = JPK_E_CORRUPT; break; }      // "Detected corrupt block!", jampack.cpp:59
-        }
-        int64_t sum = 0;
-        for (int i = 0; i < m; i++) sum += raw[i];
-        if (sum > out_cap - pos) {
-            *out_len = raw_bound;
-            if (frames) *frames = (int32_t)k;
-            return JPK_E_CAPACITY;
-        }
-        std::vector<JamGatherPiece> pieces;
-        uint64_t words = 0;
-        int64_t o = pos;
-        for (int i = 0; i < m; i++) {
-            if (raw[i] == 0) continue;
-            uint8_t *dst = d_out + o;
-            pieces.push_back(JamGatherPiece{a[i], dst, (uint64_t)raw[i], words, a[i], a[i] + slot[i]});
-            words += (((uintptr_t)dst & 15u) + (uint64_t)raw[i] + 15u) / 16u;
-            o += raw[i];
-        }
-        if (!pieces.empty()) {
-            JPK_HIP(hipMemcpyAsync(d_pieces, pieces.data(), pieces.size() * sizeof(JamGatherPiece), hipMemcpyHostToDevice, ctx->stream));
-            JPK_TRY(jpk_jam_gather_enqueue(ctx, d_pieces, (uint32_t)pieces.size(), words, (uint64_t)sum));
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->prof_on) jpk_prof_resolve(ctx);
-        }
-        pos += sum;
-        if (m < n) {
-            *out_len = pos;
-            if (frames) *frames = (int32_t)k + m;
-            if (bad_frame) *bad_frame = (int32_t)k + m;
-            return rc;
-        }
-        k = e;
-    }
-    *out_len = pos;
-    if (frames) *frames = (int32_t)fr.size();
-    if (bad >= 0) {
-        if (bad_frame) *bad_frame = bad;
-        return JPK_E_CORRUPT;
-    }
-    return JPK_OK;
-}
-
-extern "C" int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame)
-{
-    if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad, true);
-    int64_t bound = 0;
-    for (const JamFrame &f : fr) bound += f.block_size;
-    if (frames) *frames = (int32_t)fr.size();
-    if (raw_bound) *raw_bound = bound;
-    if (bad_frame) *bad_frame = bad;
-    return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
-}
-
-extern "C" int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
-{
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
-    *out_len = 0;
-    if (frames) *frames = 0;
-    if (bad_frame) *bad_frame = -1;
-    jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad, true);
-    int64_t raw_bound = 0;
-    for (const JamFrame &f : fr) raw_bound += f.block_size;
-    // staged one pass at a time: the pass's frames are an archive of their own for the device call, which decodes them into what is
-    // left of out_cap (at most the pass's BlockSize bytes)
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_cli_pass_end(fr, k);
-        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
-        int64_t room = 0;
-        for (size_t i = k; i < e; i++) room += fr[i].block_size;
-        room = std::min(room, out_cap - pos);
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
-        JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
-        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
-        int64_t n = 0;
-        int32_t nf = 0, bf = -1;
-        const int rc = jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
-        if (rc == JPK_E_CAPACITY) {
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-            *out_len = raw_bound;
-            if (frames) *frames = (int32_t)k;
-            return rc;
-        }
-        if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        JPK_HIP(hipStreamSynchronize(ctx->stream));
-        if (rc != JPK_OK) {
-            if (rc == JPK_E_CORRUPT) *out_len = pos + n;
-            if (frames) *frames = (int32_t)k + nf;
-            if (bad_frame && bf >= 0) *bad_frame = (int32_t)k + bf;
-            return rc;
-        }
-        pos += n;
-        k = e;
-    }
-    *out_len = pos;
-    if (frames) *frames = (int32_t)fr.size();
-    if (bad >= 0) {
-        if (bad_frame) *bad_frame = bad;
-        return JPK_E_CORRUPT;
-    }
-    return JPK_OK;
-}
-
-// ---- range reads of a .jam archive: jpk_jam_index + jpk_dev_jam_read / jpk_jam_read -----------------------------------------------
-// The index is the frame table of the walks with the 64-bit prefix sum of the raw sizes.  A read maps every range to the frames it
-// touches, decodes each touched frame ONCE -- in place in the first range that contains it whole, otherwise into a padded slot of
-// ctx->jam_scratch -- in passes with the limits of the archive calls, checks every decoded frame against its header crc, and delivers
-// the pieces of the verified frames with one k_jam_gather launch per pass.  A frame no range touches is neither decoded nor checked.
-struct jpk_jam_index {
-    struct Frame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
-    std::vector<Frame> fr;
-    std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
-    int64_t archive_len = 0;
-    int32_t bad = -1;
-};
-
-namespace {
-jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad)
-{
-    jpk_jam_index *ix = new (std::nothrow) jpk_jam_index;
-    if (!ix) return nullptr;
-    try {
-        ix->fr.reserve(fr.size());
-        ix->raw_off.reserve(fr.size() + 1);
-    } catch (const std::bad_alloc &) { delete ix; return nullptr; }
-    int64_t raw = 0;
-    for (const JamFrame &f : fr) {
-        ix->fr.push_back(jpk_jam_index::Frame{f.payload_off, f.psize, f.crc, f.block_size, f.raw});
-        ix->raw_off.push_back(raw);
-        raw += f.raw;
-    }
-    ix->raw_off.push_back(raw);
-    ix->archive_len = in_len;
-    ix->bad = bad;
-    return ix;
-}
-
-// the argument checks of both read entries: nothing is touched before they pass
-int jam_read_check(const jpk_jam_index *ix, const void *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out)
-{
-    if (!ix || n < 0 || in_len != ix->archive_len || (n > 0 && (!off || !len || !out))) return JPK_E_ARG;
-    const int64_t raw_len = ix->raw_off.back();
-    for (int32_t r = 0; r < n; r++) {
-        if (off[r] < 0 || len[r] < 0 || off[r] > raw_len || len[r] > raw_len - off[r]) return JPK_E_ARG;
-        if (len[r] > 0 && (!out[r] || !in)) return JPK_E_ARG;
-    }
-    return JPK_OK;
-}
-
-// The read itself.  The archive is d_in (HBM) or, when d_in is NULL, h_in (host memory: the payloads of a pass's frames are staged
-// through ctx->stage_in); d_out[] are device buffers in both cases.  status has n entries.
-int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
-                    uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
-{
-    const size_t F = ix->fr.size();
-    const std::vector<int64_t> &ro = ix->raw_off;
-    // frames [first[r], last[r]] of range r; pieces per frame (a piece = the part of one frame one range wants); the in-place home of
-    // a frame: inside the first range that contains it whole
-    std::vector<int32_t> first((size_t)n, -1), last((size_t)n, -1);
-    std::vector<size_t> start(F + 1, 0);
-    std::vector<uint8_t *> home(F, nullptr);
-    for (int32_t r = 0; r < n; r++) {
-        status[r] = JPK_OK;
-        if (len[r] == 0) continue;
-        const int64_t a = off[r], b = a + len[r];
-        first[r] = (int32_t)(std::upper_bound(ro.begin(), ro.end(), a) - ro.begin()) - 1;
-        last[r] = (int32_t)(std::lower_bound(ro.begin(), ro.end(), b) - ro.begin()) - 1;
-        for (int32_t f = first[r]; f <= last[r]; f++) {
-            if (ix->fr[(size_t)f].raw == 0) continue;
-            start[(size_t)f + 1]++;
-            if (!home[(size_t)f] && ro[(size_t)f] >= a && ro[(size_t)f + 1] <= b) home[(size_t)f] = d_out[r] + (ro[(size_t)f] - a);
-        }
-    }
-    std::vector<size_t> touched;
-    for (size_t f = 0; f < F; f++) {
-        if (start[f + 1]) touched.push_back(f);
-        start[f + 1] += start[f];
-    }
-    std::vector<int32_t> piece_range(start[F]);
-    {
-        std::vector<size_t> fill(start.begin(), start.end() - 1);
-        for (int32_t r = 0; r < n; r++)
-            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
-                if (ix->fr[(size_t)f].raw) piece_range[fill[(size_t)f]++] = r;
-    }
-    std::vector<int32_t> fstat(F, JPK_OK);
-    const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
-    for (size_t k = 0; k < touched.size();) {
-        size_t e = k;
-        uint64_t pass_raw = 0;
-        while (e < touched.size() && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || pass_raw + (uint64_t)ix->fr[touched[e]].raw <= JAM_PASS_RAW))
-            pass_raw += (uint64_t)ix->fr[touched[e++]].raw;
-        const int m = (int)(e - k);
-        size_t npieces = 0, slot_bytes = 0, stage_bytes = 0;
-        for (int i = 0; i < m; i++) {
-            const size_t f = touched[k + i];
-            npieces += start[f + 1] - start[f];
-            if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
-            stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
-        }
-        const size_t o_slots = o_tab + jpk_align(npieces * sizeof(JamGatherPiece));
-        JPK_TRY(buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, o_slots + slot_bytes));
-        if (!d_in) JPK_TRY(buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-        JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
-        std::vector<const uint8_t *> ins((size_t)m);
-        std::vector<uint8_t *> outs((size_t)m);
-        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m);
-        size_t slot = o_slots, stage = 0;
-        for (int i = 0; i < m; i++) {
-            const size_t f = touched[k + i];
-            const jpk_jam_index::Frame &fr = ix->fr[f];
-            if (d_in) ins[i] = d_in + fr.payload_off;
-            else {
-                JPK_HIP(hipMemcpyAsync(ctx->stage_in + stage, h_in + fr.payload_off, (size_t)fr.psize, hipMemcpyHostToDevice, ctx->stream));
-                ins[i] = ctx->stage_in + stage;
-                stage += jpk_align((size_t)fr.psize + 64);
-            }
-            lens[i] = fr.psize; caps[i] = (int32_t)fr.raw;
-            if (home[f]) outs[i] = home[f];
-            else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
-        }
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
-        // one batched checksum of the frames that decoded, against their header crcs
-        std::vector<int> dec;
-        std::vector<const uint8_t *> cin;
-        std::vector<int32_t> clen;
-        for (int i = 0; i < m; i++) {
-            if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
-            dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
-        }
-        if (!dec.empty()) {
-            std::vector<uint32_t> crc(dec.size());
-            JPK_TRY(jpk_checksums_device(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc));
-            JPK_HIP(hipMemcpyAsync(crc.data(), d_crc, dec.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-            for (size_t q = 0; q < dec.size(); q++)
-                if (crc[q] != ix->fr[touched[k + (size_t)dec[q]]].crc) fstat[touched[k + (size_t)dec[q]]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
-        }
-        // the pieces of the verified frames (the one a frame was decoded into in place is already where it belongs)
-        std::vector<JamGatherPiece> tab;
-        tab.reserve(npieces);
-        uint64_t words = 0, bytes = 0;
-        for (int i = 0; i < m; i++) {
-            const size_t f = touched[k + i];
-            if (fstat[f] != JPK_OK) continue;
-            const int64_t raw = ix->fr[f].raw;
-            const uint8_t *hi = home[f] ? outs[i] + raw : outs[i] + ((raw + 15) & ~(int64_t)15) + 16;
-            for (size_t q = start[f]; q < start[f + 1]; q++) {
-                const int32_t r = piece_range[q];
-                const int64_t a = std::max(ro[f], off[r]), b = std::min(ro[f + 1], off[r] + len[r]);
-                JamGatherPiece pc;
-                pc.src = outs[i] + (a - ro[f]); pc.dst = d_out[r] + (a - off[r]); pc.len = (uint64_t)(b - a); pc.word0 = words;
-                pc.src_lo = outs[i]; pc.src_hi = hi;
-                if (pc.src == pc.dst) continue;
-                words += (((uint64_t)(uintptr_t)pc.dst & 15u) + pc.len + 15u) / 16u;
-                bytes += pc.len;
-                tab.push_back(pc);
-            }
-        }
-        if (!tab.empty()) {
-            JPK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(JamGatherPiece), hipMemcpyHostToDevice, ctx->stream));
-            JPK_TRY(jpk_jam_gather_enqueue(ctx, d_tab, (uint32_t)tab.size(), words, bytes));
-            JPK_HIP(hipStreamSynchronize(ctx->stream));
-        }
-        k = e;
-    }
-    int32_t bad = -1;
-    for (size_t f : touched) if (fstat[f] != JPK_OK) { bad = (int32_t)f; break; }
-    if (bad >= 0)
-        for (int32_t r = 0; r < n; r++)
-            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
-                if (ix->fr[(size_t)f].raw && fstat[(size_t)f] != JPK_OK) { status[r] = fstat[(size_t)f]; break; }
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
-}
-
-// n and the number of pieces are the caller's: the host tables of a read that does not fit in memory end in JPK_E_ALLOC, not in an
-// exception that leaves through the C ABI
-int jam_read_run(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
-                 uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
-{
-    try {
-        return jam_read_pieces(ctx, ix, d_in, h_in, n, off, len, d_out, status, bad_frame);
-    } catch (const std::bad_alloc &) {
-        (void)hipStreamSynchronize(ctx->stream);             // nothing queued may outlive the tables it reads
-        return JPK_E_ALLOC;
-    }
-}
-
-// no range wants a byte: nothing to decode, every status JPK_OK
-bool jam_read_empty(int32_t n, const int64_t *len, int32_t *status)
-{
-    for (int32_t r = 0; r < n; r++) if (len[r] > 0) return false;
-    if (status) for (int32_t r = 0; r < n; r++) status[r] = JPK_OK;
-    return true;
-}
-
-int jam_read_result(int32_t n, const int32_t *st, int32_t *status)
-{
-    if (status) { for (int32_t r = 0; r < n; r++) status[r] = st[r]; return JPK_OK; }
-    for (int32_t r = 0; r < n; r++) if (st[r] != JPK_OK) return st[r];
-    return JPK_OK;
-}
-}  // namespace
-
-extern "C" int jpk_dev_jam_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
-{
-    JPK_ENTER(ctx);
-    if (!index || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
-    *index = nullptr;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
-    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
-}
-
-extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
-{
-    if (!index || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
-    *index = nullptr;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad);
-    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
-}
-
-extern "C" int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len)
-{
-    if (!index) return JPK_E_ARG;
-    if (frames) *frames = (int32_t)index->fr.size();
-    if (raw_len) *raw_len = index->raw_off.back();
-    if (archive_len) *archive_len = index->archive_len;
-    return JPK_OK;
-}
-
-extern "C" int jpk_jam_index_frame(const jpk_jam_index *index, int32_t k, int64_t *raw_off, int64_t *raw, int64_t *payload_off, int32_t *psize)
-{
-    if (!index || k < 0 || (size_t)k >= index->fr.size()) return JPK_E_ARG;
-    if (raw_off) *raw_off = index->raw_off[(size_t)k];
-    if (raw) *raw = index->fr[(size_t)k].raw;
-    if (payload_off) *payload_off = index->fr[(size_t)k].payload_off;
-    if (psize) *psize = index->fr[(size_t)k].psize;
-    return JPK_OK;
-}
-
-extern "C" void jpk_jam_index_destroy(jpk_jam_index *index) { delete index; }
-
-extern "C" int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
-                                uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
-{
-    // (JPK_ENTER taken apart: the argument checks come before the first device call)
-    if (!ctx) return JPK_E_ARG;
-    JPK_TRY(jam_read_check(index, d_in, in_len, n, off, len, d_out));
-    JPK_HIP(hipSetDevice(ctx->device));
-    if (bad_frame) *bad_frame = -1;
-    if (jam_read_empty(n, len, status)) return JPK_OK;
-    std::vector<int32_t> st;
-    try { st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
-    JPK_TRY(jam_read_run(ctx, index, d_in, nullptr, n, off, len, d_out, st.data(), bad_frame));
-    return jam_read_result(n, st.data(), status);
-}
-
-extern "C" int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out,
-                            int32_t *status, int32_t *bad_frame)
-{
-    JPK_TRY(jam_read_check(index, in, in_len, n, off, len, out));
-    if (bad_frame) *bad_frame = -1;
-    if (jam_read_empty(n, len, status)) return JPK_OK;
-    jpk_ctx *ctx;
-    JPK_TRY(tls_ctx(&ctx));
-    JPK_HIP(hipSetDevice(ctx->device));
-    // the ranges side by side in ctx->stage_res (a range may start at any address); only they travel back
-    std::vector<uint8_t *> d_out;
-    std::vector<int32_t> st;
-    try { d_out.resize((size_t)n); st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
-    int64_t total = 0;
-    for (int32_t r = 0; r < n; r++) total += len[r];
-    JPK_TRY(buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)total + 64));
-    total = 0;
-    for (int32_t r = 0; r < n; r++) { d_out[(size_t)r] = ctx->stage_res + total; total += len[r]; }
-    JPK_TRY(jam_read_run(ctx, index, nullptr, in, n, off, len, d_out.data(), st.data(), bad_frame));
-    // few ranges: one copy each; many small ones: one copy of all of them and the split on the host
-    if (n <= 16 || total > (64ll << 20)) {
-        for (int32_t r = 0; r < n; r++)
-            if (len[r] > 0 && st[(size_t)r] == JPK_OK) JPK_HIP(hipMemcpyAsync(out[r], d_out[(size_t)r], (size_t)len[r], hipMemcpyDeviceToHost, ctx->stream));
-        JPK_HIP(hipStreamSynchronize(ctx->stream));
-    } else {
-        std::vector<uint8_t> all;
-        try { all.resize((size_t)total); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
-        JPK_HIP(hipMemcpyAsync(all.data(), ctx->stage_res, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-        JPK_HIP(hipStreamSynchronize(ctx->stream));
-        for (int32_t r = 0; r < n; r++)
-            if (len[r] > 0 && st[(size_t)r] == JPK_OK) memcpy(out[r], all.data() + (d_out[(size_t)r] - ctx->stage_res), (size_t)len[r]);
-    }
-    return jam_read_result(n, st.data(), status);
 }

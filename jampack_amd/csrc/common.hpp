@@ -204,6 +204,22 @@ struct JpkCompressInflight {
 // moves the per-round statistics of the last suffix sort from the pinned mailbox into ctx->stats (call after a stream sync)
 void jpk_sa_stats_sync(jpk_ctx *ctx);
 
+// ---- what the archive layer (jam_archive.hip) shares with abi.hip, which defines each of them once -------
+#define JPK_ENTER(ctx)                         \
+    if (!(ctx)) return JPK_E_ARG;              \
+    JPK_HIP(hipSetDevice((ctx)->device))
+// grows the device buffer *p of ctx to at least `bytes` (its contents are lost; synchronises the stream when it grows)
+int jpk_buf_ensure(jpk_ctx *ctx, uint8_t **p, size_t *cap, size_t bytes);
+// the calling thread's context from the process-wide pool (borrowed on its first call)
+int jpk_tls_ctx(jpk_ctx **out);
+// the opening of a host-buffer entry: jpk_tls_ctx, its device current, ctx->stage_in of at least stage_in_bytes
+int jpk_host_enter(jpk_ctx **ctx, size_t stage_in_bytes);
+// the output slot that always holds the compressed form of a block of len bytes
+size_t jpk_multi_comp_cap(int32_t len);
+bool jpk_jam_block_size_ok(int32_t bs);
+// the 15-byte frame header at h, `avail` bytes from h to the end of the input: the fields, and whether they pass DecompReadBlock's checks
+bool jpk_jam_header_parse(const uint8_t *h, int64_t avail, uint32_t *crc, int32_t *psize, int32_t *block_size);
+
 // ---- stage drivers (device buffers) -----------------------------------------------------------------
 int jpk_fwd_bwt_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint8_t *d_out);
 int jpk_suffix_array_device(jpk_ctx *ctx, const uint8_t *d_t, int32_t n, int32_t *d_sa);

@@ -4,7 +4,7 @@
 //                from payload slots in scratch, organised by destination: a thread owns aligned 16-byte words of the output
 //   k_jam_gather delivers the pieces of a range read -- (source, destination, length) of decoded bytes -- organised by destination
 //                in the same way: a thread owns aligned 16-byte words of a piece's destination
-// The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress / jpk_dev_jam_read (abi.hip).
+// The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress / jpk_dev_jam_read (jam_archive.hip).
 #include "common.hpp"
 
 namespace {

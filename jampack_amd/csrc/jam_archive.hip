@@ -1,0 +1,829 @@
+// jam_archive.hip -- whole .jam archives of the C ABI (include/jampack_abi.h): the frame walks, the batched compress and decompress
+// calls of plain and stock-CLI archives with their host-buffer forms, and the index + range reads.  Host drivers only: the kernels
+// are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines and the context pool in abi.hip.
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "common.hpp"
+
+// ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
+// Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
+// in ctx->jam_scratch, the frame offsets on the host (64-bit), one k_jam_pack launch that writes the frames.  Decompress: the frame
+// walk (k_jam_walk, one launch + one read-back per JPK_JAM_PASS_FRAMES frames) and the decoded sizes (pass 1 of the batch decoder)
+// over the whole archive first -- that is what makes the capacity answer exact and leaves d_out untouched when it is too small --
+// then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out (its payload read in place in the archive),
+// one batched checksum of the outputs, and the comparison with the header crcs.  A pass holds at most JPK_JAM_PASS_FRAMES frames
+// and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
+// The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
+// the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
+// of the raw slices.  With JPK_CLI_DEDUPE the k_dd_* launches come first (raw slice -> S1' in slot B), the pass's S1' lengths are read
+// on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.
+
+// one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
+struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
+
+namespace {
+constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
+
+int jam_pass_frames(int32_t block_size)
+{
+    const uint64_t k = JAM_PASS_RAW / (uint64_t)block_size;
+    return k < (uint64_t)JPK_JAM_PASS_FRAMES ? (int)k : JPK_JAM_PASS_FRAMES;
+}
+
+// the checks of the frame walk beyond its header (k_jam_walk / jam_walk_host): the payload declares at least the BWT trailer and at
+// most BlockSize raw bytes (the reference decodes into buffers of 1.05 x BlockSize, jampack.cpp:156-159) -- for a frame of the stock
+// CLI, whose entropy-decoded bytes are the output of its pre-stages (filter headers and LZ tokens add bytes), at most the reference's
+// stage buffers, 1.05 x BlockSize + 4096 (jampack.cpp:156), as jpk_jam_cli_block_read has them
+int32_t jam_cli_cap(int32_t block_size) { return (int32_t)((int64_t)((double)block_size * 1.05) + 4096); }
+bool jam_decoded_ok(int64_t decoded, int32_t block_size, bool cli)
+{
+    return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= (cli ? jam_cli_cap(block_size) : block_size);
+}
+
+// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); cli: frames of the
+// stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders)
+void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
+{
+    *bad = -1;
+    int64_t o = 0;
+    while (o < in_len) {
+        JamFrame f;
+        f.payload_off = o + JPK_JAM_HEADER_BYTES;
+        int64_t decoded = 0;
+        // a bad header (1..14 trailing bytes are one), bad chunk headers in the payload, or a payload that declares too much
+        if (!jpk_jam_header_parse(in + o, in_len - o, &f.crc, &f.psize, &f.block_size) ||
+            jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size, cli)) {
+            *bad = (int32_t)fr.size();
+            return;
+        }
+        f.raw = decoded - JPK_TRAILER_BYTES;
+        fr.push_back(f);
+        o = f.payload_off + f.psize;
+    }
+}
+
+// the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
+int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
+{
+    *bad = -1;
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
+    JamWalkFrame *d_tab = reinterpret_cast<JamWalkFrame *>(ctx->jam_scratch);
+    std::vector<JamWalkFrame> h(JPK_JAM_PASS_FRAMES);
+    std::vector<const uint8_t *> ins;
+    std::vector<int32_t> lens, st;
+    std::vector<int64_t> dec;
+    uint64_t o = 0;
+    while (o < (uint64_t)in_len) {
+        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail));
+        JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
+        uint32_t m[4];
+        JPK_TRY(jpk_read_mail(ctx, m, 4));                   // synchronises: the table is on the host too
+        const int n = (int)m[0];
+        ins.resize((size_t)n); lens.resize((size_t)n); st.resize((size_t)n); dec.resize((size_t)n);
+        for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
+        JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
+        for (int i = 0; i < n; i++) {
+            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], h[i].block_size, cli)) { *bad = (int32_t)fr.size(); return JPK_OK; }
+            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, h[i].block_size, dec[i] - JPK_TRAILER_BYTES});
+        }
+        if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
+        o = ((uint64_t)m[3] << 32) | m[2];
+    }
+    return JPK_OK;
+}
+
+// items [k, e) of n form the pass that starts at item k: at most JPK_JAM_PASS_FRAMES of them and JAM_PASS_RAW bytes of weight(i) in
+// all (one item at least)
+template <class W> size_t jam_pass_end(size_t n, size_t k, W weight)
+{
+    size_t e = k;
+    uint64_t sum = 0;
+    while (e < n && e - k < (size_t)JPK_JAM_PASS_FRAMES && (e == k || sum + (uint64_t)weight(e) <= JAM_PASS_RAW)) sum += (uint64_t)weight(e++);
+    return e;
+}
+
+// what a frame weighs in a decompress pass and in the size answers: its raw bytes, or (cli: known only behind its last stage) its BlockSize
+int64_t jam_weight(const JamFrame &f, bool cli) { return cli ? f.block_size : f.raw; }
+size_t jam_pass_end(const std::vector<JamFrame> &fr, size_t k, bool cli)
+{
+    return jam_pass_end(fr.size(), k, [&](size_t i) { return jam_weight(fr[i], cli); });
+}
+int64_t jam_sum(const std::vector<JamFrame> &fr, size_t k, size_t e, bool cli)
+{
+    int64_t sum = 0;
+    for (size_t i = k; i < e; i++) sum += jam_weight(fr[i], cli);
+    return sum;
+}
+
+// the crcs of n device segments on the host: one batched checksum into d_crc, one read-back, synchronised
+int jam_crcs(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *len, uint32_t *d_crc, uint32_t *crc)
+{
+    JPK_TRY(jpk_checksums_device(ctx, n, d_in, len, d_crc));
+    JPK_HIP(hipMemcpyAsync(crc, d_crc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    return JPK_OK;
+}
+
+// appends the piece src[0..len) -> dst (readable around src: [lo, hi)) to tab; *words = the destination words of the pieces so far
+void jam_piece_add(std::vector<JamGatherPiece> &tab, uint64_t *words, const uint8_t *src, uint8_t *dst, uint64_t len, const uint8_t *lo, const uint8_t *hi)
+{
+    tab.push_back(JamGatherPiece{src, dst, len, *words, lo, hi});
+    *words += (((uint64_t)(uintptr_t)dst & 15u) + len + 15u) / 16u;
+}
+
+// delivers the pieces of tab (through d_tab) with one launch, synchronised
+int jam_gather(jpk_ctx *ctx, JamGatherPiece *d_tab, const std::vector<JamGatherPiece> &tab, uint64_t words, uint64_t bytes)
+{
+    if (tab.empty()) return JPK_OK;
+    JPK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(JamGatherPiece), hipMemcpyHostToDevice, ctx->stream));
+    JPK_TRY(jpk_jam_gather_enqueue(ctx, d_tab, (uint32_t)tab.size(), words, bytes));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    return JPK_OK;
+}
+
+// what the decompress entries report.  zero: on entry; stop: frame f failed with rc, len verified bytes in front of it; done: every
+// frame the walk found is out, and a walk that stopped at a bad frame makes the call JPK_E_CORRUPT
+struct JamResult { int64_t *out_len; int32_t *frames, *bad_frame; };
+void jam_result_zero(const JamResult &r)
+{
+    *r.out_len = 0;
+    if (r.frames) *r.frames = 0;
+    if (r.bad_frame) *r.bad_frame = -1;
+}
+int jam_result_stop(const JamResult &r, int64_t len, int32_t f, int rc)
+{
+    *r.out_len = len;
+    if (r.frames) *r.frames = f;
+    if (r.bad_frame) *r.bad_frame = f;
+    return rc;
+}
+int jam_result_done(const JamResult &r, int64_t len, size_t frames, int32_t bad)
+{
+    *r.out_len = len;
+    if (r.frames) *r.frames = (int32_t)frames;
+    if (bad < 0) return JPK_OK;
+    if (r.bad_frame) *r.bad_frame = bad;
+    return JPK_E_CORRUPT;
+}
+
+// what the batch compress is given for a raw slice of len bytes: the slice, or its S4 (cli; prestage.cpp) -- and the payload it can give
+int32_t jam_bwt_len(int32_t len, bool cli) { return cli ? (int32_t)jpk_cli_stages_bound(len) : len; }
+int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (int64_t)jpk_multi_comp_cap(jam_bwt_len(len, cli)); }
+
+// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
+// of the stock CLI
+int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
+                      int32_t in_flight, bool cli, uint32_t flags)
+{
+    const int n = (int)((len + block_size - 1) / block_size);
+    std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
+    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n);
+    std::vector<int32_t> lens((size_t)n), blens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+    const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
+    size_t need = o_slots;
+    for (int i = 0; i < n; i++) {
+        ins[i] = d_in + (int64_t)i * block_size;
+        lens[i] = (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size);
+        blens[i] = jam_bwt_len(lens[i], cli);
+        caps[i] = (int32_t)jpk_multi_comp_cap(blens[i]);
+        need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
+        if (cli) need += 2 * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
+    }
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(ctx->jam_scratch + o_frames);
+    size_t off = o_slots;
+    for (int i = 0; i < n; i++) {
+        slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64);
+        bwt_in[i] = ins[i];
+        if (cli) {
+            sa[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
+            sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
+            bwt_in[i] = sb[i];
+        }
+    }
+    // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
+    JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
+    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
+    JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
+    for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
+    std::vector<JamPackFrame> fr((size_t)n);
+    uint64_t pos = 0;
+    for (int i = 0; i < n; i++) {
+        fr[i].slot = slots[i]; fr[i].off = pos; fr[i].psize = outl[i]; fr[i].pad = 0;
+        pos += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)outl[i];
+    }
+    if ((int64_t)pos > out_room) return JPK_E_CAPACITY;
+    JPK_HIP(hipMemcpyAsync(d_frames, fr.data(), (size_t)n * sizeof(JamPackFrame), hipMemcpyHostToDevice, ctx->stream));
+    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, block_size, d_out, pos));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    *pass_len = (int64_t)pos;
+    return JPK_OK;
+}
+}  // namespace
+
+namespace {
+int64_t jam_compress_bound(int64_t in_len, int32_t block_size, bool cli)
+{
+    if (in_len < 0 || !jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;
+    const int64_t full = in_len / block_size, rest = in_len % block_size;
+    return full * jam_frame_bound(block_size, cli) + (rest ? jam_frame_bound((int32_t)rest, cli) : 0);
+}
+
+int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                     int32_t in_flight, bool cli, uint32_t flags = 0u)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
+    *out_len = 0;
+    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
+    int64_t pos = 0;
+    for (int64_t o = 0; o < in_len; o += step) {
+        int64_t n = 0;
+        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli, flags));
+        pos += n;
+    }
+    *out_len = pos;
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, false); }
+extern "C" int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, true); }
+
+extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                    int32_t in_flight)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, false);
+}
+
+extern "C" int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                        int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true);
+}
+
+extern "C" int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                           int64_t *out_len, int32_t in_flight, uint32_t flags)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true, flags);
+}
+
+extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                      int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    const JamResult res{out_len, frames, bad_frame};
+    jam_result_zero(res);
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
+    const int64_t need = jam_sum(fr, 0, fr.size(), false);
+    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }         // the size query (out_cap = 0) ends here
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * 4));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, false);
+        const int n = (int)(e - k);
+        std::vector<const uint8_t *> ins((size_t)n);
+        std::vector<uint8_t *> outs((size_t)n);
+        std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+        std::vector<uint32_t> crc((size_t)n);
+        int64_t o = pos;
+        for (int i = 0; i < n; i++) {
+            const JamFrame &f = fr[k + i];
+            ins[i] = d_in + f.payload_off; lens[i] = f.psize;
+            outs[i] = d_out + o; caps[i] = (int32_t)f.raw;
+            o += f.raw;
+        }
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
+        int fail = n, rc = JPK_OK;
+        for (int i = 0; i < n && fail == n; i++) if (st[i] != JPK_OK || outl[i] != caps[i]) { fail = i; rc = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; }
+        if (fail > 0) {
+            JPK_TRY(jam_crcs(ctx, fail, outs.data(), caps.data(), d_crc, crc.data()));
+            for (int i = 0; i < fail; i++) if (crc[i] != fr[k + i].crc) { fail = i; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
+        }
+        for (int i = 0; i < fail; i++) pos += caps[i];
+        if (fail < n) return jam_result_stop(res, pos, (int32_t)(k + fail), rc);
+        k = e;
+    }
+    return jam_result_done(res, pos, fr.size(), bad);
+}
+
+namespace {
+// jpk_jam_frames / jpk_jam_cli_frames: the host walk, *len = the raw bytes (cli: the sum of BlockSize) of the frames it found
+int jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *len, int32_t *bad_frame, bool cli)
+{
+    if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad, cli);
+    if (frames) *frames = (int32_t)fr.size();
+    if (len) *len = jam_sum(fr, 0, fr.size(), cli);
+    if (bad_frame) *bad_frame = bad;
+    return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
+}
+
+int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli,
+                      uint32_t flags = 0u)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;
+    *out_len = 0;
+    jpk_ctx *ctx;
+    JPK_TRY(jpk_host_enter(&ctx, 0));
+    // staged one pass at a time: the device call makes the same passes, so the frames are those of one call over the whole input
+    const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
+    int64_t pos = 0;
+    for (int64_t o = 0; o < in_len; o += step) {
+        const int64_t len = std::min(step, in_len - o), bound = jam_compress_bound(len, block_size, cli);
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 64));
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
+        int64_t n = 0;
+        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli, flags));
+        if (n > out_cap - pos) return JPK_E_CAPACITY;
+        JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        pos += n;
+    }
+    *out_len = pos;
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame)
+{
+    return jam_frames(in, in_len, frames, raw_len, bad_frame, false);
+}
+
+extern "C" int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame)
+{
+    return jam_frames(in, in_len, frames, raw_bound, bad_frame, true);
+}
+
+extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, false);
+}
+
+extern "C" int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true);
+}
+
+extern "C" int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
+                                       uint32_t flags)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true, flags);
+}
+
+// ---- whole archives of the stock CLI: every frame through the four pre-stage decoders on the device (prestage_dev.hip) -------------
+// Per pass: jpk_dev_blocks_decompress into slot A of every frame, then Lz77 A -> B, Lpx B -> A, Filters A -> B, Lz77 B -> A (the
+// order of Jampack::Decomp(), jampack.cpp:51-57), one batched checksum of the A slots against the header crcs, one k_jam_gather
+// launch that packs the verified frames back to back into d_out.  A frame's raw size is known only behind its last stage; every stage
+// works on the frames in front of the first one that has failed so far, which is where the call stops.  A pass holds at most
+// JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW bytes of BlockSize.
+namespace {
+// the first block of st[0..m) that failed (*rc = its status), m when none did.  A stage that runs out of its slot (1.05 x BlockSize +
+// 4096, or BlockSize behind the last stage) met a bad frame: JPK_E_CAPACITY is kept for the caller's out_cap.
+int jam_cli_cut(const std::vector<int32_t> &st, int m, int *rc)
+{
+    for (int i = 0; i < m; i++) if (st[(size_t)i] != JPK_OK) { *rc = st[(size_t)i] == JPK_E_CAPACITY ? JPK_E_CORRUPT : st[(size_t)i]; return i; }
+    return m;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                          int32_t *frames, int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    const JamResult res{out_len, frames, bad_frame};
+    jam_result_zero(res);
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, true));
+    const int64_t raw_bound = jam_sum(fr, 0, fr.size(), true);
+    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, true);
+        const int n = (int)(e - k);
+        std::vector<const uint8_t *> ins((size_t)n), a_in((size_t)n), b_in((size_t)n);
+        std::vector<uint8_t *> a((size_t)n), b((size_t)n);
+        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), l0((size_t)n), l1((size_t)n), l3((size_t)n), raw((size_t)n), st((size_t)n);
+        std::vector<size_t> slot((size_t)n);
+        size_t need = o_slots;
+        for (int i = 0; i < n; i++) {
+            const JamFrame &f = fr[k + i];
+            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size;
+            caps[i] = jam_cli_cap(f.block_size);
+            slot[i] = jpk_align((size_t)caps[i] + 64);           // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            need += 2 * slot[i];
+        }
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
+        size_t off = o_slots;
+        for (int i = 0; i < n; i++) {
+            a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i];
+            a_in[i] = a[i]; b_in[i] = b[i];
+        }
+        int rc = JPK_OK;
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), a.data(), caps.data(), l0.data(), st.data()));   // Ans::Decode + InverseBwt
+        int m = jam_cli_cut(st, n, &rc);
+        if (m) {
+            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, a_in.data(), l0.data(), b.data(), caps.data(), l1.data(), st.data()));   // Lz->Decompress
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, b_in.data(), l1.data(), a.data(), st.data()));                             // LocalModel->Decode
+        if (m) {
+            JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, a_in.data(), l1.data(), b.data(), caps.data(), l3.data(), st.data()));    // Filter->Decode
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) {
+            // Lz->Decompress; a frame that decodes to more than its BlockSize is a bad frame
+            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, b_in.data(), l3.data(), a.data(), bsz.data(), raw.data(), st.data()));
+            m = jam_cli_cut(st, m, &rc);
+        }
+        if (m) {
+            std::vector<uint32_t> crc((size_t)m);
+            JPK_TRY(jam_crcs(ctx, m, a_in.data(), raw.data(), d_crc, crc.data()));
+            for (int i = 0; i < m; i++) if (crc[i] != fr[k + i].crc) { m = i; rc = JPK_E_CORRUPT; break; }      // "Detected corrupt block!", jampack.cpp:59
+        }
+        int64_t sum = 0;
+        for (int i = 0; i < m; i++) sum += raw[i];
+        if (sum > out_cap - pos) {
+            *out_len = raw_bound;
+            if (frames) *frames = (int32_t)k;
+            return JPK_E_CAPACITY;
+        }
+        std::vector<JamGatherPiece> pieces;
+        uint64_t words = 0;
+        int64_t o = pos;
+        for (int i = 0; i < m; i++) {
+            if (raw[i] == 0) continue;
+            jam_piece_add(pieces, &words, a[i], d_out + o, (uint64_t)raw[i], a[i], a[i] + slot[i]);
+            o += raw[i];
+        }
+        JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, (uint64_t)sum));
+        if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
+        pos += sum;
+        if (m < n) return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        k = e;
+    }
+    return jam_result_done(res, pos, fr.size(), bad);
+}
+
+namespace {
+// jpk_jam_decompress / jpk_jam_cli_decompress: the archive staged one pass at a time -- the pass's frames are an archive of their own
+// for the device call
+int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame, bool cli)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    const JamResult res{out_len, frames, bad_frame};
+    jam_result_zero(res);
+    jpk_ctx *ctx;
+    JPK_TRY(jpk_host_enter(&ctx, 0));
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad, cli);
+    // plain: the raw bytes, known from the walk -- the capacity answer comes first and nothing is touched; cli: the raw bound
+    const int64_t total = jam_sum(fr, 0, fr.size(), cli);
+    if (!cli && total > out_cap) { *out_len = total; return JPK_E_CAPACITY; }
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, cli);
+        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+        // the pass decodes into its raw bytes; cli: into what is left of out_cap, at most the pass's BlockSize bytes
+        int64_t room = jam_sum(fr, k, e, cli);
+        if (cli) room = std::min(room, out_cap - pos);
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+        int64_t n = 0;
+        int32_t nf = 0, bf = -1;
+        const int rc = cli ? jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
+                           : jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
+        if (cli && rc == JPK_E_CAPACITY) {
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            *out_len = total;
+            if (frames) *frames = (int32_t)k;
+            return rc;
+        }
+        if (n > 0 && (rc == JPK_OK || rc == JPK_E_CORRUPT)) JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        if (rc != JPK_OK) {
+            // the pass's own report, its frame numbers counted from the archive's start
+            if (rc == JPK_E_CORRUPT) *out_len = pos + n;
+            if (frames) *frames = (int32_t)k + nf;
+            if (bad_frame && bf >= 0) *bad_frame = (int32_t)k + bf;
+            return rc;
+        }
+        pos += n;
+        k = e;
+    }
+    return jam_result_done(res, pos, fr.size(), bad);
+}
+}  // namespace
+
+extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
+{
+    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, false);
+}
+
+extern "C" int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
+{
+    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, true);
+}
+
+// ---- range reads of a .jam archive: jpk_jam_index + jpk_dev_jam_read / jpk_jam_read -----------------------------------------------
+// The index is the frame table of the walks with the 64-bit prefix sum of the raw sizes.  A read maps every range to the frames it
+// touches, decodes each touched frame ONCE -- in place in the first range that contains it whole, otherwise into a padded slot of
+// ctx->jam_scratch -- in passes with the limits of the archive calls, checks every decoded frame against its header crc, and delivers
+// the pieces of the verified frames with one k_jam_gather launch per pass.  A frame no range touches is neither decoded nor checked.
+struct jpk_jam_index {
+    std::vector<JamFrame> fr;
+    std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
+    int64_t archive_len = 0;
+    int32_t bad = -1;
+};
+
+namespace {
+jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad)
+{
+    jpk_jam_index *ix = new (std::nothrow) jpk_jam_index;
+    if (!ix) return nullptr;
+    try {
+        ix->fr = fr;
+        ix->raw_off.reserve(fr.size() + 1);
+    } catch (const std::bad_alloc &) { delete ix; return nullptr; }
+    int64_t raw = 0;
+    for (const JamFrame &f : fr) {
+        ix->raw_off.push_back(raw);
+        raw += f.raw;
+    }
+    ix->raw_off.push_back(raw);
+    ix->archive_len = in_len;
+    ix->bad = bad;
+    return ix;
+}
+
+// the argument checks of both read entries: nothing is touched before they pass
+int jam_read_check(const jpk_jam_index *ix, const void *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out)
+{
+    if (!ix || n < 0 || in_len != ix->archive_len || (n > 0 && (!off || !len || !out))) return JPK_E_ARG;
+    const int64_t raw_len = ix->raw_off.back();
+    for (int32_t r = 0; r < n; r++) {
+        if (off[r] < 0 || len[r] < 0 || off[r] > raw_len || len[r] > raw_len - off[r]) return JPK_E_ARG;
+        if (len[r] > 0 && (!out[r] || !in)) return JPK_E_ARG;
+    }
+    return JPK_OK;
+}
+
+// The read itself.  The archive is d_in (HBM) or, when d_in is NULL, h_in (host memory: the payloads of a pass's frames are staged
+// through ctx->stage_in); d_out[] are device buffers in both cases.  status has n entries.
+int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
+                    uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    const size_t F = ix->fr.size();
+    const std::vector<int64_t> &ro = ix->raw_off;
+    // frames [first[r], last[r]] of range r; pieces per frame (a piece = the part of one frame one range wants); the in-place home of
+    // a frame: inside the first range that contains it whole
+    std::vector<int32_t> first((size_t)n, -1), last((size_t)n, -1);
+    std::vector<size_t> start(F + 1, 0);
+    std::vector<uint8_t *> home(F, nullptr);
+    for (int32_t r = 0; r < n; r++) {
+        status[r] = JPK_OK;
+        if (len[r] == 0) continue;
+        const int64_t a = off[r], b = a + len[r];
+        first[r] = (int32_t)(std::upper_bound(ro.begin(), ro.end(), a) - ro.begin()) - 1;
+        last[r] = (int32_t)(std::lower_bound(ro.begin(), ro.end(), b) - ro.begin()) - 1;
+        for (int32_t f = first[r]; f <= last[r]; f++) {
+            if (ix->fr[(size_t)f].raw == 0) continue;
+            start[(size_t)f + 1]++;
+            if (!home[(size_t)f] && ro[(size_t)f] >= a && ro[(size_t)f + 1] <= b) home[(size_t)f] = d_out[r] + (ro[(size_t)f] - a);
+        }
+    }
+    std::vector<size_t> touched;
+    for (size_t f = 0; f < F; f++) {
+        if (start[f + 1]) touched.push_back(f);
+        start[f + 1] += start[f];
+    }
+    std::vector<int32_t> piece_range(start[F]);
+    {
+        std::vector<size_t> fill(start.begin(), start.end() - 1);
+        for (int32_t r = 0; r < n; r++)
+            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
+                if (ix->fr[(size_t)f].raw) piece_range[fill[(size_t)f]++] = r;
+    }
+    std::vector<int32_t> fstat(F, JPK_OK);
+    const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    for (size_t k = 0; k < touched.size();) {
+        const size_t e = jam_pass_end(touched.size(), k, [&](size_t i) { return ix->fr[touched[i]].raw; });
+        const int m = (int)(e - k);
+        size_t npieces = 0, slot_bytes = 0, stage_bytes = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            npieces += start[f + 1] - start[f];
+            if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
+        }
+        const size_t o_slots = o_tab + jpk_align(npieces * sizeof(JamGatherPiece));
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, o_slots + slot_bytes));
+        if (!d_in) JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+        JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
+        std::vector<const uint8_t *> ins((size_t)m);
+        std::vector<uint8_t *> outs((size_t)m);
+        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m);
+        size_t slot = o_slots, stage = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            const JamFrame &fr = ix->fr[f];
+            if (d_in) ins[i] = d_in + fr.payload_off;
+            else {
+                JPK_HIP(hipMemcpyAsync(ctx->stage_in + stage, h_in + fr.payload_off, (size_t)fr.psize, hipMemcpyHostToDevice, ctx->stream));
+                ins[i] = ctx->stage_in + stage;
+                stage += jpk_align((size_t)fr.psize + 64);
+            }
+            lens[i] = fr.psize; caps[i] = (int32_t)fr.raw;
+            if (home[f]) outs[i] = home[f];
+            else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
+        }
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
+        // one batched checksum of the frames that decoded, against their header crcs
+        std::vector<int> dec;
+        std::vector<const uint8_t *> cin;
+        std::vector<int32_t> clen;
+        for (int i = 0; i < m; i++) {
+            if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
+            dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
+        }
+        if (!dec.empty()) {
+            std::vector<uint32_t> crc(dec.size());
+            JPK_TRY(jam_crcs(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc, crc.data()));
+            for (size_t q = 0; q < dec.size(); q++)
+                if (crc[q] != ix->fr[touched[k + (size_t)dec[q]]].crc) fstat[touched[k + (size_t)dec[q]]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
+        }
+        // the pieces of the verified frames (the one a frame was decoded into in place is already where it belongs)
+        std::vector<JamGatherPiece> tab;
+        tab.reserve(npieces);
+        uint64_t words = 0, bytes = 0;
+        for (int i = 0; i < m; i++) {
+            const size_t f = touched[k + i];
+            if (fstat[f] != JPK_OK) continue;
+            const int64_t raw = ix->fr[f].raw;
+            const uint8_t *hi = home[f] ? outs[i] + raw : outs[i] + ((raw + 15) & ~(int64_t)15) + 16;
+            for (size_t q = start[f]; q < start[f + 1]; q++) {
+                const int32_t r = piece_range[q];
+                const int64_t a = std::max(ro[f], off[r]), b = std::min(ro[f + 1], off[r] + len[r]);
+                const uint8_t *src = outs[i] + (a - ro[f]);
+                uint8_t *dst = d_out[r] + (a - off[r]);
+                if (src == dst) continue;
+                jam_piece_add(tab, &words, src, dst, (uint64_t)(b - a), outs[i], hi);
+                bytes += (uint64_t)(b - a);
+            }
+        }
+        JPK_TRY(jam_gather(ctx, d_tab, tab, words, bytes));
+        k = e;
+    }
+    int32_t bad = -1;
+    for (size_t f : touched) if (fstat[f] != JPK_OK) { bad = (int32_t)f; break; }
+    if (bad >= 0)
+        for (int32_t r = 0; r < n; r++)
+            for (int32_t f = first[r]; f >= 0 && f <= last[r]; f++)
+                if (ix->fr[(size_t)f].raw && fstat[(size_t)f] != JPK_OK) { status[r] = fstat[(size_t)f]; break; }
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+// n and the number of pieces are the caller's: the host tables of a read that does not fit in memory end in JPK_E_ALLOC, not in an
+// exception that leaves through the C ABI
+int jam_read_run(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, int32_t n, const int64_t *off, const int64_t *len,
+                 uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    try {
+        return jam_read_pieces(ctx, ix, d_in, h_in, n, off, len, d_out, status, bad_frame);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);             // nothing queued may outlive the tables it reads
+        return JPK_E_ALLOC;
+    }
+}
+
+// no range wants a byte: nothing to decode, every status JPK_OK
+bool jam_read_empty(int32_t n, const int64_t *len, int32_t *status)
+{
+    for (int32_t r = 0; r < n; r++) if (len[r] > 0) return false;
+    if (status) for (int32_t r = 0; r < n; r++) status[r] = JPK_OK;
+    return true;
+}
+
+int jam_read_result(int32_t n, const int32_t *st, int32_t *status)
+{
+    if (status) { for (int32_t r = 0; r < n; r++) status[r] = st[r]; return JPK_OK; }
+    for (int32_t r = 0; r < n; r++) if (st[r] != JPK_OK) return st[r];
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!index || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
+    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    if (!index || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad);
+    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len)
+{
+    if (!index) return JPK_E_ARG;
+    if (frames) *frames = (int32_t)index->fr.size();
+    if (raw_len) *raw_len = index->raw_off.back();
+    if (archive_len) *archive_len = index->archive_len;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_frame(const jpk_jam_index *index, int32_t k, int64_t *raw_off, int64_t *raw, int64_t *payload_off, int32_t *psize)
+{
+    if (!index || k < 0 || (size_t)k >= index->fr.size()) return JPK_E_ARG;
+    if (raw_off) *raw_off = index->raw_off[(size_t)k];
+    if (raw) *raw = index->fr[(size_t)k].raw;
+    if (payload_off) *payload_off = index->fr[(size_t)k].payload_off;
+    if (psize) *psize = index->fr[(size_t)k].psize;
+    return JPK_OK;
+}
+
+extern "C" void jpk_jam_index_destroy(jpk_jam_index *index) { delete index; }
+
+extern "C" int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                                uint8_t *const *d_out, int32_t *status, int32_t *bad_frame)
+{
+    // (JPK_ENTER taken apart: the argument checks come before the first device call)
+    if (!ctx) return JPK_E_ARG;
+    JPK_TRY(jam_read_check(index, d_in, in_len, n, off, len, d_out));
+    JPK_HIP(hipSetDevice(ctx->device));
+    if (bad_frame) *bad_frame = -1;
+    if (jam_read_empty(n, len, status)) return JPK_OK;
+    std::vector<int32_t> st;
+    try { st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+    JPK_TRY(jam_read_run(ctx, index, d_in, nullptr, n, off, len, d_out, st.data(), bad_frame));
+    return jam_read_result(n, st.data(), status);
+}
+
+extern "C" int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out,
+                            int32_t *status, int32_t *bad_frame)
+{
+    JPK_TRY(jam_read_check(index, in, in_len, n, off, len, out));
+    if (bad_frame) *bad_frame = -1;
+    if (jam_read_empty(n, len, status)) return JPK_OK;
+    jpk_ctx *ctx;
+    JPK_TRY(jpk_host_enter(&ctx, 0));
+    // the ranges side by side in ctx->stage_res (a range may start at any address); only they travel back
+    std::vector<uint8_t *> d_out;
+    std::vector<int32_t> st;
+    try { d_out.resize((size_t)n); st.resize((size_t)n); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+    int64_t total = 0;
+    for (int32_t r = 0; r < n; r++) total += len[r];
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)total + 64));
+    total = 0;
+    for (int32_t r = 0; r < n; r++) { d_out[(size_t)r] = ctx->stage_res + total; total += len[r]; }
+    JPK_TRY(jam_read_run(ctx, index, nullptr, in, n, off, len, d_out.data(), st.data(), bad_frame));
+    // few ranges: one copy each; many small ones: one copy of all of them and the split on the host
+    if (n <= 16 || total > (64ll << 20)) {
+        for (int32_t r = 0; r < n; r++)
+            if (len[r] > 0 && st[(size_t)r] == JPK_OK) JPK_HIP(hipMemcpyAsync(out[r], d_out[(size_t)r], (size_t)len[r], hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+    } else {
+        std::vector<uint8_t> all;
+        try { all.resize((size_t)total); } catch (const std::bad_alloc &) { return JPK_E_ALLOC; }
+        JPK_HIP(hipMemcpyAsync(all.data(), ctx->stage_res, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        for (int32_t r = 0; r < n; r++)
+            if (len[r] > 0 && st[(size_t)r] == JPK_OK) memcpy(out[r], all.data() + (d_out[(size_t)r] - ctx->stage_res), (size_t)len[r]);
+    }
+    return jam_read_result(n, st.data(), status);
+}

@@ -187,6 +187,30 @@ def test_corrupt_frame_stops_there(gpu, what):
         assert e.value.status == -3
 
 
+@pytest.mark.parametrize("damage", ["crc", "trailing"])
+def test_bad_frame_in_the_second_pass(gpu, oracle, damage):
+    """130 frames of 1 000 bytes: the host form stages 128 frames, then 2, and numbers the bad frame from the archive's start"""
+    torch, jam, ctx = gpu
+    data = jam.corpus.make("text", 130 * 1000, 67)
+    a = _archive(oracle, data, MiB, 1000)
+    s = _starts(a)
+    assert len(s) == 130
+    if damage == "crc":
+        bad, k = a.copy(), 129
+        bad[s[k] + 3] ^= 1
+    else:
+        bad, k = np.concatenate([a, np.full(7, 0x5A, dtype=np.uint8)]), 130
+    host = np.zeros(len(data), dtype=np.uint8)
+    n, hf, hb = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    assert jam.lib().jpk_jam_decompress(bad.ctypes.data, len(bad), host.ctypes.data, len(data), C.byref(n), C.byref(hf), C.byref(hb)) == -3
+    assert (n.value, hf.value, hb.value) == (k * 1000, k, k)
+    assert np.array_equal(host[: k * 1000], data[: k * 1000])
+    _, d_a = _dev(torch, bad, lead=1)
+    out = torch.full((len(data),), SENT, dtype=torch.uint8, device="cuda")
+    assert ctx.jam_decompress(d_a, len(bad), out.data_ptr(), len(data), check=False) == (k * 1000, k, k, -3)
+    assert np.array_equal(out[: k * 1000].cpu().numpy(), data[: k * 1000])
+
+
 def test_device_walk_agrees_with_host_walk(gpu, oracle):
     torch, jam, ctx = gpu
     data = jam.corpus.make("text", 4 * 6000 + 2345, 71)

@@ -123,6 +123,48 @@ def test_capacity_exact_and_one_byte_short(gpu, arch40):
     assert (out[len(exp) - 1:] == SENT).all()
 
 
+@pytest.fixture(scope="module")
+def arch130(gpu):
+    """130 one-frame archives of 1 000 bytes each, BlockSize 1 MiB, back to back: (archive, frame starts, input)"""
+    _, jam, _ = gpu
+    data = jam.corpus.make("text", 130 * 1000, 99)
+    parts = [jam.jam_cli_block_write(data[o: o + 1000], MiB) for o in range(0, len(data), 1000)]
+    return np.concatenate(parts), np.cumsum([0] + [len(p) for p in parts]).tolist(), data
+
+
+def _host(jam, a, cap):
+    """jpk_jam_cli_decompress with `cap` bytes of output -> (output buffer, out_len, frames, bad, status)"""
+    import ctypes as C
+    out = np.full(max(cap, 1), SENT, dtype=np.uint8)
+    n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+    rc = jam.lib().jpk_jam_cli_decompress(a.ctypes.data, len(a), out.ctypes.data, cap, C.byref(n), C.byref(nf), C.byref(bf))
+    return out, n.value, nf.value, bf.value, rc
+
+
+@pytest.mark.parametrize("damage", ["crc", "trailing", "capacity"])
+def test_second_pass_of_130_frames(gpu, arch130, damage):
+    """the host form stages 128 frames, then 2: a bad frame there is numbered from the archive's start, and a pass that does not fit
+    reports the frame it starts at"""
+    _, jam, _ = gpu
+    a, starts, data = arch130
+    assert jam.jam_cli_frames(a) == (130, 130 * MiB, -1)
+    if damage == "capacity":
+        _, n, nf, bf, rc = _host(jam, a, len(data) - 1)
+        assert (rc, n, nf) == (E_CAPACITY, 130 * MiB, 128)
+        return
+    if damage == "crc":
+        b, k = a.copy(), 129
+        b[starts[k] + 3] ^= 1
+    else:
+        b, k = np.concatenate([a, np.full(7, 0x5A, dtype=np.uint8)]), 130
+    out, n, nf, bf, rc = _host(jam, b, len(data))
+    assert (rc, n, nf, bf) == (E_CORRUPT, k * 1000, k, k)
+    assert np.array_equal(out[: n], data[: n])
+    got, nf, bf, rc, n, guard = _dev(gpu, b, len(data))
+    assert (rc, n, nf, bf) == (E_CORRUPT, k * 1000, k, k) and guard
+    assert np.array_equal(got, data[: n])
+
+
 def test_empty_archive(gpu):
     _, jam, _ = gpu
     e = np.zeros(0, dtype=np.uint8)
