@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "prestage_rules.hpp"
 
 // Independent blocks run on separate contexts (= HIP streams).  ROCm multiplexes streams onto GPU_MAX_HW_QUEUES
 // hardware queues, round robin in creation order (default 4: tools/conctest.hip shows exactly four kernels at a time whatever
@@ -1704,25 +1705,6 @@ extern "C" int jpk_ans_decode(const uint8_t *in, int32_t in_len, uint8_t *out, i
     return JPK_OK;
 }
 
-namespace {
-// LEB128 "with carry" (utils.cpp:70-90), host side; returns bytes consumed or -1
-int leb_host(uint32_t *v, const uint8_t *b, int64_t avail)
-{
-    static const uint32_t C[4] = {127u, 16510u, 2113661u, 270549116u};
-    int d = 0;
-    uint32_t x = 0;
-    while (d < avail && !(b[d] & 0x80)) {
-        if (d >= 4) return -1;
-        x = (x << 7) | b[d++];
-    }
-    if (d >= avail) return -1;
-    x = (x << 7) | (b[d] & 0x7fu);
-    if (d > 0) x += C[d - 1];
-    *v = x;
-    return d + 1;
-}
-}  // namespace
-
 extern "C" int jpk_ans_decoded_size(const uint8_t *in, int32_t in_len, int64_t *decoded_len, int32_t *chunks)
 {
     if (!decoded_len || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
@@ -1732,7 +1714,7 @@ extern "C" int jpk_ans_decoded_size(const uint8_t *in, int32_t in_len, int64_t *
         int64_t fsum = 0;
         uint32_t v = 0, olen = 0;
         for (int s = 0; s < 259; s++) {                 // 256 frequencies, olen, clen, rlen (ans.cpp:272-302)
-            const int n = leb_host(&v, in + ip, (int64_t)in_len - ip);
+            const int n = pre::leb_read(in + ip, (int64_t)in_len - ip, &v);
             if (n < 0) return JPK_E_CORRUPT;
             ip += n;
             if (s < 256) { if (v > (uint32_t)JPK_ANS_CHUNK) return JPK_E_CORRUPT; fsum += v; }

@@ -3,6 +3,7 @@
 #include <stdint.h>
 
 #include "../../include/jampack_abi.h"
+#include "prestage_rules.hpp"
 #include "prims.hpp"
 
 namespace jpk {
@@ -55,37 +56,6 @@ __device__ __forceinline__ int32_t adapt_step(int32_t x, int i, int sym, int A)
 {
     int32_t mix = (i <= sym) ? i : i + 65536 - A;
     return x + ((mix - x) >> 5);
-}
-
-// LEB128 "with carry" (utils.cpp:22-68)
-__device__ __forceinline__ int leb_encode(uint32_t v, uint8_t *b)
-{
-    const uint32_t C0 = 127u, C1 = 16510u, C2 = 2113661u, C3 = 270549116u;
-    int n;
-    if (v < C0) n = 1;
-    else if (v < C1) { n = 2; v -= C0; }
-    else if (v < C2) { n = 3; v -= C1; }
-    else if (v < C3) { n = 4; v -= C2; }
-    else { n = 5; v -= C3; }
-    for (int k = 0; k < n; k++) b[k] = (uint8_t)((v >> (7 * (n - 1 - k))) & 0x7f);
-    b[n - 1] |= 0x80;
-    return n;
-}
-// returns bytes consumed or -1
-__device__ __forceinline__ int leb_decode(uint32_t *v, const uint8_t *b, int64_t avail)
-{
-    const uint32_t C[4] = {127u, 16510u, 2113661u, 270549116u};
-    int d = 0;
-    uint32_t x = 0;
-    while (d < avail && !(b[d] & 0x80)) {
-        if (d >= 4) return -1;
-        x = (x << 7) | b[d++];
-    }
-    if (d >= avail) return -1;
-    x = (x << 7) | (b[d] & 0x7fu);
-    if (d > 0) x += C[d - 1];
-    *v = x;
-    return d + 1;
 }
 
 }  // namespace jpk

@@ -62,7 +62,6 @@ __global__ __launch_bounds__(64) void k_dec_headers(const DecBlock *__restrict__
     int32_t *freq = WRITE ? freq_all + (size_t)B.cbase * 256 : nullptr;
     uint32_t *mail = mail_all + 8 * blockIdx.x;
     const int l = lane_id();
-    const uint32_t C[4] = {127u, 16510u, 2113661u, 270549116u};
     uint64_t ip = 0, op = 0, rp = 0;
     uint32_t nch = 0;
     int status = 0;
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(64) void k_dec_headers(const DecBlock *__restrict__
                     uint32_t x = 0;
                     for (uint32_t k = nlead; k > 0; k--) x = (x << 7) | in[p - k];
                     x = (x << 7) | (byte & 0x7fu);
-                    if (nlead > 0) x += C[nlead - 1];
+                    if (nlead > 0) x += pre::LEB_OFF[nlead - 1];
                     if (vidx < 256u) {
                         if (x > (uint32_t)ANS_CHUNK) bad = true;
                         if (WRITE) freq[(size_t)nch * 256 + vidx] = (int32_t)x;

@@ -1289,16 +1289,16 @@ __global__ __launch_bounds__(256) void k_headers(EncDims d, const int32_t *__res
     const uint32_t c = blockIdx.x;
     uint8_t *h = hdr + (size_t)c * HDR_MAX;
     uint8_t tmp[5];
-    const uint32_t n = (uint32_t)leb_encode((uint32_t)freq[(size_t)c * 256 + threadIdx.x], tmp);
+    const uint32_t n = pre::leb_write((uint32_t)freq[(size_t)c * 256 + threadIdx.x], tmp);
     uint32_t tot;
     const uint32_t inc = block_incl_scan<OpSum>(n, sm, &tot);
     uint8_t *o = h + (inc - n);
     for (uint32_t k = 0; k < n; k++) o[k] = tmp[k];
     if (threadIdx.x == 0) {
         int p = (int)tot;
-        p += leb_encode(chunk_len(d, c), h + p);
-        p += leb_encode(csize[c], h + p);
-        p += leb_encode(rlen[c], h + p);
+        p += pre::leb_write(chunk_len(d, c), h + p);
+        p += pre::leb_write(csize[c], h + p);
+        p += pre::leb_write(rlen[c], h + p);
         hsize[c] = (uint32_t)p;
     }
 }

@@ -5,11 +5,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIP__)
-#define JPK_HD __host__ __device__ __forceinline__
-#else
-#define JPK_HD inline
-#endif
+#include "prestage_rules.hpp"
 
 namespace dd {
 
@@ -109,38 +105,15 @@ JPK_HD Run extend(const uint8_t *in, uint32_t n, const uint32_t *table, int bits
     return r;
 }
 
-// Utils::EncodeLeb128 (utils.cpp:22-68), the "with carry" code leb_read of prestage.cpp decodes: big-endian 7-bit groups, bit 7 on the last
-// byte, a longer code starts where the shorter ones end
-JPK_HD uint32_t leb_write(uint32_t v, uint8_t *b)
-{
-    if (v < 127u) { b[0] = (uint8_t)(v | 0x80u); return 1; }
-    if (v < 16510u) { v -= 127u; b[0] = (uint8_t)((v >> 7) & 0x7fu); b[1] = (uint8_t)((v & 0x7fu) | 0x80u); return 2; }
-    if (v < 2113661u) {
-        v -= 16510u;
-        b[0] = (uint8_t)((v >> 14) & 0x7fu); b[1] = (uint8_t)((v >> 7) & 0x7fu); b[2] = (uint8_t)((v & 0x7fu) | 0x80u);
-        return 3;
-    }
-    if (v < 270549116u) {
-        v -= 2113661u;
-        b[0] = (uint8_t)((v >> 21) & 0x7fu); b[1] = (uint8_t)((v >> 14) & 0x7fu); b[2] = (uint8_t)((v >> 7) & 0x7fu);
-        b[3] = (uint8_t)((v & 0x7fu) | 0x80u);
-        return 4;
-    }
-    v -= 270549116u;
-    b[0] = (uint8_t)((v >> 28) & 0x7fu); b[1] = (uint8_t)((v >> 21) & 0x7fu); b[2] = (uint8_t)((v >> 14) & 0x7fu);
-    b[3] = (uint8_t)((v >> 7) & 0x7fu); b[4] = (uint8_t)((v & 0x7fu) | 0x80u);
-    return 5;
-}
-
 // Lz77::WriteToken (lz77.cpp:53-70): token byte, offset, the extension of a saturated match class, of a saturated literal class; <= 16 bytes
 JPK_HD uint32_t token_write(uint32_t match, uint32_t lit, uint32_t off, uint8_t *b)
 {
     match -= 4u;                                                       // MIN_MATCH, lz77.hpp:33
     uint32_t pos = 0;
     b[pos++] = (uint8_t)(((match < 31u ? match : 31u) << 3) | (lit < 7u ? lit : 7u));
-    pos += leb_write(off, b + pos);
-    if (match >= 31u) pos += leb_write(match - 31u, b + pos);
-    if (lit >= 7u) pos += leb_write(lit - 7u, b + pos);
+    pos += pre::leb_write(off, b + pos);
+    if (match >= 31u) pos += pre::leb_write(match - 31u, b + pos);
+    if (lit >= 7u) pos += pre::leb_write(lit - 7u, b + pos);
     return pos;
 }
 
@@ -182,7 +155,7 @@ struct Select {
         Tok t;
         t.out_off = out; t.lit_src = cursor; t.lit = n - cursor; t.hlen = 2;
         for (int i = 0; i < 16; i++) t.hdr[i] = 0;
-        t.hdr[0] = 0x04; t.hdr[1] = 0x80;                              // WriteToken(MIN_MATCH, MIN_MATCH, 0), lz77.cpp:620
+        t.hdr[0] = pre::END_TOKEN[0]; t.hdr[1] = pre::END_TOKEN[1];
         if (store) toks[ntok] = t;
         ntok++;
         return out + 2u + t.lit;

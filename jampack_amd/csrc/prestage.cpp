@@ -17,57 +17,17 @@
 #include "../../include/jampack_abi.h"
 #include "dedupe.hpp"
 
-namespace {
-
-// LEB128 "with carry" (Utils::DecodeLeb128, utils.cpp:73-90): big-endian 7-bit groups, the last byte has bit 7 set,
-// a d-byte prefix adds the class offset of its length.  Returns bytes consumed or -1.
-int leb_read(const uint8_t *b, int64_t avail, int32_t *v)
-{
-    static const uint32_t C[4] = {127u, 16510u, 2113661u, 270549116u};
-    int d = 0;
-    uint32_t x = 0;
-    while (d < avail && !(b[d] & 0x80)) {
-        if (d >= 4) return -1;
-        x = (x << 7) | b[d++];
-    }
-    if (d >= avail) return -1;
-    x = (x << 7) | (b[d] & 0x7fu);
-    if (d > 0) x += C[d - 1];
-    *v = (int32_t)x;
-    return d + 1;
-}
-
-}  // namespace
-
-// Lz77::Decompress (lz77.cpp:678-714).  Token (lz77.cpp:75-98): one byte = match length class (5 bits) | literal
-// count class (3 bits), then the offset, then the extensions of a saturated class; match lengths are stored minus 4.
-// Offset 0 ends the LZ code: the rest of the input is copied through.
+// Lz77::Decompress (lz77.cpp:678-714); the token is pre::parse_token.  Offset 0 ends the LZ code: the rest of the input is copied through.
 extern "C" int jpk_lz77_decompress(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
     int64_t pos = 0, op = 0;
     while (pos < in_len) {
-        const uint32_t token = in[pos++];
-        int32_t off = 0;
-        int64_t len = (int64_t)(token >> 3), lit = (int64_t)(token & 7u);   // 64-bit: the extensions are attacker-controlled int32
-        int n = leb_read(in + pos, in_len - pos, &off);
-        if (n < 0) return JPK_E_CORRUPT;
-        pos += n;
-        if (len == 31) {
-            int32_t e = 0;
-            n = leb_read(in + pos, in_len - pos, &e);
-            if (n < 0 || e < 0) return JPK_E_CORRUPT;
-            pos += n;
-            len += e;
-        }
-        len += 4;                                                      // MIN_MATCH, lz77.hpp:33
-        if (lit == 7) {
-            int32_t e = 0;
-            n = leb_read(in + pos, in_len - pos, &e);
-            if (n < 0 || e < 0) return JPK_E_CORRUPT;
-            pos += n;
-            lit += e;
-        }
+        pre::Token t;
+        if (!pre::parse_token([&](int j) { return (uint32_t)in[pos + j]; }, in_len - pos, &t)) return JPK_E_CORRUPT;
+        const int32_t off = t.off;
+        const int64_t len = t.len, lit = t.lit;
+        pos += t.used;
         if (off == 0) {                                                // end marker: raw remainder
             const int64_t rest = in_len - pos;
             if (op + rest > out_cap) return JPK_E_CAPACITY;
@@ -91,140 +51,35 @@ extern "C" int jpk_lz77_decompress(const uint8_t *in, int32_t in_len, uint8_t *o
 
 namespace {
 
-// Lpx: localized prefix model (lpx.hpp:12-24, lpx.cpp:11-52).  Three tables (context orders 1..3) of 256 records
-// keyed by the leading prefix byte; the decoder mirrors the encoder's table walk exactly.
-struct PrefixRecord {
-    uint32_t cxt, pos, hits, miss;
-    int32_t threshold;
-};
-constexpr int LPX_MAX_THRESHOLD = 128, LPX_MIN_THRESHOLD = 4;
-constexpr uint32_t LPX_MAX_RECORD = 64u << 10;
-
-struct LpxState {
-    PrefixRecord table[3][256];
-    uint32_t cxt = 0;
-    int order = 3;
-    LpxState()
-    {
-        memset(table, 0, sizeof table);
+// Lpx::Encode (lpx.cpp:56-99, 148-158) / Lpx::Decode (lpx.cpp:101-169): every part (pre::part_of) with a fresh model, pre::step byte by
+// byte.  The plain bytes behind position i are input bytes in encode and output bytes in decode.
+template <bool ENC> int lpx_code(const uint8_t *in, int32_t len, uint8_t *out)
+{
+    if (len < 0 || (len > 0 && (!in || !out))) return JPK_E_ARG;
+    pre::Record table[3][256];
+    uint32_t start = 0, plen = 0;
+    for (uint32_t pi = 0; pre::part_of((uint32_t)len, pi, &start, &plen); pi++) {
+        const uint8_t *src = in + start, *plain = ENC ? src : out + start;
+        uint8_t *dst = out + start;
         for (auto &t : table)
-            for (auto &r : t) r.threshold = LPX_MAX_THRESHOLD >> 1;
+            for (auto &r : t) r = pre::fresh_record();
+        pre::Walk w;
+        for (uint32_t i = 0; i < plen; i++) dst[i] = pre::step<ENC>(table, w, i, src[i], [&](uint32_t d) { return plain[i - d]; });
     }
-    // lpx.cpp:11-52.  Note the reference re-indexes the table with the *updated* order for the threshold adjustments.
-    void update(uint32_t pos)
-    {
-        const uint32_t lp = (cxt >> (order * 8)) & 0xffu;
-        const uint32_t ls = cxt & ((1u << (order * 8)) - 1u);
-        PrefixRecord *r = &table[order - 1][lp];
-        const int32_t distance = (int32_t)(pos - r->pos);
-        const int32_t lower = LPX_MIN_THRESHOLD;
-        int32_t upper;
-        if (r->hits < (uint32_t)LPX_MAX_THRESHOLD) upper = distance > LPX_MIN_THRESHOLD ? distance : LPX_MIN_THRESHOLD;
-        else { const int32_t a = distance >> order, b = LPX_MAX_THRESHOLD >> order; upper = a < b ? a : b; }
-        const int32_t bound = (distance <= lower) ? lower : (distance > upper ? upper : distance);
-        if (pos <= (uint32_t)order) return;
-        if (r->cxt == ls) {
-            r->pos = pos - (uint32_t)order;
-            r->hits++;
-            r->miss = 0;
-            if (r->hits > (uint32_t)((r->threshold << order) << 3) && order > 1 && order <= 3) order--;
-            r = &table[order - 1][lp];
-            if (r->hits > (uint32_t)(r->threshold << 1) && r->miss == 0) r->threshold += (bound - r->threshold) >> order;
-        } else {
-            r->hits >>= 2;
-            r->miss++;
-            r->cxt = ls;
-            if (r->miss > (uint32_t)(r->threshold * r->threshold * order) && order >= 1 && order < 3) order++;
-            r = &table[order - 1][lp];
-            if (r->miss > (uint32_t)r->threshold) r->threshold += (LPX_MAX_THRESHOLD - r->threshold) >> (4 - order);
-        }
-    }
-};
-
-// Lpx::EncodeBlock (lpx.cpp:56-99): the mirror image of the decoder below.  The whole input is known, so prediction, stretch flag and
-// context all come from input bytes; the model walk (LpxState::update) is the decoder's.  r.pos <= i always holds (update stores
-// pos - order), which is the `dist <= i` the decoder checks on its untrusted stream.
-void lpx_encode_part(const uint8_t *in, uint8_t *out, int64_t len)
-{
-    LpxState *st = new LpxState();
-    for (int64_t i = 0; i < len;) {
-        const PrefixRecord &r = st->table[st->order - 1][st->cxt & 0xffu];
-        const uint32_t dist = (uint32_t)i - r.pos;
-        if (r.hits > (uint32_t)r.threshold && dist < LPX_MAX_RECORD && dist <= (uint32_t)i) {
-            uint8_t err;
-            do {
-                out[i] = err = (uint8_t)(in[i - dist] ^ in[i]);
-                st->update((uint32_t)i);
-                st->cxt = (st->cxt << 8) | in[i];
-                i++;
-            } while (err == 0 && i < len);
-        } else {
-            out[i] = in[i];
-            st->update((uint32_t)i);
-            st->cxt = (st->cxt << 8) | in[i];
-            i++;
-        }
-    }
-    delete st;
-}
-
-// Lpx::DecodeBlock (lpx.cpp:101-144): inside a predicted stretch the stream holds prediction XOR byte
-void lpx_decode_part(const uint8_t *in, uint8_t *out, int64_t len)
-{
-    LpxState *st = new LpxState();
-    for (int64_t i = 0; i < len;) {
-        const PrefixRecord &r = st->table[st->order - 1][st->cxt & 0xffu];
-        const uint32_t dist = (uint32_t)i - r.pos;
-        if (r.hits > (uint32_t)r.threshold && dist < LPX_MAX_RECORD && dist <= (uint32_t)i) {
-            uint8_t err;
-            do {
-                err = in[i];
-                out[i] = out[i - dist] ^ in[i];
-                st->update((uint32_t)i);
-                st->cxt = (st->cxt << 8) | out[i];
-                i++;
-            } while (err == 0 && i < len);
-        } else {
-            out[i] = in[i];
-            st->update((uint32_t)i);
-            st->cxt = (st->cxt << 8) | out[i];
-            i++;
-        }
-    }
-    delete st;
+    return JPK_OK;
 }
 
 }  // namespace
 
-// Lpx::Decode (lpx.cpp:158-169): the block is cut into parts of len / 4 bytes (a fifth, shorter one when len is not a
-// multiple of 4), each decoded with a fresh model.  The reference loops forever for 0 < len < 4 (part size 0); no
-// encoder output can be that short, so such inputs are passed through as one part.
-extern "C" int jpk_lpx_decode(const uint8_t *in, int32_t len, uint8_t *out)
-{
-    if (len < 0 || (len > 0 && (!in || !out))) return JPK_E_ARG;
-    const int64_t part = len / 4;
-    if (part == 0) { if (len) lpx_decode_part(in, out, len); return JPK_OK; }
-    for (int64_t i = 0; i < len; i += part) lpx_decode_part(in + i, out + i, (i + part < len) ? part : len - i);
-    return JPK_OK;
-}
-
-// Lpx::Encode (lpx.cpp:148-158): the same cut into parts of len / 4 bytes as the decoder, each with a fresh model (and the same
-// pass-through as one part for 0 < len < 4, where the reference does not terminate)
-extern "C" int jpk_lpx_encode(const uint8_t *in, int32_t len, uint8_t *out)
-{
-    if (len < 0 || (len > 0 && (!in || !out))) return JPK_E_ARG;
-    const int64_t part = len / 4;
-    if (part == 0) { if (len) lpx_encode_part(in, out, len); return JPK_OK; }
-    for (int64_t i = 0; i < len; i += part) lpx_encode_part(in + i, out + i, (i + part < len) ? part : len - i);
-    return JPK_OK;
-}
+extern "C" int jpk_lpx_decode(const uint8_t *in, int32_t len, uint8_t *out) { return lpx_code<false>(in, len, out); }
+extern "C" int jpk_lpx_encode(const uint8_t *in, int32_t len, uint8_t *out) { return lpx_code<true>(in, len, out); }
 
 // Filters::Decode (filters.cpp:442-490): per 64 KiB block two header bytes (filter type, channel width), width 0 =
 // raw.  Types: 0 delta and 1 adaptive linear prediction on de-interleaved channels, 2 in-place delta per channel.
 extern "C" int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
-    constexpr int64_t FBS = 64 << 10;
+    constexpr int64_t FBS = pre::FBS;
     std::vector<uint8_t> dbuf((size_t)FBS);
     int64_t i = 0, op = 0;
     while (i < in_len) {
@@ -248,17 +103,8 @@ extern "C" int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *ou
             if (type == 0) {                                            // DeltaDecode: running sum over the whole block
                 uint8_t prev = 0;
                 for (int64_t k = 0; k < len; k++) { prev = (uint8_t)(src[k] + prev); dbuf[(size_t)k] = prev; }
-            } else {                                                    // LpcDecode: x = w + 2 p1 - p2 - err, w += (err - w) >> 6
-                int32_t weight = 0;
-                uint8_t p1 = 0, p2 = 0;
-                for (int64_t k = 0; k < len; k++) {
-                    const uint8_t err = src[k];
-                    const uint8_t cur = (uint8_t)(weight + (((int32_t)p1 - (int32_t)p2) + (int32_t)p1) - (int32_t)err);
-                    dbuf[(size_t)k] = cur;
-                    weight += ((int32_t)err - weight) >> 6;
-                    p2 = p1;
-                    p1 = cur;
-                }
+            } else {
+                pre::lpc_decode(src, dbuf.data(), (uint32_t)len);
             }
             int64_t p = 0;                                              // Unreorder: channel c holds bytes c, c + width, ...
             for (int c = 0; c < width; c++)
@@ -285,28 +131,24 @@ extern "C" int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *ou
 //   the reference's stage buffers hold (int)(B * 1.05) >= B + B / 20 - 1 bytes (jampack.cpp:157), and B / 20 - B / 32768 >= 52396 at
 //   B = 2^20 and grows with B, which is above 487: the frame fits them, and with them this library's own 1.05 B + 4096 on the
 //   entropy-decoded size.  At B = JPK_MAX_BLOCKSIZE |S4| = 1048576000 + 4 + 2 * 16001 stays below 2^31 and below JPK_FWD_BWT_LIMIT.
-namespace {
-constexpr int64_t CLI_FBS = 64 << 10;
-constexpr uint8_t CLI_TOKEN[2] = {0x04, 0x80};
-}
-
 extern "C" int64_t jpk_cli_stages_bound(int64_t n)
 {
     if (n < 0) return JPK_E_ARG;
-    return n + 4 + 2 * ((n + 2 + CLI_FBS - 1) / CLI_FBS);
+    return pre::s4_of_s1(n + 2);
 }
 
 // S4 of S1 = head | body: the filter pieces, Lpx::Encode, the second end token
 static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
-    const int64_t s1 = nhead + nbody, total = s1 + 2 + 2 * ((s1 + CLI_FBS - 1) / CLI_FBS), s2 = total - 2;
+    constexpr int64_t FBS = pre::FBS;
+    const int64_t s1 = nhead + nbody, total = pre::s4_of_s1(s1), s2 = total - 2;
     if (total > 0x7fffffff) return JPK_E_ARG;
     if (total > out_cap) return JPK_E_CAPACITY;
     std::vector<uint8_t> buf;
     try { buf.resize((size_t)s2); } catch (...) { return JPK_E_ALLOC; }
     int64_t op = 0;
     for (int64_t i = 0; i < s1;) {                                     // byte i of S1: head[i], then body[i - nhead]
-        const int64_t len = (i + CLI_FBS < s1) ? CLI_FBS : s1 - i;
+        const int64_t len = (i + FBS < s1) ? FBS : s1 - i;
         if (op + 2 + len > s2) return JPK_E_CAPACITY;                  // cannot happen: s2 counts exactly these bytes
         buf[(size_t)op] = 0; buf[(size_t)op + 1] = 0;
         op += 2;
@@ -316,7 +158,7 @@ static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *bo
         op += len;
         i += len;
     }
-    out[0] = CLI_TOKEN[0]; out[1] = CLI_TOKEN[1];
+    out[0] = pre::END_TOKEN[0]; out[1] = pre::END_TOKEN[1];
     const int rc = jpk_lpx_encode(buf.data(), (int32_t)s2, out + 2);
     if (rc != JPK_OK) return rc;
     *out_len = (int32_t)total;
@@ -378,7 +220,7 @@ extern "C" int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *o
 {
     if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
     if (jpk_cli_stages_bound(n) > 0x7fffffff) return JPK_E_ARG;
-    if (!(flags & JPK_CLI_DEDUPE)) return cli_stages_from(CLI_TOKEN, 2, in, n, out, out_cap, out_len);
+    if (!(flags & JPK_CLI_DEDUPE)) return cli_stages_from(pre::END_TOKEN, 2, in, n, out, out_cap, out_len);
     std::vector<uint8_t> s1;
     try { s1.resize((size_t)n + 2); } catch (...) { return JPK_E_ALLOC; }
     int32_t m = 0;

@@ -1,12 +1,14 @@
 // prestage_dev.hip -- the decoders of the three stages the stock CLI runs in front of the BWT (Jampack::Decomp, jampack.cpp:47-60), on gfx950,
 // for batches of blocks that already sit in HBM behind the batched rANS decode + inverse BWT:
 //   k_pre_lz77     Lz77::Decompress (lz77.cpp:678-714)   one workgroup per block: every lane parses the token, all lanes copy
-//   k_pre_lpx      Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
+//   k_lpx<false>   Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
+//                  (k_pre_lpx in the profiler's table and in DESIGN 4.7)
 //   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
 // and the two kernels of the writer of such frames (writing; the stage chain of jpk_cli_stages_encode):
 //   k_enc_wrap     raw block -> S2: the LZ77 end token and the 00 00 header of every 64 KiB filter piece around the unchanged bytes,
 //                  organised by destination like k_jam_pack: a thread owns aligned 16-byte words of the output
-//   k_enc_lpx      Lpx::Encode      (lpx.cpp:56-99, 148-158) one workgroup per part, the mirror image of k_pre_lpx
+//   k_lpx<true>    Lpx::Encode      (lpx.cpp:56-99, 148-158) one workgroup per part, the other instance of the decoder's kernel (k_enc_lpx
+//                  in the profiler's table)
 // and the dedupe of the writer's first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp, shared with the host form):
 //   k_dd_anchor    every aligned 64-byte window into its slot of the block's table, atomicMin on the position
 //   k_dd_cand      one workgroup per tile of 1024 positions: fingerprints of all positions by six doubling steps in LDS, the candidate offset
@@ -14,20 +16,27 @@
 //   k_dd_extend    one thread per head: its run
 //   k_dd_select    one workgroup per block: the greedy chain over the runs, token records with their output offsets
 //   k_dd_emit      token headers and literal runs by destination, as k_enc_wrap
-// Each is bit-identical to its host form in prestage.cpp (statuses included) and keeps that file's bounds checks: every read is checked
+// Each is bit-identical to its host form in prestage.cpp (statuses included), and by construction where a rule decides a byte or a status:
+// the LEB128 code, the LZ77 token, the LPX model, part cut and step, the filter sizes and the LPC recurrence are prestage_rules.hpp, the
+// dedupe is dedupe.hpp, and both forms compile them.  What is written here is the device shape around the rules: the copies, the scans,
+// the tiles and the word assembly.  Each keeps the host file's bounds checks: every read is checked
 // against in_len and every write against out_cap before it is made, in 64-bit arithmetic.  No workgroup waits for another one, every
 // loop is bounded by the stream length or the output capacity, and a bad stream sets the block's mail word and ends the workgroup.
 #include <vector>
 
 #include "common.hpp"
 #include "dedupe.hpp"
+#include "prestage_rules.hpp"
 
 namespace {
 
-// one block of a batch: wg0 = the workgroups of the blocks in front of it (k_pre_lpx, k_pre_filters: several workgroups per block)
+// one block of a batch: wg0 = the workgroups of the blocks in front of it (k_lpx, k_pre_filters: several workgroups per block)
 struct PreJob { const uint8_t *in; uint8_t *out; int32_t in_len; int32_t out_cap; uint32_t wg0; uint32_t pad; };
 
 constexpr int PRE_TB = 256;
+using pre::FBS;
+using pre::LPX_RING;
+using pre::LPX_TILE;
 
 // the block of workgroup w: the last job with wg0 <= w (jobs without workgroups share the wg0 of their successor and are skipped by it)
 __device__ __forceinline__ uint32_t job_of(const PreJob *__restrict__ jobs, uint32_t n, uint32_t w)
@@ -41,25 +50,6 @@ __device__ __forceinline__ uint32_t job_of(const PreJob *__restrict__ jobs, uint
 // A token is at most 16 bytes (token, three LEB128 values of up to five bytes): every wave loads the 16 bytes at `pos` once, lane l the
 // byte (l & 15), and reads them back by index, so the parse is the same in every lane and costs one load per token.
 __device__ __forceinline__ uint32_t win_byte(uint32_t w, int j) { return (uint32_t)__shfl((int)w, j, 64); }
-
-// leb_read of prestage.cpp on the window: the value at window offset `at`, avail = bytes of the stream from there
-__device__ __forceinline__ int leb_win(uint32_t w, int at, int64_t avail, int32_t *v)
-{
-    int d = 0;
-    uint32_t x = 0, b;
-    for (;;) {
-        if (d >= avail) return -1;
-        b = win_byte(w, at + d);
-        if (b & 0x80u) break;
-        if (d >= 4) return -1;
-        x = (x << 7) | b;
-        d++;
-    }
-    x = (x << 7) | (b & 0x7fu);
-    if (d > 0) x += d == 1 ? 127u : (d == 2 ? 16510u : (d == 3 ? 2113661u : 270549116u));
-    *v = (int32_t)x;
-    return d + 1;
-}
 
 // mail[2 b] = status, mail[2 b + 1] = out_len.  The match copy out[op + k] = out[op - off + k mod off] reads only bytes below op, which
 // the tokens in front of this one (and this token's literals) wrote: one fence + barrier per token, between the literal copy and the
@@ -77,29 +67,11 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_lz77(const PreJob *__restrict__ 
     while (pos < in_len) {
         const int64_t wi = pos + (int64_t)(tid & 15u);
         const uint32_t w = wi < in_len ? in[wi] : 0u;
-        const uint32_t token = win_byte(w, 0);
-        int at = 1;
-        int32_t off = 0;
-        int64_t len = (int64_t)(token >> 3), lit = (int64_t)(token & 7u);
-        int n = leb_win(w, at, in_len - pos - at, &off);
-        if (n < 0) { status = JPK_E_CORRUPT; break; }
-        at += n;
-        if (len == 31) {
-            int32_t e = 0;
-            n = leb_win(w, at, in_len - pos - at, &e);
-            if (n < 0 || e < 0) { status = JPK_E_CORRUPT; break; }
-            at += n;
-            len += e;
-        }
-        len += 4;                                                      // MIN_MATCH, lz77.hpp:33
-        if (lit == 7) {
-            int32_t e = 0;
-            n = leb_win(w, at, in_len - pos - at, &e);
-            if (n < 0 || e < 0) { status = JPK_E_CORRUPT; break; }
-            at += n;
-            lit += e;
-        }
-        pos += at;
+        pre::Token t;
+        if (!pre::parse_token([w](int j) { return win_byte(w, j); }, in_len - pos, &t)) { status = JPK_E_CORRUPT; break; }
+        const int32_t off = t.off;
+        const int64_t len = t.len, lit = t.lit;
+        pos += t.used;
         if (off == 0) {                                                // end marker: raw remainder
             const int64_t rest = in_len - pos;
             if (op + rest > out_cap) { status = JPK_E_CAPACITY; break; }
@@ -137,169 +109,56 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_lz77(const PreJob *__restrict__ 
 }
 
 // ---- LPX -----------------------------------------------------------------------------------------------------------------------
-struct PrefixRecord { uint32_t cxt, pos, hits, miss; int32_t threshold; };
-constexpr int LPX_MAX_THRESHOLD = 128, LPX_MIN_THRESHOLD = 4;
-constexpr uint32_t LPX_MAX_RECORD = 64u << 10;
-constexpr uint32_t LPX_TILE = 16u << 10;
-constexpr uint32_t LPX_RING = LPX_MAX_RECORD + LPX_TILE;         // position p lives at p mod LPX_RING until p + LPX_RING is written
-
-// LpxState::update of prestage.cpp (lpx.cpp:11-52), the tables in LDS
-__device__ __forceinline__ void lpx_update(PrefixRecord (*table)[256], uint32_t cxt, int &order, uint32_t pos)
+// One workgroup per part (pre::part_of: a block is cut into parts of len / 4 bytes, each with a fresh model).  The model is byte-serial and
+// adaptive -- every byte's prediction depends on the tables the byte in front of it left -- so the chain of a part is ONE lane running
+// pre::step, with the three tables (15 KiB), one tile (16 KiB) and a ring of the last 64 KiB + one tile of PLAIN bytes (80 KiB) in LDS: 111
+// KiB, one workgroup per CU; the other lanes only move tiles between HBM and LDS.  A stretch may cross a tile edge (pre::Walk::run).
+//   decode  the tile holds the input, lane 0 leaves the output in the ring (its predictions read it), all lanes write the ring's tile out
+//   encode  the whole input is known, so the chain reads only input bytes: all lanes load a tile straight into the ring, lane 0 leaves the
+//           error bytes in the tile, all lanes write the tile out.  token != 0: the job's output is S3 inside an S4 buffer and part 0 puts
+//           the LZ77 end token into the two bytes in front of it.
+template <bool ENC> __global__ __launch_bounds__(PRE_TB) void k_lpx(const PreJob *__restrict__ jobs, uint32_t n, uint32_t token)
 {
-    const uint32_t lp = (cxt >> (order * 8)) & 0xffu;
-    const uint32_t ls = cxt & ((1u << (order * 8)) - 1u);
-    PrefixRecord *r = &table[order - 1][lp];
-    const int32_t distance = (int32_t)(pos - r->pos);
-    const int32_t lower = LPX_MIN_THRESHOLD;
-    int32_t upper;
-    if (r->hits < (uint32_t)LPX_MAX_THRESHOLD) upper = distance > LPX_MIN_THRESHOLD ? distance : LPX_MIN_THRESHOLD;
-    else { const int32_t a = distance >> order, b = LPX_MAX_THRESHOLD >> order; upper = a < b ? a : b; }
-    const int32_t bound = (distance <= lower) ? lower : (distance > upper ? upper : distance);
-    if (pos <= (uint32_t)order) return;
-    if (r->cxt == ls) {
-        r->pos = pos - (uint32_t)order;
-        r->hits++;
-        r->miss = 0;
-        if (r->hits > (uint32_t)((r->threshold << order) << 3) && order > 1 && order <= 3) order--;
-        r = &table[order - 1][lp];                                     // re-indexed with the UPDATED order, as the reference does
-        if (r->hits > (uint32_t)(r->threshold << 1) && r->miss == 0) r->threshold += (bound - r->threshold) >> order;
-    } else {
-        r->hits >>= 2;
-        r->miss++;
-        r->cxt = ls;
-        if (r->miss > (uint32_t)(r->threshold * r->threshold * order) && order >= 1 && order < 3) order++;
-        r = &table[order - 1][lp];
-        if (r->miss > (uint32_t)r->threshold) r->threshold += (LPX_MAX_THRESHOLD - r->threshold) >> (4 - order);
-    }
-}
-
-// One workgroup per part (Lpx::Decode cuts a block into parts of len / 4 bytes, each with a fresh model).  The model is byte-serial and
-// adaptive -- every byte's prediction depends on the tables the byte in front of it left -- so the chain of a part is ONE lane, with
-// the three tables (15 KiB), the input tile and the last 64 KiB + one tile of output in LDS; the other lanes only move tiles between HBM
-// and LDS.  lpx_decode_part's inner do-while (a predicted stretch runs on while the error byte is 0) is the `run` flag here, so that a
-// stretch may cross a tile edge.
-__global__ __launch_bounds__(PRE_TB) void k_pre_lpx(const PreJob *__restrict__ jobs, uint32_t n)
-{
-    __shared__ PrefixRecord table[3][256];
-    __shared__ uint8_t s_in[LPX_TILE];
+    __shared__ pre::Record table[3][256];
+    __shared__ uint8_t tile[LPX_TILE];
     __shared__ uint8_t ring[LPX_RING];
     const uint32_t tid = threadIdx.x;
     const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
-    const uint32_t len = (uint32_t)jb.in_len, part = len / 4u, pi = blockIdx.x - jb.wg0;
-    const uint32_t start = part ? pi * part : 0u;
-    if (start >= len) return;
-    const uint32_t plen = (part && part < len - start) ? part : len - start;
+    const uint32_t pi = blockIdx.x - jb.wg0;
+    uint32_t start, plen;
+    if (!pre::part_of((uint32_t)jb.in_len, pi, &start, &plen)) return;
     const uint8_t *in = jb.in + start;
     uint8_t *out = jb.out + start;
-    for (uint32_t k = tid; k < 3u * 256u; k += PRE_TB) {
-        PrefixRecord r;
-        r.cxt = 0; r.pos = 0; r.hits = 0; r.miss = 0; r.threshold = LPX_MAX_THRESHOLD >> 1;
-        table[k >> 8][k & 255u] = r;
-    }
-    uint32_t cxt = 0, dist = 0;
-    int order = 3;
-    bool run = false;
+    if (ENC && token && pi == 0 && tid == 0) { jb.out[-2] = pre::END_TOKEN[0]; jb.out[-1] = pre::END_TOKEN[1]; }
+    for (uint32_t k = tid; k < 3u * 256u; k += PRE_TB) table[k >> 8][k & 255u] = pre::fresh_record();
+    pre::Walk w;
     for (uint32_t base = 0; base < plen; base += LPX_TILE) {
         const uint32_t cnt = plen - base < LPX_TILE ? plen - base : LPX_TILE;
         const uint32_t rb = base % LPX_RING;
-        for (uint32_t k = tid; k < cnt; k += PRE_TB) s_in[k] = in[base + k];
-        __syncthreads();
+        for (uint32_t k = tid; k < cnt; k += PRE_TB) {
+            const uint32_t q = rb + k;
+            if constexpr (ENC) ring[q >= LPX_RING ? q - LPX_RING : q] = in[base + k];
+            else tile[k] = in[base + k];
+        }
+        __syncthreads();                                               // (orders the table set-up and the last tile's reads as well)
         if (tid == 0) {
             uint32_t wi = rb;                                          // ring index of position i
             for (uint32_t k = 0; k < cnt; k++) {
-                const uint32_t i = base + k;
-                if (!run) {
-                    const PrefixRecord *r = &table[order - 1][cxt & 0xffu];
-                    const uint32_t d = i - r->pos;
-                    if (r->hits > (uint32_t)r->threshold && d < LPX_MAX_RECORD && d <= i) { run = true; dist = d; }
-                }
-                const uint8_t e = s_in[k];
-                uint8_t o = e;
-                if (run) {
-                    const uint32_t hi = wi >= dist ? wi - dist : wi + LPX_RING - dist;
-                    o = (uint8_t)(ring[hi] ^ e);
-                    if (e != 0) run = false;
-                }
-                ring[wi] = o;
-                lpx_update(table, cxt, order, i);
-                cxt = (cxt << 8) | o;
+                const uint8_t o = pre::step<ENC>(table, w, base + k, ENC ? ring[wi] : tile[k], [&](uint32_t d) { return ring[pre::ring_back(wi, d)]; });
+                if constexpr (ENC) tile[k] = o;
+                else ring[wi] = o;
                 wi = wi + 1 == LPX_RING ? 0u : wi + 1;
             }
         }
         __syncthreads();
         for (uint32_t k = tid; k < cnt; k += PRE_TB) {
             const uint32_t q = rb + k;
-            out[base + k] = ring[q >= LPX_RING ? q - LPX_RING : q];
+            out[base + k] = ENC ? tile[k] : ring[q >= LPX_RING ? q - LPX_RING : q];
         }
-    }
-}
-
-// Lpx::Encode, the mirror image of k_pre_lpx: one workgroup per part, one lane runs the model.  In encode the whole input is known, so the
-// chain reads only INPUT bytes -- the prediction in[i - dist], the byte in[i] it is compared with (the stretch goes on while their XOR
-// is 0) and the context -- and the ring holds the last 64 KiB + one tile of input: all lanes load a tile straight into the ring, lane 0
-// walks it and leaves the error bytes in s_out, all lanes write s_out to HBM.  LDS: tables 15 KiB + ring 80 KiB + tile 16 KiB = 111 KiB,
-// as the decoder: one workgroup per CU.  token != 0: the job's output is S3 inside an S4 buffer and part 0 puts the LZ77 end token
-// (04 80, prestage.cpp) into the two bytes in front of it.
-__global__ __launch_bounds__(PRE_TB) void k_enc_lpx(const PreJob *__restrict__ jobs, uint32_t n, uint32_t token)
-{
-    __shared__ PrefixRecord table[3][256];
-    __shared__ uint8_t s_out[LPX_TILE];
-    __shared__ uint8_t ring[LPX_RING];
-    const uint32_t tid = threadIdx.x;
-    const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
-    const uint32_t len = (uint32_t)jb.in_len, part = len / 4u, pi = blockIdx.x - jb.wg0;
-    const uint32_t start = part ? pi * part : 0u;
-    if (start >= len) return;
-    const uint32_t plen = (part && part < len - start) ? part : len - start;
-    const uint8_t *in = jb.in + start;
-    uint8_t *out = jb.out + start;
-    if (token && pi == 0 && tid == 0) { jb.out[-2] = 0x04; jb.out[-1] = 0x80; }
-    for (uint32_t k = tid; k < 3u * 256u; k += PRE_TB) {
-        PrefixRecord r;
-        r.cxt = 0; r.pos = 0; r.hits = 0; r.miss = 0; r.threshold = LPX_MAX_THRESHOLD >> 1;
-        table[k >> 8][k & 255u] = r;
-    }
-    uint32_t cxt = 0, dist = 0;
-    int order = 3;
-    bool run = false;
-    for (uint32_t base = 0; base < plen; base += LPX_TILE) {
-        const uint32_t cnt = plen - base < LPX_TILE ? plen - base : LPX_TILE;
-        const uint32_t rb = base % LPX_RING;
-        for (uint32_t k = tid; k < cnt; k += PRE_TB) {
-            const uint32_t q = rb + k;
-            ring[q >= LPX_RING ? q - LPX_RING : q] = in[base + k];
-        }
-        __syncthreads();                                               // (orders the table set-up and the last tile's s_out reads as well)
-        if (tid == 0) {
-            uint32_t wi = rb;                                          // ring index of position i
-            for (uint32_t k = 0; k < cnt; k++) {
-                const uint32_t i = base + k;
-                if (!run) {
-                    const PrefixRecord *r = &table[order - 1][cxt & 0xffu];
-                    const uint32_t d = i - r->pos;
-                    if (r->hits > (uint32_t)r->threshold && d < LPX_MAX_RECORD && d <= i) { run = true; dist = d; }
-                }
-                const uint8_t c = ring[wi];
-                uint8_t e = c;
-                if (run) {
-                    const uint32_t hi = wi >= dist ? wi - dist : wi + LPX_RING - dist;
-                    e = (uint8_t)(ring[hi] ^ c);
-                    if (e != 0) run = false;
-                }
-                s_out[k] = e;
-                lpx_update(table, cxt, order, i);
-                cxt = (cxt << 8) | c;
-                wi = wi + 1 == LPX_RING ? 0u : wi + 1;
-            }
-        }
-        __syncthreads();
-        for (uint32_t k = tid; k < cnt; k += PRE_TB) out[base + k] = s_out[k];
     }
 }
 
 // ---- filters -------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t FBS = 64u << 10;
-
 // Running sums with stride W in LDS, in place: s[k0 + m W + c] += s[k0 + (m - 1) W + c] for m = 1 .. M - 1, every channel c < W on
 // its own (mod 256).  Thread t owns channel t mod W and the (t / W)-th run of rows: partial sums, their prefix over the runs in front
 // of its own, then the running sum over its rows.  All threads of the workgroup call it.
@@ -357,19 +216,8 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_filters(const PreJob *__restrict
     }
     if (type == 0) {                                                   // DeltaDecode: running sum over the whole block
         scan_stride(s, part, 0, 1, len);
-    } else {                                                           // LpcDecode: x = w + 2 p1 - p2 - err, w += (err - w) >> 6; serial
-        if (tid == 0) {
-            int32_t weight = 0;
-            uint8_t p1 = 0, p2 = 0;
-            for (uint32_t k = 0; k < len; k++) {
-                const uint8_t err = s[k];
-                const uint8_t cur = (uint8_t)(weight + (((int32_t)p1 - (int32_t)p2) + (int32_t)p1) - (int32_t)err);
-                s[k] = cur;
-                weight += ((int32_t)err - weight) >> 6;
-                p2 = p1;
-                p1 = cur;
-            }
-        }
+    } else {                                                           // LpcDecode: serial
+        if (tid == 0) pre::lpc_decode(s, s, len);
         __syncthreads();
     }
     // Unreorder: channel c holds bytes c, c + width, ...: it has len / width elements, one more when c < len mod width
@@ -391,7 +239,7 @@ template <bool TOK> __device__ __forceinline__ uint32_t wrap_byte(uint32_t p, co
     if (r < 2u) return 0u;
     const uint32_t s1 = pj * FBS + r - 2u;
     if (!TOK) return in[s1];
-    return s1 < 2u ? (s1 == 0u ? 0x04u : 0x80u) : in[s1 - 2u];
+    return s1 < 2u ? (s1 == 0u ? pre::END_TOKEN[0] : pre::END_TOKEN[1]) : in[s1 - 2u];
 }
 
 // Job: in = R (in_len bytes), out = S2 (out_cap = |S2| bytes), wg0 as for the other kernels; a workgroup owns WRAP_WORDS * PRE_TB
@@ -666,9 +514,25 @@ int pre_finish(jpk_ctx *ctx, const uint32_t *d_mail, std::vector<uint32_t> &mail
     return JPK_OK;
 }
 
-int first_status(int32_t n, const int32_t *st)
+int pre_finish(jpk_ctx *ctx)
 {
-    for (int b = 0; b < n; b++) if (st[b] != JPK_OK) return st[b];
+    std::vector<uint32_t> none;
+    return pre_finish(ctx, nullptr, none);
+}
+
+// the per-block arguments of a batch entry (the array pointers themselves have been checked)
+bool blocks_args_ok(int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out, const int32_t *out_cap)
+{
+    for (int b = 0; b < n; b++)
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return false;
+    return true;
+}
+
+// the answer of a batch entry: per block in status[] when it is given one (stp == status), else the first status that is not JPK_OK
+int finish_statuses(int32_t n, const int32_t *status, const int32_t *stp)
+{
+    if (status) return JPK_OK;
+    for (int b = 0; b < n; b++) if (stp[b] != JPK_OK) return stp[b];
     return JPK_OK;
 }
 
@@ -757,8 +621,7 @@ int dd_emit(jpk_ctx *ctx, int n, DdCall *dc, uint8_t *const *outs, const int32_t
             JPK_LAUNCH(ctx, PROF_DD_EMIT, dc->bytes, k_dd_emit, dim3(jpk_grid(max_words, WRAP_WORDS * PRE_TB), (unsigned)std::min(DD_GRID_Y, n - b0)), dim3(PRE_TB),
                        dc->d_jobs + b0);
     }
-    std::vector<uint32_t> none;
-    return pre_finish(ctx, nullptr, none);
+    return pre_finish(ctx);
 }
 
 }  // namespace
@@ -769,10 +632,10 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
     JPK_TRY(pre_enter(ctx));
     if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
     if (n == 0) return JPK_OK;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
     std::vector<PreJob> jobs((size_t)n);
     uint64_t bytes = 0;
     for (int b = 0; b < n; b++) {
-        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
         jobs[(size_t)b] = PreJob{d_in[b], d_out[b], in_len[b], out_cap[b], (uint32_t)b, 0u};
         bytes += (uint32_t)in_len[b];
     }
@@ -787,15 +650,14 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
         stp[b] = (int32_t)mail[2 * (size_t)b];
         out_len[b] = stp[b] == JPK_OK ? (int32_t)mail[2 * (size_t)b + 1] : 0;
     }
-    return status ? JPK_OK : first_status(n, stp);
+    return finish_statuses(n, status, stp);
 }
 
 extern "C" int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                           const int32_t *out_cap, int32_t *out_len, int32_t *status)
 {
     if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
-    for (int b = 0; b < n; b++)
-        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
     JPK_TRY(pre_enter(ctx));
     if (n == 0) return JPK_OK;
     DdCall dc;
@@ -809,18 +671,10 @@ extern "C" int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t
         out_len[b] = stp[b] == JPK_OK ? s1[(size_t)b] : 0;
     }
     JPK_TRY(dd_emit(ctx, n, &dc, outs.data(), s1.data()));
-    return status ? JPK_OK : first_status(n, stp);
+    return finish_statuses(n, status, stp);
 }
 
 namespace {
-// workgroups of one block in k_pre_lpx / k_enc_lpx: Lpx::Decode's loop `for (i = 0; i < len; i += part)` with part = len / 4: four parts,
-// more when len is not a multiple of 4 (a fifth, short one; up to seven for len < 8); one part for len < 4
-uint32_t lpx_parts(int32_t len)
-{
-    const uint32_t part = (uint32_t)len / 4u;
-    return part ? ((uint32_t)len + part - 1) / part : (len ? 1u : 0u);
-}
-
 // Lpx::Decode / Lpx::Encode of n blocks, one launch
 int lpx_batch(jpk_ctx *ctx, bool encode, int32_t n, const uint8_t *const *d_in, const int32_t *len, uint8_t *const *d_out, int32_t *status)
 {
@@ -832,17 +686,16 @@ int lpx_batch(jpk_ctx *ctx, bool encode, int32_t n, const uint8_t *const *d_in, 
     for (int b = 0; b < n; b++) {
         if (len[b] < 0 || (len[b] > 0 && (!d_in[b] || !d_out[b]))) return JPK_E_ARG;
         jobs[(size_t)b] = PreJob{d_in[b], d_out[b], len[b], len[b], (uint32_t)wgs, 0u};
-        wgs += lpx_parts(len[b]);
+        wgs += pre::parts((uint32_t)len[b]);
         bytes += (uint32_t)len[b];
     }
     if (wgs > 0x7fffffffull) return JPK_E_ARG;
     if (wgs) {
         PreCall pc;
         JPK_TRY(pre_upload(ctx, jobs, 0, 0, &pc));
-        if (encode) JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_enc_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n, 0u);
-        else JPK_LAUNCH(ctx, PROF_PRE_LPX, bytes, k_pre_lpx, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n);
-        std::vector<uint32_t> none;
-        JPK_TRY(pre_finish(ctx, nullptr, none));
+        if (encode) JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_lpx<true>, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n, 0u);
+        else JPK_LAUNCH(ctx, PROF_PRE_LPX, bytes, k_lpx<false>, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n, 0u);
+        JPK_TRY(pre_finish(ctx));
     }
     if (status) for (int b = 0; b < n; b++) status[b] = JPK_OK;      // any byte string is a valid stream / a valid input
     return JPK_OK;
@@ -860,12 +713,12 @@ extern "C" int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t 
 }
 
 // The stage chain of jpk_cli_stages_encode_ex for n blocks in HBM: k_enc_wrap R -> S2 into d_mid[b] (jpk_cli_stages_bound - 2 bytes; d_mid
-// == nullptr: in the context's arena), k_enc_lpx S2 -> S3 two bytes into d_out[b], with the second end token in front of it.
+// == nullptr: in the context's arena), k_lpx<true> S2 -> S3 two bytes into d_out[b], with the second end token in front of it.
 // in_len[b] < 0: the block is skipped.  The caller has checked that every jpk_cli_stages_bound fits its buffer and an int32.
 // flags & JPK_CLI_DEDUPE: dd_find and dd_emit first, S1' into d_out[b] (|S1'| < |S4|: it fits), and k_enc_wrap reads S1' from there at the
-// length the host has read; k_enc_lpx overwrites it behind k_enc_wrap in stream order.  s4_len[b] (nullable) = |S4|.
+// length the host has read; k_lpx<true> overwrites it behind k_enc_wrap in stream order.  s4_len[b] (nullable) = |S4|.
 namespace {
-int64_t s4_of_s1(int64_t s1) { return s1 + 2 + 2 * ((s1 + FBS - 1) / FBS); }
+using pre::s4_of_s1;
 
 // found != nullptr: dd_find has run for these blocks (its scratch is still in the arena) and found_s1[] holds its lengths
 int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out, uint32_t flags,
@@ -910,7 +763,7 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
         lj[(size_t)b] = PreJob{mid, d_out[b] + 2, s2, s2, (uint32_t)lwg, 0u};
         const uint64_t words = (((uintptr_t)mid & 15u) + (uint64_t)s2 + 15u) / 16u;
         wwg += (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
-        lwg += lpx_parts(s2);
+        lwg += pre::parts((uint32_t)s2);
         bytes += (uint32_t)s2;
     }
     if (wwg > 0x7fffffffull || lwg > 0x7fffffffull) return JPK_E_ARG;
@@ -919,10 +772,9 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
         JPK_HIP(hipMemcpyAsync(d_jobs + n, lj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
         if (dedupe) JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         else JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
-        JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_enc_lpx, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
+        JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_lpx<true>, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
     }
-    std::vector<uint32_t> none;
-    return pre_finish(ctx, nullptr, none);
+    return pre_finish(ctx);
 }
 }  // namespace
 
@@ -937,10 +789,8 @@ extern "C" int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, cons
                                                    const int32_t *out_cap, int32_t *out_len, int32_t *status, uint32_t flags)
 {
     if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
-    for (int b = 0; b < n; b++) {
-        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
-        if (jpk_cli_stages_bound(in_len[b]) > 0x7fffffff) return JPK_E_ARG;
-    }
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    for (int b = 0; b < n; b++) if (jpk_cli_stages_bound(in_len[b]) > 0x7fffffff) return JPK_E_ARG;
     JPK_TRY(pre_enter(ctx));
     if (n == 0) return JPK_OK;
     std::vector<int32_t> lens((size_t)n), st_local((size_t)n), s1((size_t)n);
@@ -960,7 +810,7 @@ extern "C" int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, cons
         out_len[b] = stp[b] == JPK_OK ? (int32_t)total : 0;
     }
     JPK_TRY(cli_stages_run(ctx, n, d_in, lens.data(), nullptr, d_out, flags, nullptr, dedupe ? &dc : nullptr, s1.data()));
-    return status ? JPK_OK : first_status(n, stp);
+    return finish_statuses(n, status, stp);
 }
 
 extern "C" int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
@@ -975,13 +825,13 @@ extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint
     JPK_TRY(pre_enter(ctx));
     if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
     if (n == 0) return JPK_OK;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
     std::vector<PreJob> jobs((size_t)n);
     std::vector<uint32_t> nfb((size_t)n);
     uint64_t wgs = 0, bytes = 0;
     for (int b = 0; b < n; b++) {
-        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b]) || (out_cap[b] > 0 && !d_out[b])) return JPK_E_ARG;
         jobs[(size_t)b] = PreJob{d_in[b], d_out[b], in_len[b], out_cap[b], (uint32_t)wgs, 0u};
-        nfb[(size_t)b] = (uint32_t)(((int64_t)in_len[b] + FBS + 1) / (FBS + 2));
+        nfb[(size_t)b] = pre::filter_blocks(in_len[b]);
         wgs += nfb[(size_t)b];
         bytes += (uint32_t)in_len[b];
     }
@@ -1000,5 +850,5 @@ extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint
         stp[b] = m == 0xFFFFFFFFu ? JPK_OK : ((m & 1u) ? JPK_E_CAPACITY : JPK_E_CORRUPT);
         out_len[b] = stp[b] == JPK_OK ? in_len[b] - 2 * (int32_t)nfb[(size_t)b] : 0;
     }
-    return status ? JPK_OK : first_status(n, stp);
+    return finish_statuses(n, status, stp);
 }

@@ -46,6 +46,11 @@ def lpx_cases(gpu):
         for n in LPX_LENS:
             t = make(jam, kind, n, 81)
             out.append((f"{kind}/{n}", t, jam.Lpx().encode(t)))
+    # the seams of the kernel's walk: parts of exactly one tile (16 KiB), one tile + 1, exactly the ring (80 KiB), the ring + 1
+    for kind in ("zero", "repeat4k"):
+        for n in (65_536, 65_540, 327_680, 327_684):
+            t = make(jam, kind, n, 82)
+            out.append((f"seam {kind}/{n}", t, jam.Lpx().encode(t)))
     return out
 
 

@@ -198,6 +198,10 @@ def test_lpx_every_length_and_content(gpu):
     # parts longer than the 64 KiB + one tile of output history the kernel keeps
     cases.append(("text 360001", jam.corpus.make("text", 360_001, 94), 360_001))
     cases.append(("zero 400000", np.zeros(400_000, np.uint8), 400_000))
+    # the seams of the kernel's walk: parts of exactly one tile (16 KiB), one tile + 1, exactly the ring (80 KiB), the ring + 1
+    for n in (65_536, 65_540, 327_680, 327_684):
+        cases.append((f"seam zero {n}", np.zeros(n, np.uint8), n))
+        cases.append((f"seam repeat4k {n}", jam.corpus.make("repeat4k", n, 95), n))
     st = _run(gpu, "lpx", cases)
     assert all(rc == OK for rc in st), st
 
