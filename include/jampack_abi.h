@@ -186,7 +186,8 @@ JPK_API uint32_t jpk_checksum_host(const uint8_t *p, int32_t size);
 JPK_API int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed);
 
 /* The stages the stock CLI's decoder undoes behind its inverse BWT, written WITHOUT match finding or filter selection (the format
- * lets LZ77 and Filters be written as "stored"; Lpx::Encode runs exactly).  For a raw block R of n bytes:
+ * lets LZ77 and Filters be written as "stored"; Lpx::Encode runs exactly; the _ex forms below add a dedupe and a filter choice as
+ * options).  For a raw block R of n bytes:
  *   S1 = 04 80 | R                  the LZ77 end token (offset 0: the rest are literals, lz77.cpp:620, 705-711)
  *   S2 = every 64 KiB piece of S1 behind a 00 00 header (raw, filters.cpp:421-426); split as filters.cpp:245
  *   S3 = Lpx::Encode(S2),  S4 = 04 80 | S3
@@ -214,6 +215,19 @@ JPK_API int jpk_lz77_dedupe(const uint8_t *in, int32_t n, uint8_t *out, int32_t 
  * unchanged (stored filter pieces over S1, Lpx::Encode, stored second LZ77), so out_len depends on the data and jpk_cli_stages_bound /
  * jpk_jam_cli_compress_bound stay bounds.  flags = 0 is the entry without _ex, byte for byte; any other bit is JPK_E_ARG. */
 #define JPK_CLI_DEDUPE 1
+/* JPK_CLI_FILTERS: every 64 KiB piece of S1 (of the dedupe's S1' with both flags) goes through the filter choice of DESIGN 4.7 "Filters" and
+ * leaves as `type, width | transformed piece` (type 0 = reorder + delta, type 2 = in-place delta, widths 1..32) when a candidate's integer
+ * order-0 cost beats the raw piece's by more than a sixteenth, as `00 00 | piece` otherwise.  Lengths do not change.  It is bit 2, not bit
+ * 1: the values 2 and 3 were refused before this flag existed and stay refused (tests/test_dedupe_host.py pins them).  The accepted values
+ * of flags are exactly 0, 1, 4 and 5. */
+#define JPK_CLI_FILTERS 4
+#define JPK_CLI_FLAGS_OK(f) (((f) & ~(uint32_t)(JPK_CLI_DEDUPE | JPK_CLI_FILTERS)) == 0u)
+/* Filters::Encode (filters.hpp:43) with that choice: S2 of in_len bytes of S1, *out_len = in_len + 2 * ceil(in_len / 65536); JPK_E_CAPACITY
+ * (nothing written) when out_cap is below it.  jpk_filters_decode gives `in` back, and so does the reference's Filters::Decode. */
+JPK_API int jpk_filters_encode(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len);
+/* the rule's cost (1/4096 bit) of one candidate for one piece of len bytes in [1, 65536]: type 0 or 2 at width 1..32, width 0 = raw (type
+ * ignored); computed from the candidate's actual output bytes.  JPK_E_ARG otherwise. */
+JPK_API int jpk_filters_cost(const uint8_t *piece, int32_t len, int32_t type, int32_t width, int64_t *cost);
 JPK_API int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
 JPK_API int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
 
@@ -345,6 +359,12 @@ JPK_API int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t *c
  *   every block's length from its result (one host read for all blocks); out_len[b] = the host form's */
 JPK_API int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                                 const int32_t *out_cap, int32_t *out_len, int32_t *status, uint32_t flags);
+/*   jpk_filters_encode of n blocks of S1, the bytes and statuses of the host form, one launch (k_enc_filters: one workgroup per 64 KiB
+ *   piece -- the piece and the 65 histograms in LDS, the costs, the choice, the transformed piece by destination).  A block whose out_cap
+ *   is below in_len + 2 * ceil(in_len / 65536) reports JPK_E_CAPACITY alone, out_len[b] = 0, and nothing of it is written.  With
+ *   JPK_CLI_FILTERS the _ex writer entries run the same kernel in the place of k_enc_wrap; no host read is added. */
+JPK_API int jpk_dev_blocks_filters_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                          const int32_t *out_cap, int32_t *out_len, int32_t *status);
 /* Jampack::Decompress (jampack.cpp:262-336) of an archive written by an unmodified `jampack c` (any -m / -f setting; the frames of
  * jpk_jam_cli_block_read, back to back): the frame walk of jpk_dev_jam_decompress, with an entropy-decoded size of at most
  * 1.05 x BlockSize + 4096 per frame (the reference's stage buffers, jampack.cpp:156), then per pass jpk_dev_blocks_decompress into
@@ -383,7 +403,8 @@ JPK_API int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t bloc
 /* The same with flags (JPK_CLI_DEDUPE): the frames of jpk_jam_cli_block_write_ex over the slices.  With the dedupe a pass runs the k_dd_*
  * launches from the raw slices into slot B, reads the pass's S1' lengths on the host -- jpk_dev_blocks_compress wants host lengths: ONE
  * synchronisation per pass, never one per frame -- and goes on with k_enc_wrap from B into A and k_enc_lpx from A into B at those lengths.
- * The dedupe's scratch (about 1.2 bytes per input byte of the pass) comes from ctx's arena. */
+ * The dedupe's scratch (about 1.2 bytes per input byte of the pass) comes from ctx's arena.  With JPK_CLI_FILTERS k_enc_filters runs in the
+ * place of k_enc_wrap, on the raw slices or on the dedupe's S1'; the lengths do not depend on its choices, so a pass gains no host read. */
 JPK_API int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
                                         int64_t *out_len, int32_t in_flight, uint32_t flags);
 JPK_API int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,

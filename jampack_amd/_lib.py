@@ -81,6 +81,8 @@ _SIGS = {
     "jpk_jam_cli_block_write": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_lz77_dedupe": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_cli_stages_encode_ex": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p, C.c_uint32]),
+    "jpk_filters_encode": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p]),
+    "jpk_filters_cost": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "jpk_jam_cli_block_write_ex": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, _i32p, C.c_uint32]),
     "jpk_dev_bwt_forward": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _i32p]),
     "jpk_dev_bwt_inverse": (C.c_int, [_vp, _vp, C.c_int32, _vp, C.c_int32, _i32p]),
@@ -121,6 +123,7 @@ _SIGS = {
     "jpk_jam_cli_compress": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32]),
     "jpk_dev_blocks_lz77_dedupe": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
     "jpk_dev_blocks_cli_stages_encode_ex": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p, C.c_uint32]),
+    "jpk_dev_blocks_filters_encode": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
     "jpk_dev_jam_cli_compress_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
     "jpk_jam_cli_compress_ex": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
     "jpk_dev_jam_cli_decompress": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),

@@ -315,7 +315,18 @@ class Lpx:
 
 
 class Filters:
-    """Decoder side of `class Filters` (filters.hpp:43-44); host code."""
+    """`class Filters` (filters.hpp:43-44); host code.  Encode picks a delta filter per 64 KiB piece by this library's own integer cost
+    ("Filters"), not by the reference's heuristic; every decoder of the format reads what it writes."""
+
+    def Encode(self, buf) -> np.ndarray:
+        t = _np_u8(buf)
+        cap = len(t) + 2 * -(-len(t) // 65_536)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n = C.c_int32(0)
+        _chk(lib().jpk_filters_encode(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "Filters::Encode")
+        return out[: n.value]
+
+    encode = Encode
 
     def Decode(self, buf, cap: int) -> np.ndarray:
         t = _np_u8(buf)
@@ -323,6 +334,14 @@ class Filters:
         n = C.c_int32(0)
         _chk(lib().jpk_filters_decode(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n)), "Filters::Decode")
         return out[: n.value]
+
+
+def filters_cost(piece, type: int, width: int) -> int:
+    """jpk_filters_cost: the writer's cost (1/4096 bit) of one filter candidate for one piece of 1..65536 bytes; width 0 = raw"""
+    t = _np_u8(piece)
+    c = C.c_int64(0)
+    _chk(lib().jpk_filters_cost(_ptr(t), len(t), type, width, C.byref(c)), "jpk_filters_cost")
+    return c.value
 
 
 def checksum_host(buf) -> int:
@@ -348,27 +367,33 @@ def cli_stages_bound(n: int) -> int:
 
 
 CLI_DEDUPE = 1        # JPK_CLI_DEDUPE
+CLI_FILTERS = 4       # JPK_CLI_FILTERS (bit 2: the values 2 and 3 stay refused)
 
 
-def cli_stages_encode(block, cap: int | None = None, dedupe: bool = False) -> np.ndarray:
+def _cli_flags(dedupe: bool, filters: bool) -> int:
+    return (CLI_DEDUPE if dedupe else 0) | (CLI_FILTERS if filters else 0)
+
+
+def cli_stages_encode(block, cap: int | None = None, dedupe: bool = False, filters: bool = False) -> np.ndarray:
     """jpk_cli_stages_encode_ex: end token | Lpx::Encode(raw filter pieces of (end token | block)) -- what the stock decoder's four
-    pre-stage decoders turn back into `block`; host code.  dedupe: Lz77().dedupe(block) in place of (end token | block)."""
+    pre-stage decoders turn back into `block`; host code.  dedupe: Lz77().dedupe(block) in place of (end token | block).  filters:
+    Filters().Encode in place of the raw pieces."""
     t = _np_u8(block)
     cap = cli_stages_bound(len(t)) if cap is None else cap
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     n = C.c_int32(0)
-    _chk(lib().jpk_cli_stages_encode_ex(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n), CLI_DEDUPE if dedupe else 0), "jpk_cli_stages_encode_ex")
+    _chk(lib().jpk_cli_stages_encode_ex(_ptr(t), len(t), out.ctypes.data, cap, C.byref(n), _cli_flags(dedupe, filters)), "jpk_cli_stages_encode_ex")
     return out[: n.value]
 
 
-def jam_cli_block_write(block, block_size: int, cap: int | None = None, dedupe: bool = False) -> np.ndarray:
+def jam_cli_block_write(block, block_size: int, cap: int | None = None, dedupe: bool = False, filters: bool = False) -> np.ndarray:
     """One frame an unmodified `jampack d` decodes: the header of jam_block_write + block_compress of the stage chain of `block`
-    (dedupe: with long repeats taken out first, cli_stages_encode)."""
+    (dedupe: with long repeats taken out first, filters: with a delta filter chosen per 64 KiB piece; cli_stages_encode)."""
     t = _np_u8(block)
     cap = JAM_HEADER + ans_capacity(cli_stages_bound(len(t)) + TRAILER) if cap is None else cap
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     n = C.c_int32(0)
-    _chk(lib().jpk_jam_cli_block_write_ex(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n), CLI_DEDUPE if dedupe else 0), "jam_cli_block_write")
+    _chk(lib().jpk_jam_cli_block_write_ex(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n), _cli_flags(dedupe, filters)), "jam_cli_block_write")
     return out[: n.value]
 
 
@@ -379,14 +404,15 @@ def jam_cli_compress_bound(n: int, block_size: int = 8 << 20) -> int:
     return b
 
 
-def jam_cli_compress(data, block_size: int = 8 << 20, dedupe: bool = False) -> np.ndarray:
+def jam_cli_compress(data, block_size: int = 8 << 20, dedupe: bool = False, filters: bool = False) -> np.ndarray:
     """The archive an unmodified `jampack d` decodes, made by one jpk_jam_cli_compress_ex call: frames of block_size input bytes, the
     pre-stages written in their stored forms + Lpx::Encode on the GPU, then the batch engine.  dedupe: repeats of >= 256 bytes inside
-    a block leave as LZ77 tokens in front of the BWT (the k_dd_* kernels)."""
+    a block leave as LZ77 tokens in front of the BWT (the k_dd_* kernels).  filters: every 64 KiB piece goes through the filter choice
+    (k_enc_filters in the place of k_enc_wrap)."""
     t = _np_u8(data)
     out = np.empty(max(jam_cli_compress_bound(len(t), block_size), 1), dtype=np.uint8)
     n = C.c_int64(0)
-    _chk(lib().jpk_jam_cli_compress_ex(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0, CLI_DEDUPE if dedupe else 0), "jam_cli_compress")
+    _chk(lib().jpk_jam_cli_compress_ex(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0, _cli_flags(dedupe, filters)), "jam_cli_compress")
     return out[: n.value]
 
 
@@ -556,16 +582,20 @@ class Context:
         _chk(lib().jpk_dev_blocks_lpx_encode(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*lens), P(*[_dptr(x) for x in d_outs]), st), "jpk_dev_blocks_lpx_encode")
         return list(st)[:n]
 
-    def blocks_cli_stages_encode(self, d_ins, in_lens, d_outs, out_caps, dedupe: bool = False):
+    def blocks_cli_stages_encode(self, d_ins, in_lens, d_outs, out_caps, dedupe: bool = False, filters: bool = False):
         """jpk_dev_blocks_cli_stages_encode_ex: the stage chain of independent blocks (two launches; dedupe: the k_dd_* launches and one
-        host read of the lengths in front of them) -> (out_len list, status list)"""
-        fl = CLI_DEDUPE if dedupe else 0
+        host read of the lengths in front of them; filters: k_enc_filters as the first of the two) -> (out_len list, status list)"""
+        fl = _cli_flags(dedupe, filters)
         fn = lib().jpk_dev_blocks_cli_stages_encode_ex
         return self._batch(lambda *a: fn(*a, fl), "jpk_dev_blocks_cli_stages_encode_ex", d_ins, in_lens, d_outs, out_caps)
 
     def blocks_lz77_dedupe(self, d_ins, in_lens, d_outs, out_caps):
         """jpk_dev_blocks_lz77_dedupe: Lz77().dedupe of independent blocks -> (out_len list, status list)"""
         return self._batch(lib().jpk_dev_blocks_lz77_dedupe, "jpk_dev_blocks_lz77_dedupe", d_ins, in_lens, d_outs, out_caps)
+
+    def blocks_filters_encode(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_filters_encode: Filters().Encode of independent blocks in one launch -> (out_len list, status list)"""
+        return self._batch(lib().jpk_dev_blocks_filters_encode, "jpk_dev_blocks_filters_encode", d_ins, in_lens, d_outs, out_caps)
 
     def blocks_filters_decode(self, d_ins, in_lens, d_outs, out_caps):
         """jpk_dev_blocks_filters_decode: Filters::Decode of independent blocks in one launch -> (out_len list, status list)"""
@@ -611,11 +641,11 @@ class Context:
         _chk(lib().jpk_dev_jam_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight), "jpk_dev_jam_compress")
         return n.value
 
-    def jam_cli_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0, dedupe: bool = False) -> int:
+    def jam_cli_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0, dedupe: bool = False, filters: bool = False) -> int:
         """jpk_dev_jam_cli_compress_ex: the archive of d_in[0..in_len) an unmodified `jampack d` decodes, into d_out; returns its length"""
         n = C.c_int64(0)
         _chk(lib().jpk_dev_jam_cli_compress_ex(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight,
-                                               CLI_DEDUPE if dedupe else 0), "jpk_dev_jam_cli_compress_ex")
+                                               _cli_flags(dedupe, filters)), "jpk_dev_jam_cli_compress_ex")
         return n.value
 
     def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):

@@ -112,7 +112,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
     "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
-    "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit",
+    "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit", "k_enc_filters",
     "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
@@ -1836,7 +1836,7 @@ extern "C" int jpk_jam_cli_block_read(const uint8_t *in, int32_t in_len, uint8_t
 // pre-stage encoders (jampack.cpp:36-39), ForwardBwt + Ans::Encode on the GPU, the header of CompWriteBlock (jampack.cpp:122-135).
 extern "C" int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
 {
-    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!jpk_jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
     if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
     const int32_t cap = (int32_t)jpk_cli_stages_bound(in_len);                       // < 2^31 for in_len <= JPK_MAX_BLOCKSIZE (prestage.cpp)

@@ -36,7 +36,7 @@ enum JpkProfId {
     PROF_INV_HIST, PROF_INV_BUILD, PROF_INV_WALK, PROF_INV_RANK, PROF_INV_COPY,
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
     PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM,
-    PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT,
+    PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT, PROF_ENC_FILTERS,
     PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
@@ -277,5 +277,6 @@ int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_
 // nullptr: in ctx's arena) -> S4 = end token | Lpx::Encode(S2) (k_enc_lpx) into d_out[b] (jpk_cli_stages_bound bytes); in_len[b] < 0
 // skips block b.  Two launches; synchronises the stream.  flags & JPK_CLI_DEDUPE: the k_dd_* launches first, R -> S1' into d_out[b], one host
 // read of the lengths, then k_enc_wrap from d_out[b] and k_enc_lpx back into it.  s4_len[b] (nullable) = |S4| of block b.
+// flags & JPK_CLI_FILTERS: k_enc_filters in the place of k_enc_wrap, same sources, same lengths.
 int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out,
                           uint32_t flags, int32_t *s4_len);

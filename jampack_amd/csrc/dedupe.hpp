@@ -54,7 +54,7 @@ JPK_HD bool equal_w(const uint8_t *a, const uint8_t *b)
 
 // the offset position p is a candidate for, from its fingerprint: the anchor q in its slot lies a whole window in front and holds the
 // same 64 bytes (d = p - q >= 64); 0: none
-JPK_HD uint32_t cand_fp(const uint8_t *in, uint32_t n, const uint32_t *table, int bits, uint32_t p, uint32_t fp)
+JPK_HD uint32_t cand_fp(const uint8_t *in, uint32_t /* n */, const uint32_t *table, int bits, uint32_t p, uint32_t fp)
 {
     const uint32_t q = table[slot(fp, bits)];
     if (q == EMPTY || q + W > p) return 0u;

@@ -18,7 +18,8 @@
 // The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
 // the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
 // of the raw slices.  With JPK_CLI_DEDUPE the k_dd_* launches come first (raw slice -> S1' in slot B), the pass's S1' lengths are read
-// on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.
+// on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.  With JPK_CLI_FILTERS
+// k_enc_filters stands where k_enc_wrap does; the lengths are the same.
 
 // one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
 struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
@@ -236,7 +237,7 @@ int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t 
                      int32_t in_flight, bool cli, uint32_t flags = 0u)
 {
     JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
     *out_len = 0;
     const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
@@ -332,7 +333,7 @@ int jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *len,
 int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli,
                       uint32_t flags = 0u)
 {
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;
     *out_len = 0;
     jpk_ctx *ctx;

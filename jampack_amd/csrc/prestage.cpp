@@ -3,9 +3,10 @@
 // frames written by an unmodified `jampack c` decode end to end: rANS decode + inverse BWT on the GPU, these on the
 // host where SURVEY.md section 8f (row 4) puts them -- byte-serial state machines with no data parallelism.
 // The encoder side is the part of the reference's encoders that a VALID stream needs and no more (writing): the stored forms
-// of LZ77 and Filters, and Lpx::Encode, which has no stored form and is deterministic integer code; and, as an option of the writer, a dedupe of
-// long repeats in the token format of the first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp's, not the reference's hash walk).  The
-// match finders and the filter selection with their float heuristics stay with the reference.
+// of LZ77 and Filters, and Lpx::Encode, which has no stored form and is deterministic integer code; and, as options of the writer, a dedupe of
+// long repeats in the token format of the first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp's, not the reference's hash walk) and a
+// choice among the delta filters per 64 KiB piece (jpk_filters_encode; an integer order-0 cost of this library's own, prestage_rules.hpp).
+// The match finders and the reference's filter selection with their float heuristics stay with the reference.
 //
 // Unlike the reference (which trusts its input outside NDEBUG builds, lz77.cpp:697-701) every read and write is
 // bounds checked and a bad stream gives JPK_E_CORRUPT / JPK_E_CAPACITY.
@@ -117,12 +118,77 @@ extern "C" int jpk_filters_decode(const uint8_t *in, int32_t in_len, uint8_t *ou
     return JPK_OK;
 }
 
-// ---- the stage chain of a frame the stock CLI decodes, written without match finding or filter selection (writing) -------
+// ---- Filters::Encode with this library's own choice ("Filters"; the rule is prestage_rules.hpp) ----------------------------
+namespace {
+
+// The choice for the piece x[0..len): the differences at distance w are counted once per width, and the histograms of both types' outputs
+// come from them by pre::filter_fixups -- the shape k_enc_filters has; jpk_filters_cost counts a candidate's output bytes themselves.
+pre::FilterChoice filters_choose(const uint8_t *x, uint32_t len)
+{
+    uint32_t raw[256] = {0}, d[256], h[256];
+    int64_t cost[pre::FILTER_CANDS];
+    for (uint32_t i = 0; i < len; i++) raw[x[i]]++;
+    const auto get = [x](uint32_t i) { return (uint32_t)x[i]; };
+    for (uint32_t w = 1; w <= pre::FILTER_WIDTHS; w++) {
+        memset(d, 0, sizeof d);
+        for (uint32_t i = w; i < len; i++) d[(uint8_t)(x[i] - x[i - w])]++;
+        for (uint32_t type = 0; type <= 2u; type += 2u) {
+            memcpy(h, d, sizeof h);
+            pre::filter_fixups(get, len, type, w, [&h](uint8_t b, int s) { h[b] += (uint32_t)s; });
+            cost[(type / 2u) * pre::FILTER_WIDTHS + w - 1u] = pre::filter_cost(h, len);
+        }
+    }
+    return pre::filter_choose(pre::filter_cost(raw, len), [&cost](uint32_t type, uint32_t w) { return cost[(type / 2u) * pre::FILTER_WIDTHS + w - 1u]; });
+}
+
+// one piece of S2: two header bytes and len bytes into dst, which does not overlap x
+void filters_encode_piece(const uint8_t *x, uint32_t len, uint8_t *dst)
+{
+    const pre::FilterChoice ch = filters_choose(x, len);
+    dst[0] = (uint8_t)ch.type; dst[1] = (uint8_t)ch.width;
+    if (ch.width == 0) { memcpy(dst + 2, x, len); return; }
+    const auto get = [x](uint32_t i) { return (uint32_t)x[i]; };
+    for (uint32_t pos = 0; pos < len; pos++) dst[2 + pos] = pre::filter_byte(get, len, ch.type, ch.width, pos);
+}
+
+}  // namespace
+
+extern "C" int jpk_filters_encode(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    constexpr int64_t FBS = pre::FBS;
+    const int64_t total = (int64_t)in_len + 2 * (((int64_t)in_len + FBS - 1) / FBS);
+    if (total > 0x7fffffff) return JPK_E_ARG;
+    if (total > out_cap) return JPK_E_CAPACITY;
+    int64_t op = 0;
+    for (int64_t i = 0; i < in_len;) {
+        const int64_t len = (i + FBS < in_len) ? FBS : in_len - i;
+        filters_encode_piece(in + i, (uint32_t)len, out + op);
+        op += 2 + len;
+        i += len;
+    }
+    *out_len = (int32_t)op;
+    return JPK_OK;
+}
+
+extern "C" int jpk_filters_cost(const uint8_t *piece, int32_t len, int32_t type, int32_t width, int64_t *cost)
+{
+    if (!piece || !cost || len < 1 || len > (int32_t)pre::FBS || width < 0 || width > (int32_t)pre::FILTER_WIDTHS) return JPK_E_ARG;
+    if (width > 0 && type != 0 && type != 2) return JPK_E_ARG;
+    uint32_t h[256] = {0};
+    const auto get = [piece](uint32_t i) { return (uint32_t)piece[i]; };
+    for (uint32_t pos = 0; pos < (uint32_t)len; pos++) h[pre::filter_byte(get, (uint32_t)len, (uint32_t)type, (uint32_t)width, pos)]++;
+    *cost = pre::filter_cost(h, (uint32_t)len);
+    return JPK_OK;
+}
+
+// ---- the stage chain of a frame the stock CLI decodes, written without match finding (writing) -----------------------------
 //   S1 = end token | R          the token is what the reference's own flush writes, WriteToken(MIN_MATCH, MIN_MATCH, 0) (lz77.cpp:620,
 //                               53-70): token byte (4 - 4) << 3 | 4 = 0x04, then EncodeLeb128(0) = 0x80 (utils.cpp:28-31).  Offset 0 makes
 //                               Lz77::Decompress copy the rest through (lz77.cpp:705-711).
 //   S2 = every 64 KiB piece of S1 behind a 00 00 header (type 0, width 0 = raw, filters.cpp:421-426, 480-483); the split is the
 //                               encoder's own (filters.cpp:245): all pieces but the last are full, an exactly full last piece stays one
+//                               (JPK_CLI_FILTERS: behind `type, width` and transformed where the choice above finds a filter; same length)
 //   S3 = Lpx::Encode(S2)        same length
 //   S4 = end token | S3
 // |S2| = n + 2 + 2 P with P = ceil((n + 2) / 65536) pieces (n + 2 >= 2: at least one), |S4| = n + 4 + 2 P.
@@ -138,14 +204,15 @@ extern "C" int64_t jpk_cli_stages_bound(int64_t n)
 }
 
 // S4 of S1 = head | body: the filter pieces, Lpx::Encode, the second end token
-static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len)
+static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len,
+                           bool filters)
 {
     constexpr int64_t FBS = pre::FBS;
     const int64_t s1 = nhead + nbody, total = pre::s4_of_s1(s1), s2 = total - 2;
     if (total > 0x7fffffff) return JPK_E_ARG;
     if (total > out_cap) return JPK_E_CAPACITY;
-    std::vector<uint8_t> buf;
-    try { buf.resize((size_t)s2); } catch (...) { return JPK_E_ALLOC; }
+    std::vector<uint8_t> buf, piece;
+    try { buf.resize((size_t)s2); if (filters) piece.resize((size_t)FBS); } catch (...) { return JPK_E_ALLOC; }
     int64_t op = 0;
     for (int64_t i = 0; i < s1;) {                                     // byte i of S1: head[i], then body[i - nhead]
         const int64_t len = (i + FBS < s1) ? FBS : s1 - i;
@@ -155,6 +222,10 @@ static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *bo
         int64_t k = 0;
         for (; i + k < nhead && k < len; k++) buf[(size_t)(op + k)] = head[i + k];
         if (len > k) memcpy(buf.data() + op + k, body + (i + k - nhead), (size_t)(len - k));
+        if (filters) {
+            memcpy(piece.data(), buf.data() + op, (size_t)len);
+            filters_encode_piece(piece.data(), (uint32_t)len, buf.data() + op - 2);
+        }
         op += len;
         i += len;
     }
@@ -218,15 +289,16 @@ extern "C" int jpk_lz77_dedupe(const uint8_t *in, int32_t n, uint8_t *out, int32
 
 extern "C" int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
 {
-    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (jpk_cli_stages_bound(n) > 0x7fffffff) return JPK_E_ARG;
-    if (!(flags & JPK_CLI_DEDUPE)) return cli_stages_from(pre::END_TOKEN, 2, in, n, out, out_cap, out_len);
+    const bool filters = (flags & JPK_CLI_FILTERS) != 0;
+    if (!(flags & JPK_CLI_DEDUPE)) return cli_stages_from(pre::END_TOKEN, 2, in, n, out, out_cap, out_len, filters);
     std::vector<uint8_t> s1;
     try { s1.resize((size_t)n + 2); } catch (...) { return JPK_E_ALLOC; }
     int32_t m = 0;
     const int rc = jpk_lz77_dedupe(in, n, s1.data(), n + 2, &m);       // |S1'| <= n + 2: every token pays for itself
     if (rc != JPK_OK) return rc;
-    return cli_stages_from(nullptr, 0, s1.data(), m, out, out_cap, out_len);
+    return cli_stages_from(nullptr, 0, s1.data(), m, out, out_cap, out_len, filters);
 }
 
 extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)

@@ -4,11 +4,13 @@
 //   k_lpx<false>   Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
 //                  (k_pre_lpx in the profiler's table and in DESIGN 4.7)
 //   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
-// and the two kernels of the writer of such frames (writing; the stage chain of jpk_cli_stages_encode):
+// and the kernels of the writer of such frames (writing; the stage chain of jpk_cli_stages_encode):
 //   k_enc_wrap     raw block -> S2: the LZ77 end token and the 00 00 header of every 64 KiB filter piece around the unchanged bytes,
 //                  organised by destination like k_jam_pack: a thread owns aligned 16-byte words of the output
 //   k_lpx<true>    Lpx::Encode      (lpx.cpp:56-99, 148-158) one workgroup per part, the other instance of the decoder's kernel (k_enc_lpx
 //                  in the profiler's table)
+//   k_enc_filters  S1 -> S2 with a filter chosen per 64 KiB piece (JPK_CLI_FILTERS: in the place of k_enc_wrap): the piece and the 65
+//                  histograms of the candidates in LDS, the integer cost, the choice, the transformed piece by destination
 // and the dedupe of the writer's first LZ77 stage (jpk_lz77_dedupe; the rule is dedupe.hpp, shared with the host form):
 //   k_dd_anchor    every aligned 64-byte window into its slot of the block's table, atomicMin on the position
 //   k_dd_cand      one workgroup per tile of 1024 positions: fingerprints of all positions by six doubling steps in LDS, the candidate offset
@@ -292,6 +294,95 @@ template <bool TOK> __global__ __launch_bounds__(PRE_TB) void k_enc_wrap(const P
         }
     }
 }
+
+// ---- the filter choice: S1 -> S2 (Filters::Encode with the rule of prestage_rules.hpp, DESIGN 4.7 "Filters") ---------------------------
+constexpr uint32_t FLT_RAW = pre::FILTER_CANDS;                       // histogram and cost of the raw piece, behind the 64 candidates'
+constexpr uint32_t FLT_HISTS = pre::FILTER_CANDS + 1;
+
+// One workgroup per 64 KiB piece of S1; piece j of a block reads at j 65536 and writes at j (65536 + 2).  Job: in = R (TOK: S1 = 04 80 | R)
+// or S1 itself (the dedupe's, the batch entry's), in_len its bytes, out = S2, out_cap its room.  The piece (64 KiB) and 65 histograms of 256
+// words (65 KiB) live in LDS: one workgroup per CU.
+//   1 the raw histogram and, per width w, that of the differences x[k] - x[k - w]: a thread takes four positions from nine aligned words
+//   2 the differences copied for type 2, then one thread per candidate applies pre::filter_fixups to its histogram
+//   3 a wave per candidate, a lane per four byte values: pre::cost_term summed over the wave (integer sums: any order gives the host's)
+//   4 thread 0 walks pre::filter_choose and writes the header; all threads write pre::filter_byte by destination
+// Every piece byte read is below len, every write inside [out, out + out_cap).
+template <bool TOK> __global__ __launch_bounds__(PRE_TB) void k_enc_filters(const PreJob *__restrict__ jobs, uint32_t n)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t s[FBS];
+    __shared__ uint32_t hist[FLT_HISTS][256];
+    __shared__ long long cost[FLT_HISTS];
+    __shared__ uint32_t pick[2];
+    const uint32_t tid = threadIdx.x;
+    const PreJob jb = jobs[job_of(jobs, n, blockIdx.x)];
+    const int64_t s1 = (int64_t)jb.in_len + (TOK ? 2 : 0);
+    const uint32_t j = blockIdx.x - jb.wg0;
+    const int64_t i0 = (int64_t)j * FBS;
+    if (i0 >= s1) return;
+    const uint32_t len = s1 - i0 < (int64_t)FBS ? (uint32_t)(s1 - i0) : FBS;
+    const int64_t op = (int64_t)j * (FBS + 2);
+    if (op + 2 + (int64_t)len > (int64_t)jb.out_cap) return;           // the host sized the output: cannot happen, and nothing is written if it does
+    uint8_t *dst = jb.out + op;
+    for (uint32_t k = tid; k < len; k += PRE_TB) {
+        const int64_t g = i0 + k;
+        if (TOK) s[k] = g < 2 ? (g == 0 ? pre::END_TOKEN[0] : pre::END_TOKEN[1]) : jb.in[g - 2];
+        else s[k] = jb.in[g];
+    }
+    for (uint32_t k = tid; k < FLT_HISTS * 256u; k += PRE_TB) (&hist[0][0])[k] = 0u;
+    __syncthreads();
+    const uint32_t *s32 = reinterpret_cast<const uint32_t *>(s);
+    for (uint32_t b4 = tid; b4 * 4u < len; b4 += PRE_TB) {             // positions 4 b4 .. 4 b4 + 3 and the 32 bytes in front of them
+        uint32_t wd[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) wd[i] = b4 + (uint32_t)i >= 8u ? s32[b4 + (uint32_t)i - 8u] : 0u;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t k = b4 * 4u + (uint32_t)e;
+            if (k < len) {
+                const uint32_t v = (wd[8] >> (8 * e)) & 255u;
+                atomicAdd(&hist[FLT_RAW][v], 1u);
+#pragma unroll
+                for (int w = 1; w <= (int)pre::FILTER_WIDTHS; w++) {
+                    const int o = 32 + e - w;                          // byte k - w in wd
+                    if ((uint32_t)w <= k) atomicAdd(&hist[w - 1][(v - ((wd[o >> 2] >> (8 * (o & 3))) & 255u)) & 255u], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < pre::FILTER_WIDTHS * 256u; k += PRE_TB) (&hist[pre::FILTER_WIDTHS][0])[k] = (&hist[0][0])[k];
+    __syncthreads();
+    const uint8_t *x = s;
+    const auto get = [x](uint32_t i) { return (uint32_t)x[i]; };
+    if (tid < pre::FILTER_CANDS) {
+        uint32_t *h = hist[tid];                                       // this thread's alone
+        pre::filter_fixups(get, len, tid < pre::FILTER_WIDTHS ? 0u : 2u, (tid % pre::FILTER_WIDTHS) + 1u, [h](uint8_t b, int d) { h[b] += (uint32_t)d; });
+    }
+    __syncthreads();
+    const uint32_t lg_len = pre::lg12(len), lane = tid & 63u;
+    for (uint32_t c = tid >> 6; c < FLT_HISTS; c += PRE_TB / 64) {
+        long long a = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) a += pre::cost_term(hist[c][lane + 64u * q], lg_len);
+        for (int off = 32; off; off >>= 1) a += __shfl_xor(a, off, 64);
+        if (lane == 0) cost[c] = a;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const long long *cs = cost;
+        const pre::FilterChoice ch = pre::filter_choose((int64_t)cs[FLT_RAW], [cs](uint32_t type, uint32_t w) {
+            return (int64_t)cs[(type / 2u) * pre::FILTER_WIDTHS + w - 1u];
+        });
+        pick[0] = ch.type; pick[1] = ch.width;
+        dst[0] = (uint8_t)ch.type; dst[1] = (uint8_t)ch.width;
+    }
+    __syncthreads();
+    const uint32_t type = pick[0], width = pick[1];
+    for (uint32_t k = tid; k < len; k += PRE_TB) dst[2 + k] = pre::filter_byte(get, len, type, width, k);
+}
+
+// pieces of S1: the workgroups k_enc_filters needs for a block
+inline uint64_t filter_pieces(int64_t s1) { return (uint64_t)((s1 + FBS - 1) / FBS); }
 
 // ---- the dedupe ------------------------------------------------------------------------------------------------------------------
 // One block of a batch.  Every k_dd_* grid is (workgroups of the largest block, blocks): a workgroup past its block's end leaves at once.
@@ -717,6 +808,7 @@ extern "C" int jpk_dev_blocks_lpx_encode(jpk_ctx *ctx, int32_t n, const uint8_t 
 // in_len[b] < 0: the block is skipped.  The caller has checked that every jpk_cli_stages_bound fits its buffer and an int32.
 // flags & JPK_CLI_DEDUPE: dd_find and dd_emit first, S1' into d_out[b] (|S1'| < |S4|: it fits), and k_enc_wrap reads S1' from there at the
 // length the host has read; k_lpx<true> overwrites it behind k_enc_wrap in stream order.  s4_len[b] (nullable) = |S4|.
+// flags & JPK_CLI_FILTERS: k_enc_filters, one workgroup per piece of S1, takes the place of k_enc_wrap on the same two sources.
 namespace {
 using pre::s4_of_s1;
 
@@ -724,7 +816,7 @@ using pre::s4_of_s1;
 int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out, uint32_t flags,
                    int32_t *s4_len, DdCall *found, const int32_t *found_s1)
 {
-    const bool dedupe = (flags & JPK_CLI_DEDUPE) != 0;
+    const bool dedupe = (flags & JPK_CLI_DEDUPE) != 0, filters = (flags & JPK_CLI_FILTERS) != 0;
     std::vector<int32_t> s1((size_t)n);
     for (int b = 0; b < n; b++) s1[(size_t)b] = in_len[b] < 0 ? -1 : in_len[b] + 2;
     if (dedupe) {
@@ -762,7 +854,7 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
         wj[(size_t)b] = dedupe ? PreJob{d_out[b], mid, s1[(size_t)b], s2, (uint32_t)wwg, 0u} : PreJob{d_in[b], mid, in_len[b], s2, (uint32_t)wwg, 0u};
         lj[(size_t)b] = PreJob{mid, d_out[b] + 2, s2, s2, (uint32_t)lwg, 0u};
         const uint64_t words = (((uintptr_t)mid & 15u) + (uint64_t)s2 + 15u) / 16u;
-        wwg += (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
+        wwg += filters ? filter_pieces(s1[(size_t)b]) : (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
         lwg += pre::parts((uint32_t)s2);
         bytes += (uint32_t)s2;
     }
@@ -770,7 +862,9 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
     if (wwg) {
         JPK_HIP(hipMemcpyAsync(d_jobs, wj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
         JPK_HIP(hipMemcpyAsync(d_jobs + n, lj.data(), (size_t)n * sizeof(PreJob), hipMemcpyHostToDevice, ctx->stream));
-        if (dedupe) JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        if (filters && dedupe) JPK_LAUNCH(ctx, PROF_ENC_FILTERS, bytes, k_enc_filters<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        else if (filters) JPK_LAUNCH(ctx, PROF_ENC_FILTERS, bytes, k_enc_filters<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
+        else if (dedupe) JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         else JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_lpx<true>, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
     }
@@ -788,7 +882,7 @@ int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const
 extern "C" int jpk_dev_blocks_cli_stages_encode_ex(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                                    const int32_t *out_cap, int32_t *out_len, int32_t *status, uint32_t flags)
 {
-    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len)) || (flags & ~(uint32_t)JPK_CLI_DEDUPE)) return JPK_E_ARG;
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
     for (int b = 0; b < n; b++) if (jpk_cli_stages_bound(in_len[b]) > 0x7fffffff) return JPK_E_ARG;
     JPK_TRY(pre_enter(ctx));
@@ -817,6 +911,36 @@ extern "C" int jpk_dev_blocks_cli_stages_encode(jpk_ctx *ctx, int32_t n, const u
                                                 const int32_t *out_cap, int32_t *out_len, int32_t *status)
 {
     return jpk_dev_blocks_cli_stages_encode_ex(ctx, n, d_in, in_len, d_out, out_cap, out_len, status, 0u);
+}
+
+// Filters::Encode of n blocks of S1 with the writer's choice, one launch; the lengths do not depend on the choice, so nothing is read back
+extern "C" int jpk_dev_blocks_filters_encode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                             const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    std::vector<PreJob> jobs((size_t)n);
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    uint64_t wgs = 0, bytes = 0;
+    for (int b = 0; b < n; b++) {
+        const int64_t total = (int64_t)in_len[b] + 2 * (int64_t)filter_pieces(in_len[b]);
+        if (total > 0x7fffffff) return JPK_E_ARG;
+        stp[b] = total > out_cap[b] ? JPK_E_CAPACITY : JPK_OK;         // nothing of a block that does not fit is written
+        out_len[b] = stp[b] == JPK_OK ? (int32_t)total : 0;
+        jobs[(size_t)b] = stp[b] == JPK_OK ? PreJob{d_in[b], d_out[b], in_len[b], (int32_t)total, (uint32_t)wgs, 0u} : PreJob{nullptr, nullptr, 0, 0, (uint32_t)wgs, 0u};
+        if (stp[b] == JPK_OK) { wgs += filter_pieces(in_len[b]); bytes += (uint32_t)in_len[b]; }
+    }
+    if (wgs > 0x7fffffffull) return JPK_E_ARG;
+    if (wgs) {
+        PreCall pc;
+        JPK_TRY(pre_upload(ctx, jobs, 0, 0, &pc));
+        JPK_LAUNCH(ctx, PROF_ENC_FILTERS, bytes, k_enc_filters<false>, dim3((unsigned)wgs), dim3(PRE_TB), pc.d_jobs, (uint32_t)n);
+        JPK_TRY(pre_finish(ctx));
+    }
+    return finish_statuses(n, status, stp);
 }
 
 extern "C" int jpk_dev_blocks_filters_decode(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,

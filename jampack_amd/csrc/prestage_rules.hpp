@@ -1,6 +1,7 @@
 // prestage_rules.hpp -- the rules of the stock CLI's pre-stages that the host forms (prestage.cpp) and the kernels
 // (prestage_dev.hip) share, so that both compute the same bytes and the same statuses by construction: the LEB128 code, the LZ77 token,
-// the LPX model with its part cut and its one step, and the sizes and the LPC recurrence of the filter stage.  Pure functions, no HIP
+// the LPX model with its part cut and its one step, the sizes and the LPC recurrence of the filter stage, and the writer's choice among the
+// delta filters (its integer cost, the order of its walk, the transformed bytes).  Pure functions, no HIP
 // header: the file compiles with a plain C++17 compiler, where the serial walk of the LPX kernels runs under a sanitizer.  The copy
 // loops, scans and word assembly are shapes of their own and stay with their forms; the rule of the dedupe is dedupe.hpp.
 #pragma once
@@ -204,6 +205,94 @@ JPK_HD void lpc_decode(const uint8_t *src, uint8_t *dst, uint32_t len)
         p2 = p1;
         p1 = cur;
     }
+}
+
+// ---- filter choice of the writer ("Filters"): a rule of this library's own, not the reference's float heuristic ----------
+// Per piece x[0..len) of S1 the candidates are raw, type 0 (Reorder + DeltaEncode, filters.cpp:21-30, 85-91: the delta runs over the whole
+// reordered buffer, across channel borders) at widths 1..32 and type 2 (InlineDelta, filters.cpp:101-120) at widths 1..32; type 1 is never
+// written.  A candidate costs the order-0 code length of its len output bytes in units of 1/4096 bit, in integer arithmetic, so that host
+// and device choose alike; any choice decodes.
+constexpr uint32_t FILTER_WIDTHS = 32;                     // MAX_CHANNEL_WIDTH
+constexpr uint32_t FILTER_CANDS = 2 * FILTER_WIDTHS;       // candidate (type, width) has number (type / 2) * FILTER_WIDTHS + width - 1
+
+// 4096 log2 v for 1 <= v <= 65536, off by at most 1, exact at powers of two.  The fraction comes bit by bit from sixteen squarings of the
+// mantissa in Q31 (x < 2^32, so x * x fits 64 bits): floor(2^16 frac) up to the truncations, which weigh 2^-30 in all, rounded to 12 bits.
+JPK_HD uint32_t lg12(uint32_t v)
+{
+    const uint32_t k = 31u - (uint32_t)__builtin_clz(v);
+    uint64_t x = (uint64_t)v << (31u - k);
+    uint32_t f = 0;
+    for (int i = 0; i < 16; i++) {
+        x = (x * x) >> 31;
+        f <<= 1;
+        if (x >> 32) { x >>= 1; f |= 1u; }
+    }
+    return (k << 12) + ((f + 8u) >> 4);
+}
+
+// what a byte value that occurs h times among len output bytes adds to the cost, lg_len = lg12(len): h (lg12(len) - lg12(h))
+JPK_HD int64_t cost_term(uint32_t h, uint32_t lg_len) { return h ? (int64_t)h * ((int64_t)lg_len - (int64_t)lg12(h)) : 0; }
+
+// the cost of len output bytes with byte histogram h
+JPK_HD int64_t filter_cost(const uint32_t *h, uint32_t len)
+{
+    const uint32_t lg_len = lg12(len);
+    int64_t c = 0;
+    for (int s = 0; s < 256; s++) c += cost_term(h[s], lg_len);
+    return c;
+}
+
+// The choice: raw keeps a margin of 1/16 of its cost; type 0 at widths 1..32, then type 2 at widths 1..32, a candidate wins only strictly
+// below the best so far.  cost(type, width) is asked once per candidate, in that order.  width 0: the piece stays raw (00 00).
+struct FilterChoice { uint32_t type, width; };
+template <class Cost> JPK_HD FilterChoice filter_choose(int64_t raw_cost, Cost cost)
+{
+    FilterChoice ch = {0u, 0u};
+    int64_t best = raw_cost - (raw_cost >> 4);
+    for (uint32_t type = 0; type <= 2u; type += 2u)
+        for (uint32_t w = 1; w <= FILTER_WIDTHS; w++) {
+            const int64_t c = cost(type, w);
+            if (c < best) { best = c; ch.type = type; ch.width = w; }
+        }
+    return ch;
+}
+
+// Reorder: the piece index of position pos of its output.  Channel c holds x[c], x[c + width], ...: q = len / width elements, one more when
+// c < r = len mod width, so it starts at c q + min(c, r) -- the formula k_pre_filters reads by, inverted.
+JPK_HD uint32_t reorder_src(uint32_t len, uint32_t width, uint32_t pos)
+{
+    const uint32_t q = len / width, r = len % width, big = r * (q + 1u);
+    if (pos < big) return pos / (q + 1u) + (pos % (q + 1u)) * width;
+    const uint32_t p = pos - big;                                      // q >= 1 here: q == 0 means big == len
+    return r + p / q + (p % q) * width;
+}
+
+// byte pos of the candidate's output; x(i) = byte i of the piece.  width 0: raw.
+template <class Get> JPK_HD uint8_t filter_byte(Get x, uint32_t len, uint32_t type, uint32_t width, uint32_t pos)
+{
+    if (width == 0u) return (uint8_t)x(pos);
+    if (type == 2u) return pos < len % width + width ? (uint8_t)x(pos) : (uint8_t)(x(pos) - x(pos - width));   // raw head, first group against zeros
+    const uint32_t cur = x(reorder_src(len, width, pos));
+    return pos ? (uint8_t)(cur - x(reorder_src(len, width, pos - 1u))) : (uint8_t)cur;
+}
+
+// Both types at one width share the differences D = { x[i] - x[i - width] : width <= i < len }.  What a candidate's output differs from D
+// by, as add(byte, +1 or -1) calls, fewer than 3 width of them:
+//   type 0  every i >= width is an element k >= 1 of channel i mod width, so D is all of it but the channel starts: x[0] against zero, and
+//           x[c] against the last element of channel c - 1
+//   type 2  the first min(len, len mod width + width) bytes go out as they are; those of them at i >= width leave D
+template <class Get, class Add> JPK_HD void filter_fixups(Get x, uint32_t len, uint32_t type, uint32_t width, Add add)
+{
+    if (type == 2u) {
+        const uint32_t head = len % width + width < len ? len % width + width : len;
+        for (uint32_t i = 0; i < head; i++) {
+            add((uint8_t)x(i), 1);
+            if (i >= width) add((uint8_t)(x(i) - x(i - width)), -1);
+        }
+        return;
+    }
+    if (len) add((uint8_t)x(0u), 1);
+    for (uint32_t c = 1; c < width && c < len; c++) add((uint8_t)(x(c) - x(c - 1u + (len - c) / width * width)), 1);
 }
 
 }  // namespace pre
