@@ -70,9 +70,9 @@ int jpk_stage_ensure(jpk_ctx *ctx, size_t in_bytes, size_t out_bytes)
 
 int jpk_read_mail(jpk_ctx *ctx, uint32_t *dst, int words)
 {
-    JPK_HIP(hipMemcpyAsync(ctx->h_mail, ctx->d_mail, (size_t)words * 4, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipMemcpyAsync(ctx->h_mail->read, ctx->d_mail->read, (size_t)words * 4, hipMemcpyDeviceToHost, ctx->stream));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(dst, ctx->h_mail, (size_t)words * 4);
+    memcpy(dst, ctx->h_mail->read, (size_t)words * 4);
     if (ctx->prof_on) jpk_prof_resolve(ctx);
     return JPK_OK;
 }
@@ -169,9 +169,9 @@ extern "C" int jpk_ctx_create(jpk_ctx **out, int device, void *hip_stream)
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return JPK_E_DEVICE; }
         c->own_stream = true;
     }
-    if (hipHostMalloc((void **)&c->h_mail, 256 * 4, hipHostMallocDefault) != hipSuccess ||
+    if (hipHostMalloc((void **)&c->h_mail, sizeof(JpkMail), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&c->h_map, 4096 * 4, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&c->d_mail, 256 * 4) != hipSuccess) {
+        hipMalloc((void **)&c->d_mail, sizeof(JpkMail)) != hipSuccess) {
         jpk_ctx_destroy(c);
         return JPK_E_ALLOC;
     }
@@ -647,7 +647,7 @@ extern "C" int jpk_dev_exclusive_scan_u32(jpk_ctx *ctx, uint32_t *d_data, int32_
     JPK_TRY(jpk_arena_ensure(ctx, plan.need));
     Arena real(ctx, false);
     uint32_t *sc = real.get<uint32_t>(jpk_scan_scratch_words(n));
-    JPK_TRY(jpk_exclusive_sum_u32(ctx, d_data, d_data, (size_t)n, sc, ctx->d_mail));
+    JPK_TRY(jpk_exclusive_sum_u32(ctx, d_data, d_data, (size_t)n, sc, ctx->d_mail->read));
     uint32_t t = 0;
     JPK_TRY(jpk_read_mail(ctx, &t, 1));
     if (total) *total = t;
@@ -673,7 +673,7 @@ extern "C" int jpk_dev_checksum(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_le
 {
     JPK_ENTER(ctx);
     if (!crc || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
-    JPK_TRY(jpk_checksum_device(ctx, d_in, in_len, ctx->d_mail));
+    JPK_TRY(jpk_checksum_device(ctx, d_in, in_len, ctx->d_mail->read));
     return jpk_read_mail(ctx, crc, 1);
 }
 
@@ -716,7 +716,7 @@ extern "C" int jpk_dev_jam_block_write(jpk_ctx *ctx, const uint8_t *d_in, int32_
     JPK_TRY(jpk_dev_checksum(ctx, d_in, in_len, &crc));
     int32_t n = 0;
     JPK_TRY(jpk_dev_block_compress(ctx, d_in, in_len, d_out + JPK_JAM_HEADER_BYTES, out_cap - JPK_JAM_HEADER_BYTES, &n));
-    uint8_t *h = reinterpret_cast<uint8_t *>(ctx->h_mail + 128);    // pinned; words 128.. are not used by jpk_read_mail callers
+    uint8_t *h = ctx->h_mail->jam_header;    // pinned; not used by jpk_read_mail callers
     memcpy(h, "JAM", 3);
     memcpy(h + 3, &crc, 4);
     memcpy(h + 7, &n, 4);
@@ -733,7 +733,7 @@ extern "C" int jpk_dev_jam_block_read(jpk_ctx *ctx, const uint8_t *d_in, int32_t
     JPK_ENTER(ctx);
     if (!d_in || !d_out || !out_len || in_len < 0 || out_cap < 0) return JPK_E_ARG;
     if (in_len < JPK_JAM_HEADER_BYTES) return JPK_E_CORRUPT;
-    uint8_t *h = reinterpret_cast<uint8_t *>(ctx->h_mail + 128);
+    uint8_t *h = ctx->h_mail->jam_header;
     JPK_HIP(hipMemcpyAsync(h, d_in, JPK_JAM_HEADER_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     uint32_t crc;

@@ -1026,7 +1026,7 @@ int jpk_rank_decode_device(jpk_ctx *ctx, uint8_t *d_r, const int32_t *d_freq, in
     JPK_HIP(hipMemcpyAsync(info, &ci, sizeof ci, hipMemcpyHostToDevice, st));
     JPK_HIP(hipMemcpyAsync(tab, &hb, sizeof hb, hipMemcpyHostToDevice, st));
     JPK_HIP(hipStreamSynchronize(st));
-    uint32_t *status = ctx->d_mail + 8;
+    uint32_t *status = &ctx->d_mail->dec.status;
     JPK_LAUNCH(ctx, PROF_DEC_RANK, 0, k_dec_rank, dim3(1), dim3(64), tab, info, (const uint32_t *)nullptr, hf, status);
     JPK_HIP(hipGetLastError());
     JPK_HIP(hipMemcpyAsync(d_r, tmp, (size_t)len, hipMemcpyDeviceToDevice, st));

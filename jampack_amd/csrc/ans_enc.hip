@@ -1650,7 +1650,7 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
         d.sbase = nullptr; d.lbase = nullptr;
         JPK_TRY(run_rank(ctx, d_in, d, b));
         JPK_TRY(run_rle(ctx, b.ranks, d, b));
-        hipLaunchKernelGGL(k_sym_layout, dim3(1), dim3(64), 0, st, d, b.rlen, sbase, lbase, ctx->d_mail);
+        hipLaunchKernelGGL(k_sym_layout, dim3(1), dim3(64), 0, st, d, b.rlen, sbase, lbase, ctx->d_mail->read);
         uint32_t mail[14];
         JPK_TRY(jpk_read_mail(ctx, mail, 14));
         const size_t sym_total = mail[12], lane_total = mail[13];
@@ -1742,7 +1742,7 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
         JPK_TRY(chain(d));
     }
     JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_headers, dim3(d.nch), dim3(256), d, b.freq, b.csize, b.rlen, b.hdr, b.hsize);
-    JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_out_offsets, dim3(1), dim3(64), d, b.csize, b.rlen, b.hsize, b.outoff, ctx->d_mail, b.stamp);
+    JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_out_offsets, dim3(1), dim3(64), d, b.csize, b.rlen, b.hsize, b.outoff, ctx->d_mail->read, b.stamp);
     JPK_HIP(hipGetLastError());
     return JPK_OK;
 }
@@ -1885,7 +1885,7 @@ int jpk_rle_encode_device(jpk_ctx *ctx, const uint8_t *d_ranks, int32_t len, uin
     Arena real(ctx, false);
     enc_layout(real, d, b, LAY_RLE);
     JPK_TRY(run_rle(ctx, d_ranks, d, b));
-    JPK_HIP(hipMemcpyAsync(ctx->d_mail, b.rlen, 4, hipMemcpyDeviceToDevice, ctx->stream));
+    JPK_HIP(hipMemcpyAsync(ctx->d_mail->read, b.rlen, 4, hipMemcpyDeviceToDevice, ctx->stream));
     uint32_t n = 0;
     JPK_TRY(jpk_read_mail(ctx, &n, 1));
     JPK_HIP(hipMemcpyAsync(d_rle, b.rle, (size_t)n * 2, hipMemcpyDeviceToDevice, ctx->stream));

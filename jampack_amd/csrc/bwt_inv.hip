@@ -547,12 +547,12 @@ int jpk_inv_bwt_enqueue(jpk_ctx *ctx, const uint8_t *d_in, int32_t len_with_trai
 // the same, synchronous: one host round trip, at the end (the caller wants the status anyway)
 int jpk_inv_bwt_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len_with_trailer, uint8_t *d_out)
 {
-    uint32_t *verdict = ctx->d_mail + 16;
+    uint32_t *verdict = ctx->d_mail->inv_verdict;
     JPK_TRY(jpk_inv_bwt_enqueue(ctx, d_in, len_with_trailer, d_out, verdict));
-    JPK_HIP(hipMemcpyAsync(ctx->h_mail + 16, verdict, 16, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipMemcpyAsync(ctx->h_mail->inv_verdict, verdict, sizeof ctx->h_mail->inv_verdict, hipMemcpyDeviceToHost, ctx->stream));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->prof_on) jpk_prof_resolve(ctx);
-    const uint32_t *v = ctx->h_mail + 16;
+    const uint32_t *v = ctx->h_mail->inv_verdict;
     const int32_t len = len_with_trailer - JPK_TRAILER_BYTES;
     const uint32_t n = (uint32_t)(len - len % JPK_BWT_UNITS);
     if (n) {
@@ -575,9 +575,9 @@ int jpk_inv_bwt_chains120_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len_
         if (rem > 0) JPK_HIP(hipMemcpyAsync(d_out, d_in, (size_t)rem, hipMemcpyDeviceToDevice, st));
         return JPK_OK;
     }
-    JPK_HIP(hipMemcpyAsync(ctx->h_mail, d_in + len, 4, hipMemcpyDeviceToHost, st));
+    JPK_HIP(hipMemcpyAsync(&ctx->h_mail->inv_index, d_in + len, 4, hipMemcpyDeviceToHost, st));
     JPK_HIP(hipStreamSynchronize(st));
-    const uint32_t I = ctx->h_mail[0];
+    const uint32_t I = ctx->h_mail->inv_index;
     if (I < 1 || I > n) return JPK_E_CORRUPT;
     InvBufs b;
     size_t ntiles, nsplit, max_slots;

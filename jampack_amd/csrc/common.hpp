@@ -41,6 +41,39 @@ enum JpkProfId {
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 
+// The mailbox for device->host scalars: one 256-word page, pinned on the host (jpk_ctx::h_mail) with a twin in device memory (d_mail),
+// both laid out like this.  Regions that different subsystems use at different times overlap where they always have (a context runs one
+// call at a time): the suffix sort's count records and the inverse BWT's verdict; the posted scalars, the inverse BWT's index word and
+// the entropy decoder's status word.
+struct JpkMail {
+    static constexpr int WORDS = 256, READ_WORDS = 16, SA_COUNT_WORDS = 5;
+    struct Dec { uint32_t posted[8]; uint32_t status; };              // device: k_dec_rank's status behind jpk_dev_rank_decode (ans_dec.hip)
+    struct SaCounts { uint32_t m[2], npieces, lc, nrun, pad[3]; };    // the head of the suffix sort's SaState as a round leaves it: five words, stride 8
+    struct SaStats { uint32_t round_m[JPK_SA_MAX_ROUNDS], round_lc[JPK_SA_MAX_ROUNDS], bits, depth, vmode; };   // SaState from round_m on
+    union {                                  // words 0-15
+        uint32_t read[READ_WORDS];           // device: the scalars a kernel posts; host: what jpk_read_mail copied of them (callers take up to 14)
+        uint32_t inv_index;                  // host: a trailer's index word (bwt_inv.hip, the 120-chain comparator)
+        Dec dec;
+    };
+    union {                                  // words 16-31
+        SaCounts sa_counts[2];               // host: what round r of the suffix sort left, in sa_counts[r & 1] (dead once build_sa returns)
+        uint32_t inv_verdict[4];             // both: {status, trailer index, overflow slots, bytes the head chain covers} (jpk_inv_bwt_device)
+    };
+    SaStats sa_stats;                        // words 32-114, host: stays until jpk_sa_stats_sync has read it (jpk_ctx::sa_stats_pending)
+    uint32_t spare0[120 - 32 - (int)(sizeof(SaStats) / 4)];
+    uint32_t sa_vmode;                       // word 120, host: the code round 0 of the suffix sort chose
+    uint32_t spare1[7];
+    uint8_t jam_header[4 * (WORDS - 128)];   // words 128-255, host: one frame header on its way to or from the device (abi.hip)
+};
+static_assert(sizeof(JpkMail) == 4 * JpkMail::WORDS, "the page is 256 words");
+static_assert(offsetof(JpkMail, dec.status) == 4 * 8 && offsetof(JpkMail, sa_counts) == 4 * 16 && sizeof(JpkMail::SaCounts) == 4 * 8 &&
+              offsetof(JpkMail, inv_verdict) == 4 * 16 && offsetof(JpkMail, sa_stats) == 4 * 32 && offsetof(JpkMail, sa_vmode) == 4 * 120 &&
+              offsetof(JpkMail, jam_header) == 4 * 128, "every region is where it was when it was a bare word offset");
+static_assert(sizeof(JpkMail::read) <= offsetof(JpkMail, sa_counts) && offsetof(JpkMail, sa_counts) + sizeof(JpkMail::sa_counts) <= offsetof(JpkMail, sa_stats) &&
+              offsetof(JpkMail, sa_stats) + sizeof(JpkMail::SaStats) <= offsetof(JpkMail, sa_vmode) && offsetof(JpkMail, sa_vmode) + 4 <= offsetof(JpkMail, jam_header),
+              "the suffix sort's regions meet neither one another nor what jpk_read_mail fills while sa_stats_pending is set");
+static_assert(JPK_JAM_HEADER_BYTES <= sizeof(JpkMail::jam_header), "a frame header fits");
+
 struct jpk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -63,8 +96,8 @@ struct jpk_ctx {
     size_t arena_off = 0;
     size_t arena_base = 0;           // where the bump allocator starts (non-zero while a batch runs several stage instances side by side)
     // small pinned host mailbox for device->host scalars
-    uint32_t *h_mail = nullptr;   // 256 words pinned
-    uint32_t *d_mail = nullptr;   // 256 words device
+    JpkMail *h_mail = nullptr;    // pinned
+    JpkMail *d_mail = nullptr;    // device
     // persistent staging buffers for the host-buffer entry points
     uint8_t *stage_in = nullptr, *stage_out = nullptr, *stage_res = nullptr;
     size_t stage_in_cap = 0, stage_out_cap = 0, stage_res_cap = 0;
@@ -131,7 +164,8 @@ struct Arena {
 int jpk_arena_ensure(jpk_ctx *ctx, size_t bytes);
 bool jpk_arena_fits(const jpk_ctx *ctx, size_t bytes);      // jpk_arena_ensure(bytes) would keep the arena where it is
 int jpk_stage_ensure(jpk_ctx *ctx, size_t in_bytes, size_t out_bytes);
-// copy `words` u32 from device mailbox offset to host (synchronises the stream)
+// copy the first `words` posted scalars of the device mailbox to the host (synchronises the stream).  Precondition: words <=
+// JpkMail::READ_WORDS -- more would run into the suffix sort's regions of the page
 int jpk_read_mail(jpk_ctx *ctx, uint32_t *dst, int words);
 
 static inline unsigned jpk_grid(size_t work, unsigned per_block) { return (unsigned)((work + per_block - 1) / per_block); }

@@ -77,7 +77,7 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
     std::vector<int64_t> dec;
     uint64_t o = 0;
     while (o < (uint64_t)in_len) {
-        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail));
+        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail->read));
         JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
         uint32_t m[4];
         JPK_TRY(jpk_read_mail(ctx, m, 4));                   // synchronises: the table is on the host too
