@@ -425,6 +425,29 @@ JPK_API int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int6
 /* frame k: its raw offset and raw size, where its payload starts in the archive and the payload's size; JPK_E_ARG for k out of range */
 JPK_API int jpk_jam_index_frame(const jpk_jam_index *index, int32_t k, int64_t *raw_off, int64_t *raw, int64_t *payload_off, int32_t *psize);
 JPK_API void jpk_jam_index_destroy(jpk_jam_index *index);
+/* The index of a stock-CLI archive (the frames jpk_dev_jam_cli_decompress reads).  Such a frame's raw size is in neither its header nor
+ * its chunk headers: it is known only behind the frame's last stage, the second Lz77::Decompress.  So this index is made by DECODING the
+ * archive once: the frame walk of jpk_dev_jam_cli_decompress, then its passes (at most 128 frames and 4 GiB of BlockSize, two slots of
+ * 1.05 x BlockSize + 4096 per frame in the scratch buffer of ctx) -- the whole stage chain and the batched checksum against the header
+ * crcs, but no output buffer and no gather.  Every frame in the index has been verified.  (Sizing the frames as "BlockSize each, the
+ * last one the rest" from a known total is NOT sound: `cat a.jam b.jam` with frames of 500 KB, 1 MiB and 700 KB has a plausible frame
+ * count and a middle frame that passes a per-frame check, and would be delivered at the wrong raw offset, silently.)
+ * A bad frame is handled as by the plain index: JPK_OK, an index over the frames in front of the first bad one (bad header, payload,
+ * pre-stage stream or crc, or a raw size above BlockSize), *bad_frame = its position (-1: none; may be NULL).  The arguments are
+ * checked before a device is looked for, and in_len == 0 gives an empty index without a device.  jpk_jam_index_info / _frame / _destroy
+ * work on it unchanged, and jpk_dev_jam_read / jpk_jam_read take it in the place of a plain index.  The host-buffer form stages the
+ * archive one pass at a time through the calling thread's pooled context. */
+#define JPK_JAM_INDEX_PLAIN 0
+#define JPK_JAM_INDEX_CLI 1
+JPK_API int jpk_dev_jam_cli_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
+JPK_API int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
+/* JPK_JAM_INDEX_PLAIN for an index of jpk_(dev_)jam_index_create, JPK_JAM_INDEX_CLI for one of the stock-CLI creators; JPK_E_ARG for NULL */
+JPK_API int jpk_jam_index_kind(const jpk_jam_index *index);
+/* jpk_dev_jam_cli_decompress that also hands back the index of the frames it delivered (the whole archive on JPK_OK, the frames in
+ * front of the bad one on JPK_E_CORRUPT): a caller who decodes an archive once has its index for free.  index == NULL is allowed and
+ * makes this the plain call; *index is NULL after JPK_E_CAPACITY and every other failure. */
+JPK_API int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                          int32_t *bad_frame, jpk_jam_index **index);
 /* n ranges in raw coordinates, [off[r], off[r] + len[r]) delivered at d_out[r] (a device pointer of any alignment; the buffers must
  * not overlap).  in_len must be the index's archive length and every range must satisfy 0 <= off, 0 <= len, off + len <= raw_len:
  * JPK_E_ARG otherwise, before any device work, nothing written.  len == 0 is legal anywhere in [0, raw_len] and touches no frame.
@@ -438,7 +461,16 @@ JPK_API void jpk_jam_index_destroy(jpk_jam_index *index);
  * status[r] = JPK_OK, or the status of the lowest-numbered frame of range r that failed to decode or failed its crc (JPK_E_CORRUPT);
  * ranges whose frames are all good are delivered whatever happens to the others, the buffer of a failed range is unspecified.
  * *bad_frame = the lowest failing frame any range touches, or -1 (may be NULL).  Returns as jpk_dev_blocks_decompress: with a
- * status array JPK_OK once the arguments were accepted, with status == NULL the first failing range's status. */
+ * status array JPK_OK once the arguments were accepted, with status == NULL the first failing range's status.
+ * With an index of kind JPK_JAM_INDEX_CLI the contract is the same, word for word, and the decoder of a pass is the stage chain of
+ * jpk_dev_jam_cli_decompress on the touched frames alone: passes of at most 128 touched frames and 4 GiB of BlockSize (the slots are
+ * sized by BlockSize, not by raw size), two slots of 1.05 x BlockSize + 4096 per touched frame in the scratch buffer of ctx.  A frame
+ * wholly inside a range has its LAST stage, the second Lz77::Decompress, write straight into that range's buffer; every other frame ends
+ * in its slot A.  Unlike the whole-archive call the read does not stop at the first bad frame: after every stage the jobs are compacted
+ * to the frames that passed it, a stage that runs out of its slot is JPK_E_CORRUPT (never JPK_E_CAPACITY), and the last stage's
+ * capacity is the indexed raw size exactly -- a frame that decodes to another size belongs to an archive that is not the indexed one and
+ * is JPK_E_CORRUPT.  The crc a frame must meet is the one in its header in the archive being read (four bytes per touched frame are
+ * read for it), so a header damaged after indexing fails its frame too. */
 JPK_API int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
                              uint8_t *const *d_out, int32_t *status, int32_t *bad_frame);
 /* host-buffer form through the calling thread's pooled context: only the payloads of the touched frames are staged to the device,

@@ -4,7 +4,7 @@ importing this package loads it and fails loudly if it has not been built."""
 from . import corpus  # noqa: F401
 from ._lib import ABI_SYMBOLS, CHUNK, LIB_PATH, TRAILER, JampackError, lib  # noqa: F401
 from .api import (blocks_compress_multi, blocks_decompress_multi, multi_plan, Ans, Bwt, Checksum, Context, Postcoder, ans_capacity, block_compress, block_decompress,  # noqa: F401
-                  jam_block_read, jam_block_write, jam_compress, jam_compress_bound, jam_decompress, jam_frames, jam_index, jam_read, JamIndex, Lz77, Lpx, Filters, checksum_host,
+                  jam_block_read, jam_block_write, jam_compress, jam_compress_bound, jam_decompress, jam_frames, jam_index, jam_cli_index, jam_read, JamIndex, Lz77, Lpx, Filters, checksum_host,
                   jam_cli_block_read, jam_cli_block_write, jam_cli_compress, jam_cli_compress_bound, cli_stages_bound, cli_stages_encode, CLI_DEDUPE, CLI_FILTERS, filters_cost, jam_cli_decompress, jam_cli_decompress_all, jam_cli_frames, init, shutdown, release_idle, thread_device, ans_decoded_size)
 
 lib()  # no lazy fallback: the HIP extension must be present

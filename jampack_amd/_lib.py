@@ -108,6 +108,10 @@ _SIGS = {
     "jpk_jam_frames": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(C.c_int64), _i32p]),
     "jpk_dev_jam_index_create": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(_vp), _i32p]),
     "jpk_jam_index_create": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _i32p]),
+    "jpk_dev_jam_cli_index_create": (C.c_int, [_vp, _vp, C.c_int64, C.POINTER(_vp), _i32p]),
+    "jpk_jam_cli_index_create": (C.c_int, [_vp, C.c_int64, C.POINTER(_vp), _i32p]),
+    "jpk_jam_index_kind": (C.c_int, [_vp]),
+    "jpk_dev_jam_cli_decompress_ix": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(_vp)]),
     "jpk_jam_index_info": (C.c_int, [_vp, _i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "jpk_jam_index_frame": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i32p]),
     "jpk_jam_index_destroy": (None, [_vp]),

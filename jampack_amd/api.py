@@ -218,13 +218,15 @@ def jam_decompress(stream) -> np.ndarray:
 
 class JamIndex:
     """jpk_jam_index: the frame table of one archive -- `frames`, `raw_len`, `archive_len`, `bad_frame` (-1: the whole archive is
-    indexed; otherwise the index covers the frames in front of that one) and `frame(k)`.  Keeps no reference to the archive."""
+    indexed; otherwise the index covers the frames in front of that one), `kind` (0: a plain archive, 1: an archive of the stock CLI,
+    indexed by decoding it) and `frame(k)`.  Keeps no reference to the archive."""
 
     def __init__(self, handle, bad_frame: int):
         self._h = handle
         k, raw, alen = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         _chk(lib().jpk_jam_index_info(self._h, C.byref(k), C.byref(raw), C.byref(alen)), "jpk_jam_index_info")
         self.frames, self.raw_len, self.archive_len, self.bad_frame = k.value, raw.value, alen.value, int(bad_frame)
+        self.kind = int(lib().jpk_jam_index_kind(self._h))
 
     def frame(self, k: int):
         """(raw offset, raw size, payload offset, payload size) of frame k"""
@@ -252,6 +254,15 @@ def jam_index(stream) -> JamIndex:
     return JamIndex(h, bad.value)
 
 
+def jam_cli_index(stream) -> JamIndex:
+    """jpk_jam_cli_index_create: the index of a stock-CLI archive in host memory, made by decoding it once on the device (a frame's
+    raw size is known only behind its last stage); jam_read takes it like a plain index"""
+    c = _np_u8(stream)
+    h, bad = C.c_void_p(), C.c_int32(-1)
+    _chk(lib().jpk_jam_cli_index_create(_ptr(c), len(c), C.byref(h), C.byref(bad)), "jpk_jam_cli_index_create")
+    return JamIndex(h, bad.value)
+
+
 def _ranges(ranges):
     n = len(ranges)
     L = C.c_int64 * max(n, 1)
@@ -260,7 +271,8 @@ def _ranges(ranges):
 
 def jam_read(stream, ranges, index: JamIndex | None = None):
     """jpk_jam_read: the byte ranges [(raw offset, length), ...] of an archive in host memory -> list of numpy arrays.  Only the frames
-    the ranges touch are staged and decoded.  Raises JampackError with the first failing range's status."""
+    the ranges touch are staged and decoded.  Raises JampackError with the first failing range's status.  Without an index the archive
+    is taken for a plain one; a stock-CLI archive is read through the index of jam_cli_index."""
     c = _np_u8(stream)
     ix = index if index is not None else jam_index(c)
     try:
@@ -612,6 +624,18 @@ class Context:
         _chk(rc, "jpk_dev_jam_cli_decompress")
         return n.value, nf.value, bf.value
 
+    def jam_cli_decompress_ix(self, d_in, in_len, d_out, out_cap, check: bool = True):
+        """jpk_dev_jam_cli_decompress_ix: jam_cli_decompress that also returns the index of the frames it delivered ->
+        (raw bytes, frames, bad frame, JamIndex); check=False: (raw bytes, frames, bad frame, status, JamIndex or None), no exception
+        (no index on JPK_E_CAPACITY)"""
+        n, nf, bf, h = C.c_int64(0), C.c_int32(0), C.c_int32(-1), C.c_void_p()
+        rc = lib().jpk_dev_jam_cli_decompress_ix(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf), C.byref(h))
+        ix = JamIndex(h, bf.value) if h else None
+        if not check:
+            return n.value, nf.value, bf.value, int(rc), ix
+        _chk(rc, "jpk_dev_jam_cli_decompress_ix")
+        return n.value, nf.value, bf.value, ix
+
     def checksum(self, d_in, in_len) -> int:
         crc = C.c_uint32(0)
         _chk(lib().jpk_dev_checksum(self._h, _dptr(d_in), in_len, C.byref(crc)), "jpk_dev_checksum")
@@ -662,6 +686,12 @@ class Context:
         """jpk_dev_jam_index_create: the index of an archive in HBM"""
         h, bad = C.c_void_p(), C.c_int32(-1)
         _chk(lib().jpk_dev_jam_index_create(self._h, _dptr(d_in), in_len, C.byref(h), C.byref(bad)), "jpk_dev_jam_index_create")
+        return JamIndex(h, bad.value)
+
+    def jam_cli_index(self, d_in, in_len) -> JamIndex:
+        """jpk_dev_jam_cli_index_create: the index of a stock-CLI archive in HBM, made by decoding it once (no output buffer)"""
+        h, bad = C.c_void_p(), C.c_int32(-1)
+        _chk(lib().jpk_dev_jam_cli_index_create(self._h, _dptr(d_in), in_len, C.byref(h), C.byref(bad)), "jpk_dev_jam_cli_index_create")
         return JamIndex(h, bad.value)
 
     def jam_read(self, index: JamIndex, d_in, in_len, ranges, d_outs, check: bool = True):

@@ -384,29 +384,137 @@ extern "C" int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_
     return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true, flags);
 }
 
+// the frame table behind jpk_jam_index (the range reads below; the stock-CLI calls make one from what they decode)
+struct jpk_jam_index {
+    std::vector<JamFrame> fr;
+    std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
+    int64_t archive_len = 0;
+    int32_t bad = -1;
+    int32_t kind = JPK_JAM_INDEX_PLAIN;    // JPK_JAM_INDEX_CLI: frames of the stock CLI, fr[k].raw from a decode (jam_cli_decode)
+};
+
+namespace {
+jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad, int32_t kind = JPK_JAM_INDEX_PLAIN)
+{
+    jpk_jam_index *ix = new (std::nothrow) jpk_jam_index;
+    if (!ix) return nullptr;
+    try {
+        ix->fr = fr;
+        ix->raw_off.reserve(fr.size() + 1);
+    } catch (const std::bad_alloc &) { delete ix; return nullptr; }
+    int64_t raw = 0;
+    for (const JamFrame &f : fr) {
+        ix->raw_off.push_back(raw);
+        raw += f.raw;
+    }
+    ix->raw_off.push_back(raw);
+    ix->archive_len = in_len;
+    ix->bad = bad;
+    ix->kind = kind;
+    return ix;
+}
+}  // namespace
+
 // ---- whole archives of the stock CLI: every frame through the four pre-stage decoders on the device (prestage_dev.hip) -------------
 // Per pass: jpk_dev_blocks_decompress into slot A of every frame, then Lz77 A -> B, Lpx B -> A, Filters A -> B, Lz77 B -> A (the
 // order of Jampack::Decomp(), jampack.cpp:51-57), one batched checksum of the A slots against the header crcs, one k_jam_gather
 // launch that packs the verified frames back to back into d_out.  A frame's raw size is known only behind its last stage; every stage
 // works on the frames in front of the first one that has failed so far, which is where the call stops.  A pass holds at most
 // JPK_JAM_PASS_FRAMES frames and JAM_PASS_RAW bytes of BlockSize.
+// jam_cli_pass is that stage chain for the frames of one pass; the whole-archive call, the index creation (the same pass without an
+// output: the raw sizes are what it is after) and the range reader (a sparse set of frames, the last stage straight into a caller's
+// buffer where a range holds the whole frame) run it.
 namespace {
-// the first block of st[0..m) that failed (*rc = its status), m when none did.  A stage that runs out of its slot (1.05 x BlockSize +
-// 4096, or BlockSize behind the last stage) met a bad frame: JPK_E_CAPACITY is kept for the caller's out_cap.
-int jam_cli_cut(const std::vector<int32_t> &st, int m, int *rc)
-{
-    for (int i = 0; i < m; i++) if (st[(size_t)i] != JPK_OK) { *rc = st[(size_t)i] == JPK_E_CAPACITY ? JPK_E_CORRUPT : st[(size_t)i]; return i; }
-    return m;
-}
-}  // namespace
+// The frames of one pass and where their stages work.  Stage 0 decodes ins[i] into a[i], the stages go A -> B -> A -> B, and the last
+// one, the second Lz77::Decompress, writes at most dst_cap[i] bytes to dst[i] (slot A again, or any address of a caller's buffer:
+// k_pre_lz77 writes by bytes).  The slots hold caps[i] bytes each.  crc[i] is the header's, d_crc n words of device memory.
+//   prefix  every stage runs on the frames in front of the first one that has failed so far (a whole archive stops there); otherwise
+//           on all surviving frames, compacted after every stage -- a frame that failed a stage has no lengths for the next one
+//   exact   a frame whose raw size is not dst_cap[i] is JPK_E_CORRUPT (the reader: dst_cap is the indexed raw size)
+struct CliPass {
+    int n;
+    const uint8_t *const *ins; const int32_t *lens;
+    uint8_t *const *a; uint8_t *const *b; const int32_t *caps;
+    uint8_t *const *dst; const int32_t *dst_cap;
+    const uint32_t *crc; uint32_t *d_crc;
+    bool prefix, exact;
+};
 
-extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                          int32_t *frames, int32_t *bad_frame)
+// st[i] = JPK_OK and raw[i] = the raw size of a frame that went through every stage and matches its crc -- it is at dst[i] --, else the
+// status of the stage it failed (with prefix: also of every frame behind the first failing one, none of which is decoded to the end).
+// A stage that runs out of its slot (1.05 x BlockSize + 4096, or dst_cap behind the last stage) met a bad frame: JPK_E_CORRUPT, never
+// JPK_E_CAPACITY, which is kept for a caller's out_cap.
+int jam_cli_pass(jpk_ctx *ctx, const CliPass &p, int32_t *raw, int32_t *st)
 {
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    const JamResult res{out_len, frames, bad_frame};
+    const size_t n = (size_t)p.n;
+    std::vector<int> live(n);
+    std::vector<const uint8_t *> src(n);
+    std::vector<uint8_t *> out(n);
+    std::vector<int32_t> len(n), cap(n), got(n), s(n);
+    for (size_t i = 0; i < n; i++) { live[i] = (int)i; len[i] = p.lens[i]; st[i] = JPK_OK; raw[i] = 0; }
+    // the job arrays of the next stage: the surviving frames, in order
+    auto aim = [&](const uint8_t *const *from, uint8_t *const *to, const int32_t *c) {
+        for (size_t q = 0; q < live.size(); q++) { src[q] = from[live[q]]; out[q] = to[live[q]]; cap[q] = c[live[q]]; }
+        return (int32_t)live.size();
+    };
+    // behind a stage: s[q] / got[q] of the frames it ran on -> st[], and the survivors with their new lengths
+    auto settle = [&]() {
+        size_t w = 0;
+        for (size_t q = 0; q < live.size(); q++) {
+            const int i = live[q];
+            if (s[q] != JPK_OK) {
+                st[i] = s[q] == JPK_E_CAPACITY ? JPK_E_CORRUPT : s[q];
+                if (!p.prefix) continue;
+                for (size_t r = q + 1; r < live.size(); r++) st[live[r]] = st[i];
+                break;
+            }
+            live[w] = i; len[w] = got[q]; w++;
+        }
+        live.resize(w);
+    };
+    int32_t m = aim(p.ins, p.a, p.caps);
+    if (m) {
+        JPK_TRY(jpk_dev_blocks_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));           // Ans::Decode + InverseBwt
+        settle();
+    }
+    if ((m = aim(p.a, p.b, p.caps))) {
+        JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));      // Lz->Decompress
+        settle();
+    }
+    if ((m = aim(p.b, p.a, p.caps))) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, src.data(), len.data(), out.data(), s.data()));      // LocalModel->Decode (never fails)
+    if ((m = aim(p.a, p.b, p.caps))) {
+        JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));       // Filter->Decode
+        settle();
+    }
+    if ((m = aim(p.b, p.dst, p.dst_cap))) {
+        // Lz->Decompress; a frame that decodes to more than dst_cap (its BlockSize, or its indexed raw size) is a bad frame
+        JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));
+        if (p.exact) for (int32_t q = 0; q < m; q++) if (s[(size_t)q] == JPK_OK && got[(size_t)q] != cap[(size_t)q]) s[(size_t)q] = JPK_E_CORRUPT;
+        settle();
+    }
+    if ((m = (int32_t)live.size())) {
+        std::vector<uint32_t> crc((size_t)m);
+        for (int32_t q = 0; q < m; q++) src[(size_t)q] = p.dst[live[(size_t)q]];
+        JPK_TRY(jam_crcs(ctx, m, src.data(), len.data(), p.d_crc, crc.data()));
+        for (int32_t q = 0; q < m; q++) {
+            s[(size_t)q] = crc[(size_t)q] != p.crc[live[(size_t)q]] ? JPK_E_CORRUPT : JPK_OK;     // "Detected corrupt block!", jampack.cpp:59
+            got[(size_t)q] = len[(size_t)q];
+        }
+        settle();
+    }
+    for (size_t q = 0; q < live.size(); q++) raw[live[q]] = len[q];
+    return JPK_OK;
+}
+
+// jpk_dev_jam_cli_decompress(_ix) and, with deliver == false, jpk_dev_jam_cli_index_create: the same passes without an output buffer,
+// a capacity answer or a gather.  done (nullable) receives the frames that were verified, f.raw = their raw size, and *done_bad the first
+// bad frame (-1: none) -- what an index of the archive holds.
+int jam_cli_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, bool deliver,
+                   std::vector<JamFrame> *done, int32_t *done_bad)
+{
     jam_result_zero(res);
+    if (done_bad) *done_bad = -1;
+    if (in_len == 0) return JPK_OK;                        // an empty archive: no frame, no device call
     std::vector<JamFrame> fr;
     int32_t bad = -1;
     JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, true));
@@ -416,14 +524,15 @@ extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int
     for (size_t k = 0; k < fr.size();) {
         const size_t e = jam_pass_end(fr, k, true);
         const int n = (int)(e - k);
-        std::vector<const uint8_t *> ins((size_t)n), a_in((size_t)n), b_in((size_t)n);
+        std::vector<const uint8_t *> ins((size_t)n);
         std::vector<uint8_t *> a((size_t)n), b((size_t)n);
-        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), l0((size_t)n), l1((size_t)n), l3((size_t)n), raw((size_t)n), st((size_t)n);
+        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), raw((size_t)n), st((size_t)n);
+        std::vector<uint32_t> crc((size_t)n);
         std::vector<size_t> slot((size_t)n);
         size_t need = o_slots;
         for (int i = 0; i < n; i++) {
             const JamFrame &f = fr[k + i];
-            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size;
+            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size; crc[i] = f.crc;
             caps[i] = jam_cli_cap(f.block_size);
             slot[i] = jpk_align((size_t)caps[i] + 64);           // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
             need += 2 * slot[i];
@@ -432,54 +541,68 @@ extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int
         uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
         JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
         size_t off = o_slots;
-        for (int i = 0; i < n; i++) {
-            a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i];
-            a_in[i] = a[i]; b_in[i] = b[i];
-        }
-        int rc = JPK_OK;
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), a.data(), caps.data(), l0.data(), st.data()));   // Ans::Decode + InverseBwt
-        int m = jam_cli_cut(st, n, &rc);
-        if (m) {
-            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, a_in.data(), l0.data(), b.data(), caps.data(), l1.data(), st.data()));   // Lz->Decompress
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, b_in.data(), l1.data(), a.data(), st.data()));                             // LocalModel->Decode
-        if (m) {
-            JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, a_in.data(), l1.data(), b.data(), caps.data(), l3.data(), st.data()));    // Filter->Decode
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) {
-            // Lz->Decompress; a frame that decodes to more than its BlockSize is a bad frame
-            JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, b_in.data(), l3.data(), a.data(), bsz.data(), raw.data(), st.data()));
-            m = jam_cli_cut(st, m, &rc);
-        }
-        if (m) {
-            std::vector<uint32_t> crc((size_t)m);
-            JPK_TRY(jam_crcs(ctx, m, a_in.data(), raw.data(), d_crc, crc.data()));
-            for (int i = 0; i < m; i++) if (crc[i] != fr[k + i].crc) { m = i; rc = JPK_E_CORRUPT; break; }      // "Detected corrupt block!", jampack.cpp:59
-        }
+        for (int i = 0; i < n; i++) { a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i]; }
+        // every frame ends in its slot A; a frame that decodes to more than its BlockSize is a bad frame
+        JPK_TRY(jam_cli_pass(ctx, CliPass{n, ins.data(), lens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), crc.data(), d_crc, true, false},
+                             raw.data(), st.data()));
+        int m = 0, rc = JPK_OK;
+        while (m < n && st[m] == JPK_OK) m++;
+        if (m < n) rc = st[m];
         int64_t sum = 0;
         for (int i = 0; i < m; i++) sum += raw[i];
-        if (sum > out_cap - pos) {
-            *out_len = raw_bound;
-            if (frames) *frames = (int32_t)k;
-            return JPK_E_CAPACITY;
+        if (deliver) {
+            if (sum > out_cap - pos) {
+                *res.out_len = raw_bound;
+                if (res.frames) *res.frames = (int32_t)k;
+                return JPK_E_CAPACITY;
+            }
+            std::vector<JamGatherPiece> pieces;
+            uint64_t words = 0;
+            int64_t o = pos;
+            for (int i = 0; i < m; i++) {
+                if (raw[i] == 0) continue;
+                jam_piece_add(pieces, &words, a[i], d_out + o, (uint64_t)raw[i], a[i], a[i] + slot[i]);
+                o += raw[i];
+            }
+            JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, (uint64_t)sum));
+            if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
         }
-        std::vector<JamGatherPiece> pieces;
-        uint64_t words = 0;
-        int64_t o = pos;
-        for (int i = 0; i < m; i++) {
-            if (raw[i] == 0) continue;
-            jam_piece_add(pieces, &words, a[i], d_out + o, (uint64_t)raw[i], a[i], a[i] + slot[i]);
-            o += raw[i];
-        }
-        JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, (uint64_t)sum));
-        if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
+        if (done)
+            for (int i = 0; i < m; i++) {
+                done->push_back(fr[k + i]);
+                done->back().raw = raw[i];
+            }
         pos += sum;
-        if (m < n) return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        if (m < n) {
+            if (done_bad) *done_bad = (int32_t)k + m;
+            return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        }
         k = e;
     }
+    if (done_bad) *done_bad = bad;
     return jam_result_done(res, pos, fr.size(), bad);
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                             int32_t *frames, int32_t *bad_frame, jpk_jam_index **index)
+{
+    // (JPK_ENTER taken apart: the argument checks come before the first device call)
+    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    if (index) *index = nullptr;
+    JPK_HIP(hipSetDevice(ctx->device));
+    std::vector<JamFrame> done;
+    int32_t done_bad = -1;
+    const int rc = jam_cli_decode(ctx, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, true, index ? &done : nullptr, &done_bad);
+    // the index of what was delivered: the whole archive, or the frames in front of the bad one
+    if (index && (rc == JPK_OK || rc == JPK_E_CORRUPT) && !(*index = jam_index_make(done, in_len, done_bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
+    return rc;
+}
+
+extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                          int32_t *frames, int32_t *bad_frame)
+{
+    return jpk_dev_jam_cli_decompress_ix(ctx, d_in, in_len, d_out, out_cap, out_len, frames, bad_frame, nullptr);
 }
 
 namespace {
@@ -549,33 +672,10 @@ extern "C" int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t
 // touches, decodes each touched frame ONCE -- in place in the first range that contains it whole, otherwise into a padded slot of
 // ctx->jam_scratch -- in passes with the limits of the archive calls, checks every decoded frame against its header crc, and delivers
 // the pieces of the verified frames with one k_jam_gather launch per pass.  A frame no range touches is neither decoded nor checked.
-struct jpk_jam_index {
-    std::vector<JamFrame> fr;
-    std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
-    int64_t archive_len = 0;
-    int32_t bad = -1;
-};
-
+// An index of a stock-CLI archive (kind JPK_JAM_INDEX_CLI) can only come from a decode -- a frame's raw size is in no header -- and a
+// read through it is the same plan with jam_cli_pass as the decoder: two slots of 1.05 x BlockSize + 4096 per touched frame, passes
+// bounded by BlockSize, and the last stage writes a frame that a range holds whole straight into that range at exactly its indexed size.
 namespace {
-jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad)
-{
-    jpk_jam_index *ix = new (std::nothrow) jpk_jam_index;
-    if (!ix) return nullptr;
-    try {
-        ix->fr = fr;
-        ix->raw_off.reserve(fr.size() + 1);
-    } catch (const std::bad_alloc &) { delete ix; return nullptr; }
-    int64_t raw = 0;
-    for (const JamFrame &f : fr) {
-        ix->raw_off.push_back(raw);
-        raw += f.raw;
-    }
-    ix->raw_off.push_back(raw);
-    ix->archive_len = in_len;
-    ix->bad = bad;
-    return ix;
-}
-
 // the argument checks of both read entries: nothing is touched before they pass
 int jam_read_check(const jpk_jam_index *ix, const void *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out)
 {
@@ -625,15 +725,19 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
                 if (ix->fr[(size_t)f].raw) piece_range[fill[(size_t)f]++] = r;
     }
     std::vector<int32_t> fstat(F, JPK_OK);
+    const bool cli = ix->kind == JPK_JAM_INDEX_CLI;
+    // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+    auto cli_slot = [&](size_t f) { return jpk_align((size_t)jam_cli_cap(ix->fr[f].block_size) + 64); };
     const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
     for (size_t k = 0; k < touched.size();) {
-        const size_t e = jam_pass_end(touched.size(), k, [&](size_t i) { return ix->fr[touched[i]].raw; });
+        const size_t e = jam_pass_end(touched.size(), k, [&](size_t i) { return jam_weight(ix->fr[touched[i]], cli); });
         const int m = (int)(e - k);
         size_t npieces = 0, slot_bytes = 0, stage_bytes = 0;
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             npieces += start[f + 1] - start[f];
-            if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            if (cli) slot_bytes += 2 * cli_slot(f);                                 // the stages' slots A and B, whatever the frame's raw size
+            else if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);
             stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
         }
         const size_t o_slots = o_tab + jpk_align(npieces * sizeof(JamGatherPiece));
@@ -641,9 +745,11 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
         if (!d_in) JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
         uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
         JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
-        std::vector<const uint8_t *> ins((size_t)m);
-        std::vector<uint8_t *> outs((size_t)m);
-        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m);
+        std::vector<const uint8_t *> ins((size_t)m), hi((size_t)m);           // hi[i]: the end of what is readable around the decoded frame
+        std::vector<uint8_t *> outs((size_t)m), sa, sb;
+        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m), scap;
+        std::vector<uint32_t> crcs;
+        if (cli) { sa.resize((size_t)m); sb.resize((size_t)m); scap.resize((size_t)m); crcs.resize((size_t)m); }
         size_t slot = o_slots, stage = 0;
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
@@ -655,17 +761,35 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
                 stage += jpk_align((size_t)fr.psize + 64);
             }
             lens[i] = fr.psize; caps[i] = (int32_t)fr.raw;
+            if (cli) {
+                sa[i] = ctx->jam_scratch + slot; sb[i] = sa[i] + cli_slot(f); slot += 2 * cli_slot(f);
+                scap[i] = jam_cli_cap(fr.block_size);
+                // the crc to meet is the one in the header of the archive being read, which need not be the indexed one any more
+                if (d_in) JPK_HIP(hipMemcpyAsync(&crcs[i], d_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
+                else memcpy(&crcs[i], h_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4);
+                outs[i] = home[f] ? home[f] : sa[i];
+                hi[i] = home[f] ? outs[i] + fr.raw : sa[i] + cli_slot(f);
+                continue;
+            }
             if (home[f]) outs[i] = home[f];
             else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
+            hi[i] = home[f] ? outs[i] + fr.raw : outs[i] + ((fr.raw + 15) & ~(int64_t)15) + 16;
         }
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
         // one batched checksum of the frames that decoded, against their header crcs
         std::vector<int> dec;
         std::vector<const uint8_t *> cin;
         std::vector<int32_t> clen;
-        for (int i = 0; i < m; i++) {
-            if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
-            dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
+        if (cli) {
+            // the stage chain on the touched frames alone, the last stage at the indexed raw size; the checksum is the pass's
+            JPK_TRY(jam_cli_pass(ctx, CliPass{m, ins.data(), lens.data(), sa.data(), sb.data(), scap.data(), outs.data(), caps.data(), crcs.data(), d_crc, false, true},
+                                 outl.data(), st.data()));
+            for (int i = 0; i < m; i++) fstat[touched[k + i]] = st[i];
+        } else {
+            JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
+            for (int i = 0; i < m; i++) {
+                if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
+                dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
+            }
         }
         if (!dec.empty()) {
             std::vector<uint32_t> crc(dec.size());
@@ -680,15 +804,13 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             if (fstat[f] != JPK_OK) continue;
-            const int64_t raw = ix->fr[f].raw;
-            const uint8_t *hi = home[f] ? outs[i] + raw : outs[i] + ((raw + 15) & ~(int64_t)15) + 16;
             for (size_t q = start[f]; q < start[f + 1]; q++) {
                 const int32_t r = piece_range[q];
                 const int64_t a = std::max(ro[f], off[r]), b = std::min(ro[f + 1], off[r] + len[r]);
                 const uint8_t *src = outs[i] + (a - ro[f]);
                 uint8_t *dst = d_out[r] + (a - off[r]);
                 if (src == dst) continue;
-                jam_piece_add(tab, &words, src, dst, (uint64_t)(b - a), outs[i], hi);
+                jam_piece_add(tab, &words, src, dst, (uint64_t)(b - a), outs[i], hi[i]);
                 bytes += (uint64_t)(b - a);
             }
         }
@@ -758,6 +880,56 @@ extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_i
     if (bad_frame) *bad_frame = bad;
     return JPK_OK;
 }
+
+extern "C" int jpk_dev_jam_cli_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    // (JPK_ENTER taken apart: the argument checks come before the first device call, and an empty archive makes none)
+    if (!ctx || !index || in_len < 0 || (in_len > 0 && !d_in)) return JPK_E_ARG;
+    *index = nullptr;
+    if (in_len > 0) JPK_HIP(hipSetDevice(ctx->device));
+    std::vector<JamFrame> done;
+    int64_t raw_len = 0;
+    int32_t bad = -1;
+    const int rc = jam_cli_decode(ctx, d_in, in_len, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &done, &bad);
+    if (rc != JPK_OK && rc != JPK_E_CORRUPT) return rc;      // a bad frame ends the index, not the call
+    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
+{
+    if (!index || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr, done;
+    int32_t bad = -1;
+    if (in_len > 0) {
+        jpk_ctx *ctx;
+        JPK_TRY(jpk_host_enter(&ctx, 0));
+        jam_walk_host(in, in_len, fr, &bad, true);
+        // staged one pass at a time, as jam_decompress_host: the pass's frames are an archive of their own for the device decode
+        for (size_t k = 0; k < fr.size();) {
+            const size_t e = jam_pass_end(fr, k, true);
+            const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+            JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+            std::vector<JamFrame> got;
+            int64_t raw_len = 0;
+            int32_t pass_bad = -1;
+            const int rc = jam_cli_decode(ctx, ctx->stage_in, a1 - a0, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &got, &pass_bad);
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            if (rc != JPK_OK && rc != JPK_E_CORRUPT) return rc;
+            for (JamFrame &f : got) { f.payload_off += a0; done.push_back(f); }
+            if (pass_bad >= 0) { bad = (int32_t)k + pass_bad; break; }
+            k = e;
+        }
+    }
+    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_index_kind(const jpk_jam_index *index) { return index ? index->kind : JPK_E_ARG; }
 
 extern "C" int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len)
 {
