@@ -596,21 +596,39 @@ __global__ __launch_bounds__(64) void k_quasi_build(EncDims d, const uint32_t *_
 // the set of reachable states is an interval of width <= 31 whatever the history was.
 // Item streams: the exponent entries see every symbol (class byte stream cls8); a mantissa model only sees the symbols
 // of its class, which k_cls_ord has compacted into a list (position | mantissa bit << 31), so its "time" is the
-// class ordinal and a warm-up is always the 1280 list entries in front of the segment.  Per 4096-item segment:
-//   A    warm up the two extreme states over the preceding 1280 items -> [lo, hi].  lo == hi: the start state is
-//        exact; run the segment, write the outputs, record the end state.  Otherwise record [lo, hi].
-//   tab  unresolved segments: 32 lanes walk the segment from the 32 candidate start states -> transfer table.
-//   B    one lane per (chunk, recurrence) walks the segments in order composing exact states through the tables.
-//   C    the unresolved segments are run again from their now exact start state, writing the outputs.
+// class ordinal and a warm-up is always the AD_WARM_DEFAULT list entries in front of the segment.  Per 4096-item segment:
+//   A    warm up the two extreme states over the preceding 320 items -> [lo, hi], and walk on into the segment.  lo == hi from the
+//        start: the start state is exact, the whole segment is written.  Otherwise both ends walk the segment until they meet (the
+//        merge step: a median of 44 items in, 99 % within 180 on text, profiles/adapt_merge_kernel_stats.txt); the step is monotone
+//        in the state and the true start state lies in [lo, hi], so once the ends are equal every state between them has reached
+//        that value too: the trajectory from the merge step on IS the exact one, and A writes its outputs there and then, with the
+//        one state that is left.  It records the end state (the segment's transfer is a constant, flag 3) and how many items at
+//        the front it could not write (seg_miss, whole groups of sixteen).  A plateau lane (an entry above every class that occurs,
+//        see k_adapt_a) that no symbol of the segment reaches is the identity (flag 2) and is not walked; one that is reached
+//        also records the quiet stretch in front of its first reaching symbol (seg_reach).  Ends that never meet: flag 0.
+//   tab  flag 0 only (rare: a quiet mantissa run): 32 lanes walk the segment from the 32 candidate start states -> transfer table.
+//   B    one lane per (chunk, recurrence) walks the segments in order composing exact start states through end states (flags 1, 3),
+//        identities (2) and tables (0).
+//   C    writes what A left out from the now exact start state: a constant row over the quiet stretch (16-byte stores), one walk
+//        over [seg_reach, seg_miss) -- at most a few hundred items -- and the whole segment only behind a table.
 // Every output is produced from an exact state: the result is bit-identical to the sequential reference.
+// (Before: A stopped after the warm-up unless lo == hi -- 6 % of the segments of text --, a kernel k_adapt_ext walked every open
+// segment with both ends only to learn its end state, and C walked all of it again to write it.  Measured against that scheme on
+// one box, profiles/adapt_merge_kernel_stats.txt: one 64 MiB text block alone, k_adapt_* 3.84 -> 2.15 ms (a 0.98 -> 1.25, ext 0.64 ->
+// gone, c 1.61 -> 0.27, tab and b as they were); per 100 MB pass of the bench loop, ten blocks in flight, 4.71 -> 3.28 ms (c 2.40 ->
+// 0.48) and all kernels together 1752 -> 1652 ms per 23 passes; the bench line 5285 -> 5425 MB/s, median of eight alternating
+// pairs, higher in seven of them, profiles/adapt_merge_ab.txt.)
 // Warm-up items in front of a segment.  The interval of reachable states contracts by >= floor(width / 32) per item whatever the
 // item is (floor is superadditive), so from the full range it is <= 31 wide after 259 items: any warm-up >= 320 keeps the guarantee
 // the table of 32 candidates rests on.  Beyond that a longer warm-up only decides how many segments are already a single state
-// when the segment starts (k_adapt_ext / k_adapt_tab take the rest).  Rounds 1-3 used 1280, which is best for a block ALONE (the
-// five k_adapt_* kernels: 4.3 ms per 64 MiB block against 4.9 with 320) -- but the warm-up is pure vector work (two states per item,
-// +62 % on k_adapt_a), and with blocks in flight vector issue is what is short: the bench line prefers 320 (4.41 / 4.38 / 4.29 /
-// 4.15 GB/s for 320 / 384 / 512 / 1280 in one sequence, 4.22 / 4.13 / 4.11 for 320 / 384 / 1280 interleaved three times;
-// profiles/r04_adapt_warm.txt).
+// when the segment starts, and how soon the others merge inside it (a longer warm-up trades against a shorter stretch for k_adapt_c).
+// Rounds 1-3 used 1280, which was best for a block ALONE under the old scheme (the five k_adapt_* kernels: 4.3 ms per 64 MiB block
+// against 4.9 with 320) -- but the warm-up is pure vector work (two states per item, +62 % on k_adapt_a), and with blocks in
+// flight vector issue is what is short: the bench line preferred 320 (4.41 / 4.38 / 4.29 / 4.15 GB/s for 320 / 384 / 512 / 1280 in
+// one sequence, 4.22 / 4.13 / 4.11 for 320 / 384 / 1280 interleaved three times; profiles/r04_adapt_warm.txt).
+// With the walk-on scheme a longer warm-up also shortens what k_adapt_c re-walks, so 512 was alternated against 320 again: a block
+// alone 2.11 against 2.15 ms of k_adapt_*, the bench line 5534 against 5531 MB/s (medians of twelve alternating pairs, 512 ahead in
+// six of them, median difference +27 MB/s against a run-to-run yardstick of 98): no difference, 320 stays (profiles/adapt_merge_ab.txt).
 constexpr uint32_t AD_WARM_DEFAULT = 320;
 static_assert(AD_WARM_DEFAULT % 64 == 0 && AD_WARM_DEFAULT >= 320 && AD_WARM_DEFAULT <= 4096, "whole waves of warm-up items, guarantee above");
 
@@ -802,10 +820,15 @@ struct AdArgs {
     uint16_t *exph; uint32_t *mantad;       // exph: [chunk][7 exponent entries][rle_stride] history of every entry
     uint32_t warm;                          // warm-up items in front of a segment (AD_WARM_DEFAULT)
     uint32_t *seg_flag; int32_t *seg_lo, *seg_end, *seg_start; uint16_t *seg_tab;
+    uint16_t *seg_miss, *seg_reach;         // per segment: items from its start whose outputs k_adapt_c still owes; of those, items in front of the first symbol that moves a plateau lane
 };
 
 // lanes = 64 consecutive segments of ONE recurrence (grid y): the exponent / mantissa code paths and the item widths differ, a wave
-// that mixed recurrences would walk both paths one after the other with half its lanes off
+// that mixed recurrences would walk both paths one after the other with half its lanes off.
+// One walk per segment: the warm-up with the two extreme states, then on into the segment itself -- with both ends while any lane
+// of the wave is still open (wave-uniform control, one ballot per 64 class bytes / 16 list entries), then ad_run_write with the one
+// state that is left.  A lane that is a single state when a group of sixteen items starts stores that group's outputs; the groups
+// in front of it are what seg_miss counts and k_adapt_c writes.
 __global__ __launch_bounds__(64) void k_adapt_a(EncDims d, AdArgs a)
 {
     const uint32_t c = chunk_of(d, blockIdx.z), rec = blockIdx.y;
@@ -813,61 +836,133 @@ __global__ __launch_bounds__(64) void k_adapt_a(EncDims d, AdArgs a)
     const AdRec r(rec);
     const AdStream st = ad_stream(d, r, c, a.cls8, a.clist, a.rle_stride, a.rlen, a.clstotal);
     const uint32_t nt = (st.n + ATILE - 1) / ATILE;
-    if (k >= nt) return;
-    const uint32_t t0 = k * ATILE, t1 = (t0 + ATILE < st.n) ? t0 + ATILE : st.n;
-    int32_t lo, hi;
-    if (k == 0) lo = hi = r.init();
-    else {
+    const bool valid = k < nt;                                 // (no early return: the walk below is wave-uniform)
+    const uint32_t t0 = valid ? k * ATILE : 0u, t1 = !valid ? 0u : (t0 + ATILE < st.n) ? t0 + ATILE : st.n;
+    const uint32_t len = t1 - t0;
+    const int i = r.i, A = r.A;
+    int32_t lo = r.init(), hi = lo;
+    if (valid && k != 0) {
         lo = r.smin(); hi = r.smax();
-        const int i = r.i, A = r.A;
         ad_for_each(r, st, t0 - a.warm, t0, [&](uint32_t, int sy) { lo = adapt_step(lo, i, sy, A); hi = adapt_step(hi, i, sy, A); });
     }
     const size_t so = ((size_t)c * 9 + rec) * d.tpc + k;
-    if (lo == hi) {
-        a.seg_flag[so] = 1u;
-        a.seg_end[so] = ad_run_write(r, st, t0, t1, lo, a.exph + 7 * sym_base(d, c, a.rle_stride) + (size_t)(rec < 7 ? rec : 0) * sym_stride(d, c, a.rle_stride), a.mantad + sym_base(d, c, a.rle_stride));
-        return;
-    }
-    // unresolved: k_adapt_tab tabulates the 32 candidate start states lo .. lo+31 (hi - lo <= 31 after the warm-up).
-    // Except the one case that makes most of them: an exponent entry above every class that occurs (rare large classes).  Its mix is
-    // smax at every step, hi never left smax (one other step would have dropped it for good: nothing climbs back to smax from
-    // below), lo stalled at smax - 31, and all 32 states in between are fixed points of that step.  If no symbol of the segment
-    // reaches the entry either, the segment's transfer is the identity and its history row a constant: no table, no second walk.
-    uint32_t flag = 0u;
-    if (r.exp && hi == r.smax() && lo == r.smax() - 31) {
+    const int32_t lo0 = lo, hi0 = hi;
+    // An open lane is usually an exponent entry above every class that occurs (rare large classes): its mix is smax at every step, hi
+    // never left smax (one other step would have dropped it for good: nothing climbs back to smax from below), lo stalled at
+    // smax - 31, and all 32 states in between are fixed points of that step -- a plateau lane.  If no symbol of the segment reaches
+    // the entry either, the segment's transfer is the identity and its history row a constant: no walk at all (flag 2).  Otherwise
+    // nothing moves before the first symbol that does reach it: seg_reach = the whole groups of sixteen in front of that symbol.
+    const bool plat = valid && r.exp && lo != hi && hi == r.smax() && lo == r.smax() - 31;
+    bool ident = false;
+    if (plat) {
         const uint32_t *cb = a.clsbase + ((size_t)c * d.tpc + k) * 8;
         uint32_t reach = 0;                                    // symbols of the segment with class >= i
         for (int e = r.i; e < 8; e++) reach += ((k + 1 < nt) ? cb[8 + e] : a.clstotal[(size_t)c * 8 + e]) - cb[e];
-        if (reach == 0) flag = 2u;
+        ident = reach == 0;
     }
-    a.seg_flag[so] = flag;
-    a.seg_lo[so] = lo;
-    a.seg_end[so] = hi;          // re-used as the interval's upper end until k_adapt_b has run
-}
-
-// unresolved segments, second chance: walk the two ends of the interval through the segment itself.  The step is monotone in the
-// state, so if the ends meet every start state in between reaches that same end state: the segment's transfer is a constant and no
-// table is needed (flag 3; k_adapt_c still re-runs it for the outputs once k_adapt_b knows its start).  That is the usual fate of
-// an interval left open by a quiet warm-up (no symbol reached the entry for 1280 items, then one does inside the segment: the
-// 32 stalled states drop together, contract by 31/32 per step on the climb back and merge within ~130 steps).
-__global__ __launch_bounds__(64) void k_adapt_ext(EncDims d, AdArgs a)
-{
-    const uint32_t c = chunk_of(d, blockIdx.z), rec = blockIdx.y;
-    const uint32_t k = blockIdx.x * 64 + threadIdx.x;
-    const AdRec r(rec);
-    const AdStream st = ad_stream(d, r, c, a.cls8, a.clist, a.rle_stride, a.rlen, a.clstotal);
-    const uint32_t nt = (st.n + ATILE - 1) / ATILE;
-    if (k >= nt) return;
-    const size_t so = ((size_t)c * 9 + rec) * d.tpc + k;
-    if (a.seg_flag[so]) return;
-    const uint32_t t0 = k * ATILE, t1 = (t0 + ATILE < st.n) ? t0 + ATILE : st.n;
-    int32_t lo = a.seg_lo[so], hi = a.seg_end[so];
-    const int i = r.i, A = r.A;
-    ad_for_each(r, st, t0, t1, [&](uint32_t, int sy) { lo = adapt_step(lo, i, sy, A); hi = adapt_step(hi, i, sy, A); });
-    if (lo == hi) {
-        a.seg_flag[so] = 3u;
-        a.seg_end[so] = lo;
+    const bool walk = valid && !ident;
+    bool open = walk && lo != hi, quiet = plat;
+    uint32_t miss = 0, fr = 0, u = 0;                          // u: items of the segment done, the same in every lane that walks
+    uint16_t *hist = a.exph + 7 * sym_base(d, c, a.rle_stride) + (size_t)(rec < 7 ? rec : 0) * sym_stride(d, c, a.rle_stride);
+    uint32_t *ma = a.mantad + sym_base(d, c, a.rle_stride);
+    if (r.exp) {
+        const uint8_t *p = st.c8 + t0;
+        const int32_t top = r.smax();
+        uint4 v[4];
+        if (__ballot(open && 64u <= len)) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const uint4 *>(p + ((walk && 64u <= len) ? 16 * q : 0));
+        }
+        while (__ballot(open && u + 64 <= len)) {
+            const bool in = walk && u + 64 <= len;             // lanes whose segment has ended sit the rest out
+            const uint32_t un = (in && u + 128 <= len) ? u + 64 : (in ? u : 0u);
+            uint4 nv[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) nv[q] = *reinterpret_cast<const uint4 *>(p + un + 16 * q);
+            if (in) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+                    const bool one = lo == hi;
+                    uint32_t o[8];
+#pragma unroll
+                    for (int j = 0; j < 16; j++) {
+                        if (j & 1) o[j >> 1] |= (uint32_t)lo << 16;
+                        else o[j >> 1] = (uint32_t)lo & 0xffffu;
+                        const int sy = (int)((w[j >> 2] >> (8 * (j & 3))) & 7u);
+                        lo = adapt_step(lo, i, sy, 8);
+                        hi = adapt_step(hi, i, sy, 8);
+                    }
+                    if (one) {
+                        uint4 *qq = reinterpret_cast<uint4 *>(hist + t0 + u + 16 * q);
+                        qq[0] = make_uint4(o[0], o[1], o[2], o[3]);
+                        qq[1] = make_uint4(o[4], o[5], o[6], o[7]);
+                    }
+                    if (quiet) { if (hi == top) fr = u + 16 * q + 16; else quiet = false; }
+                    if (open && lo == hi) { open = false; miss = u + 16 * q + 16; }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = nv[q];
+            u += 64;
+        }
+        if (walk && u > (len & ~63u)) u = len & ~63u;
+    } else {
+        const uint32_t *p = st.list + t0;
+        uint4 v[4];
+        if (__ballot(open && 16u <= len)) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = *reinterpret_cast<const uint4 *>(p + ((walk && 16u <= len) ? 4 * q : 0));
+        }
+        while (__ballot(open && u + 16 <= len)) {
+            const bool in = walk && u + 16 <= len;
+            const uint32_t un = (in && u + 32 <= len) ? u + 16 : (in ? u : 0u);
+            uint4 nv[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) nv[q] = *reinterpret_cast<const uint4 *>(p + un + 4 * q);
+            if (in) {
+                const bool one = lo == hi;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int m = (int)(w[j] >> 31);
+                        if (one) {
+                            const uint32_t l0 = m ? (uint32_t)lo : 0u, f = m ? 65536u - (uint32_t)lo : (uint32_t)lo;
+                            ma[w[j] & 0x7FFFFFFFu] = l0 | (f << 16);
+                        }
+                        lo = adapt_step(lo, 1, m, 2);
+                        hi = adapt_step(hi, 1, m, 2);
+                    }
+                }
+                if (open && lo == hi) { open = false; miss = u + 16; }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; q++) v[q] = nv[q];
+            u += 16;
+        }
+        if (walk && u > (len & ~15u)) u = len & ~15u;
     }
+    if (!valid) return;
+    if (ident) {
+        a.seg_flag[so] = 2u;
+        return;
+    }
+    if (open) {
+        // less than one group left and still two states (the last segment of a stream): the ends may yet meet, but then the whole
+        // segment is k_adapt_c's
+        ad_for_each(r, st, t0 + u, t1, [&](uint32_t, int sy) { lo = adapt_step(lo, i, sy, A); hi = adapt_step(hi, i, sy, A); });
+        a.seg_miss[so] = (uint16_t)len;
+        a.seg_reach[so] = (uint16_t)fr;
+        if (lo == hi) { a.seg_flag[so] = 3u; a.seg_end[so] = lo; }
+        else { a.seg_flag[so] = 0u; a.seg_lo[so] = lo0; a.seg_end[so] = hi0; }      // k_adapt_tab: the 32 candidates lo0 .. lo0 + 31
+        return;
+    }
+    a.seg_flag[so] = miss ? 3u : 1u;
+    a.seg_miss[so] = (uint16_t)miss;
+    a.seg_reach[so] = (uint16_t)fr;
+    a.seg_end[so] = ad_run_write(r, st, t0 + u, t1, lo, hist, ma);
 }
 
 // transfer table of a segment that is still unresolved: 32 lanes = 32 candidate start states walk the segment together (the
@@ -928,15 +1023,18 @@ __global__ __launch_bounds__(64) void k_adapt_c(EncDims d, AdArgs a)
     const uint32_t flag = a.seg_flag[so];
     if (flag == 1u) return;
     const uint32_t t0 = k * ATILE, t1 = (t0 + ATILE < st.n) ? t0 + ATILE : st.n;
-    if (flag == 2u) {                                          // identity segment (exponent entries only): a constant row
-        uint16_t *hist = a.exph + 7 * sym_base(d, c, a.rle_stride) + (size_t)rec * sym_stride(d, c, a.rle_stride);
-        const uint32_t x = (uint32_t)a.seg_start[so] & 0xffffu, xx = x | (x << 16);
-        uint32_t t = t0;                                       // t0 is a multiple of ATILE: 16-byte aligned in its row
-        for (; t + 8 <= t1; t += 8) *reinterpret_cast<uint4 *>(hist + t) = make_uint4(xx, xx, xx, xx);
-        for (; t < t1; t++) hist[t] = (uint16_t)x;
-        return;
+    // what k_adapt_a left out: [t0, t0 + miss), of which [t0, t0 + fr) is a constant row (an identity segment: all of it; a plateau
+    // lane: up to the first symbol that reaches the entry; fr is a multiple of 16 there, and t0 one of ATILE: 16-byte stores)
+    const uint32_t miss = flag == 2u ? t1 - t0 : a.seg_miss[so], fr = flag == 2u ? t1 - t0 : a.seg_reach[so];
+    uint16_t *hist = a.exph + 7 * sym_base(d, c, a.rle_stride) + (size_t)(rec < 7 ? rec : 0) * sym_stride(d, c, a.rle_stride);
+    const int32_t x0 = a.seg_start[so];
+    if (fr) {
+        const uint32_t x = (uint32_t)x0 & 0xffffu, xx = x | (x << 16);
+        uint32_t t = t0;
+        for (; t + 8 <= t0 + fr; t += 8) *reinterpret_cast<uint4 *>(hist + t) = make_uint4(xx, xx, xx, xx);
+        for (; t < t0 + fr; t++) hist[t] = (uint16_t)x;
     }
-    ad_run_write(r, st, t0, t1, a.seg_start[so], a.exph + 7 * sym_base(d, c, a.rle_stride) + (size_t)(rec < 7 ? rec : 0) * sym_stride(d, c, a.rle_stride), a.mantad + sym_base(d, c, a.rle_stride));
+    if (fr < miss) ad_run_write(r, st, t0 + fr, t0 + miss, x0, hist, a.mantad + sym_base(d, c, a.rle_stride));
 }
 
 // rANS records in coding order.  Pair j = 2t (exponent) / 2t+1 (mantissa) belongs to state lane j & 3; the
@@ -1402,7 +1500,7 @@ struct EncBufs {
     uint16_t *rle;
     uint32_t *clscnt, *clstotal, *ord, *qhist, *qcdf, *dens, *cmap;
     uint8_t *cls8; uint32_t *clist;
-    uint32_t *seg_flag; int32_t *seg_lo, *seg_end, *seg_start; uint16_t *seg_tab;
+    uint32_t *seg_flag; int32_t *seg_lo, *seg_end, *seg_start; uint16_t *seg_tab, *seg_miss, *seg_reach;
     uint16_t *exph; uint32_t *mantad, *pairs; uint4 *recs;
     uint16_t *x16; uint32_t *emask, *etsum, *fstate, *csize;
     uint64_t *stamp;
@@ -1454,6 +1552,8 @@ void enc_layout(Arena &a, const EncDims &d, EncBufs &b, int what, size_t sym_tot
         b.seg_end = a.get<int32_t>(segs);
         b.seg_start = a.get<int32_t>(segs);
         b.seg_tab = a.get<uint16_t>(segs * 32);
+        b.seg_miss = a.get<uint16_t>(segs);
+        b.seg_reach = a.get<uint16_t>(segs);
         b.recs = a.get<uint4>(nlane + RANS_SLACK) + (a.planning ? 0 : RANS_SLACK);   // slack in front: k_rans_lanes' prefetches past the last batch
         b.pairs = (what & LAY_PLAIN) ? a.get<uint32_t>((size_t)d.nch * stride * 2) : nullptr;
     }
@@ -1550,8 +1650,8 @@ int run_model(jpk_ctx *ctx, const uint16_t *d_rle, const uint32_t *d_rlen, const
     aa.exph = b.exph; aa.mantad = b.mantad;
     aa.warm = AD_WARM_DEFAULT;
     aa.seg_flag = b.seg_flag; aa.seg_lo = b.seg_lo; aa.seg_end = b.seg_end; aa.seg_start = b.seg_start; aa.seg_tab = b.seg_tab;
+    aa.seg_miss = b.seg_miss; aa.seg_reach = b.seg_reach;
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_a, dim3((d.tpc + 63) / 64, 9, d.ncl), dim3(64), d, aa);
-    JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_ext, dim3((d.tpc + 63) / 64, 9, d.ncl), dim3(64), d, aa);
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_tab, dim3((d.tpc + 1) / 2, 9, d.ncl), dim3(64), d, aa);
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_b, dim3(jpk_grid((size_t)d.ncl * 16, 64)), dim3(64), d, aa);
     JPK_LAUNCH(ctx, PROF_ENC_ADAPTIVE, 0, k_adapt_c, dim3((d.tpc + 63) / 64, 9, d.ncl), dim3(64), d, aa);
