@@ -731,6 +731,12 @@ __global__ __launch_bounds__(64) void k_dec_rank(const DecBlock *__restrict__ bl
     const uint32_t fast_end = rfl(len >= 64u ? len - 63u : 0u);  // the inner loop stores 64 bytes at i: it runs while i < fast_end
     uint32_t rl = rows[sym][l];                                  // entry `used` is the next unread rank (no wrap between normalisations)
     RankMeta m = meta[sym];
+    // The inner loop reads the next symbol's counters before it has counted the current run.  When the next symbol IS the current one
+    // they are stale: fend then is 0 for one test, the loop leaves, and the counters are read again.  Only a corrupt stream gets
+    // there: list positions that no bucket names hold symbol 0, a rank at or above uniq pulls them forward, and two of them reach
+    // the front; in a valid stream positions 0 and 1 differ.  rank.cpp walks the same list, so the answer is defined and has to be
+    // the same.  (Two scalar instructions off the chain; anything that branches inside the loop costs 7 % of the kernel.)
+    uint32_t fend = fast_end;
     for (;;) {
         // ---- inner loop: z zero ranks, then the real non-zero rank; z + 1 outputs.  The row itself is not touched: these
         // iterations only advance `used` (they never look past the entries known at the last normalisation).  The row and
@@ -743,7 +749,7 @@ __global__ __launch_bounds__(64) void k_dec_rank(const DecBlock *__restrict__ bl
             uint32_t z;
             asm("s_ff1_i32_b64 %0, %1" : "=s"(z) : "s"(nz));    // no non-zero entry: -1, which fails the test below
             uint32_t lim;                                        // room, or 0 behind fast_end (select on the scalar unit, no mask logic)
-            asm("s_cmp_lt_u32 %1, %2\n\ts_cselect_b32 %0, %3, 0" : "=s"(lim) : "s"(i), "s"(fast_end), "s"(room) : "scc");
+            asm("s_cmp_lt_u32 %1, %2\n\ts_cselect_b32 %0, %3, 0" : "=s"(lim) : "s"(i), "s"(fend), "s"(room) : "scc");
             if (!(z < lim)) break;
             const uint32_t nsym = (uint32_t)__builtin_amdgcn_readlane((int)L0, 1);
             // the rank that ends the run is taken out of the row BEFORE the next row is loaded: the old row's register is dead by
@@ -759,6 +765,7 @@ __global__ __launch_bounds__(64) void k_dec_rank(const DecBlock *__restrict__ bl
             i += cnt;
             meta[sym].used = used + cnt;                         // every lane stores the same word: cheaper than masking to one lane
             const uint32_t cur = sym;
+            asm("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, 0, %3" : "=s"(fend) : "s"(nsym), "s"(cur), "s"(fast_end) : "scc");
             sym = nsym; rl = nrl; m = nm;
             if (__builtin_expect(r >= 64u, 0)) { big_r = r; big_sym = cur; break; }
             const uint32_t nxt = wave_shl1(L0);
@@ -766,6 +773,12 @@ __global__ __launch_bounds__(64) void k_dec_rank(const DecBlock *__restrict__ bl
         }
         if (big_r) { list_shift<true>(L0, P, l, big_r, big_sym); continue; }
         if (i >= len) break;
+        if (fend != fast_end) {                                  // the symbol followed itself: its counters, as the run left them
+            fend = fast_end;
+            __builtin_amdgcn_s_waitcnt(0xc07f);                  // lgkmcnt(0)
+            m = meta[sym];
+            continue;
+        }
         // ---- general path ----
         if (psym < 256u) {                                       // land the top-up in flight and unblock its row
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

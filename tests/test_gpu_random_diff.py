@@ -1,7 +1,8 @@
 """Randomised differential parity: structured random blocks (mixtures of runs, repeats, noise and small alphabets at random
 sizes) through the fused GPU entry points against the oracle, byte for byte, plus the round trip.  -m gpu
 Complements the fixed corpora: it reaches the rare paths of the rewritten entropy kernels (classes 6/7, model rebuilds at
-odd positions, rank-decode row top-ups, bucket ends inside a run, chunk boundaries at arbitrary places)."""
+odd positions, chunk boundaries at arbitrary places).  The rank decoder's row top-ups and bucket ends inside a run are met here only by
+chance: test_rank_rows_model.py and test_gpu_rank_rows.py pin them to crafted texts by name."""
 import numpy as np
 import pytest
 
