@@ -214,6 +214,8 @@ JPK_API int jpk_lz77_dedupe(const uint8_t *in, int32_t n, uint8_t *out, int32_t 
 /* flags of the _ex forms of the stock-CLI writer.  JPK_CLI_DEDUPE: S1 = jpk_lz77_dedupe(R) instead of 04 80 | R; the rest of the chain is
  * unchanged (stored filter pieces over S1, Lpx::Encode, stored second LZ77), so out_len depends on the data and jpk_cli_stages_bound /
  * jpk_jam_cli_compress_bound stay bounds.  flags = 0 is the entry without _ex, byte for byte; any other bit is JPK_E_ARG. */
+/* The writer of staged frames (jpk_jam_staged_block_write, jpk_*_jam_staged_compress) takes the same two flags with the same meaning
+ * for S1 and S2, and stops the chain there. */
 #define JPK_CLI_DEDUPE 1
 /* JPK_CLI_FILTERS: every 64 KiB piece of S1 (of the dedupe's S1' with both flags) goes through the filter choice of DESIGN 4.7 "Filters" and
  * leaves as `type, width | transformed piece` (type 0 = reorder + delta, type 2 = in-place delta, widths 1..32) when a candidate's integer
@@ -409,6 +411,57 @@ JPK_API int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64
                                         int64_t *out_len, int32_t in_flight, uint32_t flags);
 JPK_API int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
                                     uint32_t flags);
+
+/* ---- staged frames: the dedupe and the filter choice in front of the BWT, without LPX and without the second LZ77 ------------------- */
+/* A staged frame is the 15-byte header + jpk_block_compress(S2), with S1 and S2 the streams of those names in DESIGN 4.7 ("Writing",
+ * "Dedupe", "Filters"): S1 = 04 80 | R, or jpk_lz77_dedupe(R) with JPK_CLI_DEDUPE; S2 = the 64 KiB pieces of S1 behind 00 00, or behind the
+ * filter choice with JPK_CLI_FILTERS.  It is what Jampack::Comp() (jampack.cpp:29-44) writes when it runs Lz->Compress (-m0), Filter->Encode,
+ * ForwardBwt and Entropy->Encode, i.e. jampack.cpp:36-41 without LocalModel->Encode and the second Lz->Compress (lines 38-39); the decoder is
+ * Jampack::Decomp() (jampack.cpp:47-60) without lines 51-52.  Every stage stream is in the reference's format.  The crc is that of R.  The
+ * header's BlockSize field carries JPK_JAM_STAGED (bit 30; JPK_MAX_BLOCKSIZE is below 2^30): the stock DecompReadBlock (jampack.cpp:150),
+ * jpk_jam_frames, jpk_jam_cli_frames and the plain and stock-CLI decoders refuse such a header, so no decoder takes a staged frame for
+ * another kind.  The flags (JPK_CLI_DEDUPE, JPK_CLI_FILTERS; accepted values 0, 1, 4, 5, anything else JPK_E_ARG) decide only whether the
+ * writer's stages are stored or real: the decoder always runs Filters::Decode, then Lz77::Decompress.  Range reads and an index of staged
+ * archives do not exist (a staged frame's raw size is known only behind its last stage). */
+#define JPK_JAM_STAGED (1 << 30)
+/* one frame, host buffers (the stages on the host, the BWT and the entropy coder on the GPU): arguments and statuses as
+ * jpk_jam_cli_block_write_ex / jpk_jam_cli_block_read; the reader takes staged frames only (any other header is JPK_E_CORRUPT) */
+JPK_API int jpk_jam_staged_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
+JPK_API int jpk_jam_staged_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed);
+/* Jampack::Compress (jampack.cpp:186-260) with that Comp(): the frames of jpk_jam_staged_block_write over consecutive block_size slices,
+ * back to back; the contract of jpk_dev_jam_cli_compress_ex.  Per pass: one batched checksum of the raw slices, the stage chain of the
+ * stock-CLI writer stopped at S2 (k_enc_wrap or k_enc_filters into slot A, behind the k_dd_* launches and their one host read with the
+ * dedupe), jpk_dev_blocks_compress from the A slots, one pack launch.  The bound counts jpk_cli_stages_bound bytes of BWT input per slice. */
+JPK_API int64_t jpk_jam_staged_compress_bound(int64_t in_len, int32_t block_size);
+JPK_API int jpk_dev_jam_staged_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                        int64_t *out_len, int32_t in_flight, uint32_t flags);
+JPK_API int jpk_jam_staged_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
+                                    uint32_t flags);
+/* host walk (DecompReadBlock's checks, jampack.cpp:140-163, with bit 30 allowed) of an archive that may hold plain and staged frames in
+ * any order -- archives are concatenable by format: *frames = the frames in front of the first bad one, *raw_bound = the raw bytes of its
+ * plain frames + the BlockSize of its staged ones (an out_cap that always suffices), *bad_frame as jpk_jam_cli_frames.  Bit 31, or bit 30
+ * with a BlockSize out of range, is a bad frame.  No device call. */
+JPK_API int jpk_jam_staged_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame);
+/* Jampack::Decompress (jampack.cpp:262-336) of such an archive, in passes of at most 128 frames and 4 GiB.  A plain frame decodes in its
+ * place in d_out as in jpk_dev_jam_decompress.  A staged frame goes jpk_dev_blocks_decompress -> slot A, k_pre_filters -> slot B,
+ * jpk_dev_blocks_lz77_decompress -> slot A (at most BlockSize bytes), one batched checksum against the header crcs, and one gather launch
+ * into its place. Bad frames, capacity and success are reported as by jpk_dev_jam_cli_decompress: a stage that runs out of its slot (1.05 x
+ * BlockSize + 4096) is JPK_E_CORRUPT; when the frames of a pass do not fit the rest of out_cap the call is JPK_E_CAPACITY with *out_len =
+ * *raw_bound of jpk_jam_staged_frames and nothing of that pass written.  Arguments are checked before a device is looked for. */
+JPK_API int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                          int32_t *frames, int32_t *bad_frame);
+JPK_API int jpk_jam_staged_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame);
+/* Lz77::Decompress(Buffer,Buffer) (lz77.hpp:46, lz77.cpp:678-714) of n blocks in two launches: bytes, lengths and statuses are those of
+ * jpk_dev_blocks_lz77_decompress for every input, valid or not.  k_lzx_plan (one wave per block) writes a record per literal run and per
+ * match, at most in_len / 64 + 4 per block in ctx's arena; k_lzx_copy fills aligned 16-byte words of the output from the records, a byte
+ * of a match finding its literal in at most 8 hops.  A block that fails a check, needs more records or a longer chase goes through
+ * k_pre_lz77 in one more launch.  The arguments are checked before a device is looked for.  No entry of the library calls it: it is far
+ * faster than the serial kernel on stored and shallow streams and slower on the deep streams the dedupe writes of large blocks of real
+ * sources ("Tried"), so the archive decoders stay with jpk_dev_blocks_lz77_decompress. */
+JPK_API int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                       const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/* how many blocks of ctx's last jpk_dev_blocks_lz77_expand call took the two parallel launches and how many the serial kernel */
+JPK_API int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial);
 
 /* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
 /* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the

@@ -133,6 +133,16 @@ _SIGS = {
     "jpk_dev_jam_cli_decompress": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_jam_cli_decompress": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_jam_cli_frames": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(C.c_int64), _i32p]),
+    "jpk_jam_staged_block_write": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, C.c_int32, _i32p, C.c_uint32]),
+    "jpk_jam_staged_block_read": (C.c_int, [_vp, C.c_int32, _vp, C.c_int32, _i32p, _i32p]),
+    "jpk_jam_staged_compress_bound": (C.c_int64, [C.c_int64, C.c_int32]),
+    "jpk_dev_jam_staged_compress": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
+    "jpk_jam_staged_compress": (C.c_int, [_vp, C.c_int64, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.c_uint32]),
+    "jpk_jam_staged_frames": (C.c_int, [_vp, C.c_int64, _i32p, C.POINTER(C.c_int64), _i32p]),
+    "jpk_dev_jam_staged_decompress": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_jam_staged_decompress": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_dev_blocks_lz77_expand": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
+    "jpk_debug_lz77_expand_last": (C.c_int, [_vp, _i32p, _i32p]),
     "jpk_dev_suffix_array": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "jpk_dev_sort_pairs_u64": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32]),
     "jpk_dev_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_uint32)]),

@@ -470,6 +470,74 @@ def jam_cli_decompress_all(stream, check: bool = True):
     return out[: n.value]
 
 
+JAM_STAGED = 1 << 30   # JPK_JAM_STAGED: the bit a staged frame's BlockSize field carries
+
+
+def jam_staged_block_write(block, block_size: int, cap: int | None = None, dedupe: bool = False, filters: bool = False, flags: int | None = None) -> np.ndarray:
+    """jpk_jam_staged_block_write: one staged frame -- the header with JAM_STAGED in the BlockSize field + block_compress of S2, the
+    stage chain of cli_stages_encode stopped in front of Lpx::Encode.  flags (an int) overrides dedupe / filters."""
+    t = _np_u8(block)
+    cap = JAM_HEADER + ans_capacity(cli_stages_bound(len(t)) + TRAILER) if cap is None else cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_int32(0)
+    fl = _cli_flags(dedupe, filters) if flags is None else flags
+    _chk(lib().jpk_jam_staged_block_write(_ptr(t), len(t), block_size, out.ctypes.data, cap, C.byref(n), fl), "jam_staged_block_write")
+    return out[: n.value]
+
+
+def jam_staged_block_read(stream, cap: int):
+    """jpk_jam_staged_block_read: one staged frame -> (block bytes, bytes consumed); entropy decode and inverse BWT on the GPU,
+    Filters::Decode and Lz77::Decompress on the host"""
+    c = _np_u8(stream)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n, used = C.c_int32(0), C.c_int32(0)
+    _chk(lib().jpk_jam_staged_block_read(_ptr(c), len(c), out.ctypes.data, cap, C.byref(n), C.byref(used)), "jam_staged_block_read")
+    return out[: n.value], used.value
+
+
+def jam_staged_compress_bound(n: int, block_size: int = 8 << 20) -> int:
+    """jpk_jam_staged_compress_bound: the largest archive of staged frames n input bytes can give with this block size"""
+    b = int(lib().jpk_jam_staged_compress_bound(n, block_size))
+    _chk(b if b < 0 else 0, "jpk_jam_staged_compress_bound")
+    return b
+
+
+def jam_staged_compress(data, block_size: int = 8 << 20, dedupe: bool = False, filters: bool = False, flags: int | None = None) -> np.ndarray:
+    """An archive of staged frames by one jpk_jam_staged_compress call: the dedupe and the filter choice (or their stored forms) in
+    front of the BWT on the GPU, no LPX.  This library's decoders read it; an unmodified `jampack d` refuses its headers."""
+    t = _np_u8(data)
+    out = np.empty(max(jam_staged_compress_bound(len(t), block_size), 1), dtype=np.uint8)
+    n = C.c_int64(0)
+    fl = _cli_flags(dedupe, filters) if flags is None else flags
+    _chk(lib().jpk_jam_staged_compress(_ptr(t), len(t), block_size, out.ctypes.data, len(out), C.byref(n), 0, fl), "jam_staged_compress")
+    return out[: n.value]
+
+
+def jam_staged_frames(stream):
+    """jpk_jam_staged_frames: host walk of an archive of plain and staged frames -> (frames, raw bound, bad frame or -1); the raw bound
+    counts a plain frame at its raw size and a staged one at its BlockSize"""
+    c = _np_u8(stream)
+    k, bound, bad = C.c_int32(0), C.c_int64(0), C.c_int32(-1)
+    rc = lib().jpk_jam_staged_frames(_ptr(c), len(c), C.byref(k), C.byref(bound), C.byref(bad))
+    if rc not in (0, -3):
+        raise JampackError(rc, "jpk_jam_staged_frames")
+    return k.value, bound.value, bad.value
+
+
+def jam_staged_decompress(stream, check: bool = True):
+    """An archive of plain and staged frames by ONE jpk_jam_staged_decompress call.  Returns the raw bytes; check=False: (raw bytes in
+    front of the first bad frame, frames, bad frame, status), no exception."""
+    c = _np_u8(stream)
+    _, bound, _ = jam_staged_frames(c)
+    out = np.empty(max(bound, 1), dtype=np.uint8)
+    n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+    rc = lib().jpk_jam_staged_decompress(_ptr(c), len(c), out.ctypes.data, bound, C.byref(n), C.byref(nf), C.byref(bf))
+    if not check:
+        return out[: n.value if rc in (0, -3) else 0], nf.value, bf.value, int(rc)
+    _chk(rc, f"jam_staged_decompress: frame {bf.value}")
+    return out[: n.value]
+
+
 def _dptr(x):
     """device pointer of a torch CUDA tensor or a raw int"""
     if x is None:
@@ -578,6 +646,17 @@ class Context:
         """jpk_dev_blocks_lz77_decompress: Lz77::Decompress of independent blocks in one launch -> (out_len list, status list)"""
         return self._batch(lib().jpk_dev_blocks_lz77_decompress, "jpk_dev_blocks_lz77_decompress", d_ins, in_lens, d_outs, out_caps)
 
+    def blocks_lz77_expand(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_lz77_expand: the same stage through the parallel expander (two launches, the serial kernel for the blocks
+        they leave to it) -> (out_len list, status list); lz77_expand_last() says which way the blocks went"""
+        return self._batch(lib().jpk_dev_blocks_lz77_expand, "jpk_dev_blocks_lz77_expand", d_ins, in_lens, d_outs, out_caps)
+
+    def lz77_expand_last(self):
+        """jpk_debug_lz77_expand_last -> (blocks of the last blocks_lz77_expand call on the parallel path, on the serial path)"""
+        p, q = C.c_int32(0), C.c_int32(0)
+        _chk(lib().jpk_debug_lz77_expand_last(self._h, C.byref(p), C.byref(q)), "jpk_debug_lz77_expand_last")
+        return p.value, q.value
+
     def blocks_lpx_decode(self, d_ins, lens, d_outs):
         """jpk_dev_blocks_lpx_decode: Lpx::Decode of independent blocks in one launch (output length = input length) -> status list"""
         n = len(d_ins)
@@ -671,6 +750,26 @@ class Context:
         _chk(lib().jpk_dev_jam_cli_compress_ex(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight,
                                                _cli_flags(dedupe, filters)), "jpk_dev_jam_cli_compress_ex")
         return n.value
+
+    def jam_staged_compress(self, d_in, in_len, block_size, d_out, out_cap, in_flight: int = 0, dedupe: bool = False, filters: bool = False,
+                            flags: int | None = None) -> int:
+        """jpk_dev_jam_staged_compress: the archive of staged frames of d_in[0..in_len) into d_out; returns its length"""
+        n = C.c_int64(0)
+        fl = _cli_flags(dedupe, filters) if flags is None else flags
+        _chk(lib().jpk_dev_jam_staged_compress(self._h, _dptr(d_in), in_len, block_size, _dptr(d_out), out_cap, C.byref(n), in_flight, fl),
+             "jpk_dev_jam_staged_compress")
+        return n.value
+
+    def jam_staged_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):
+        """jpk_dev_jam_staged_decompress: an archive of plain and staged frames in HBM -> (raw bytes, frames, bad frame); check=False:
+        (raw bytes, frames, bad frame, status), no exception (out_len is the raw bound on JPK_E_CAPACITY, the verified bytes in front
+        of the bad frame on JPK_E_CORRUPT)"""
+        n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+        rc = lib().jpk_dev_jam_staged_decompress(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf))
+        if not check:
+            return n.value, nf.value, bf.value, int(rc)
+        _chk(rc, "jpk_dev_jam_staged_decompress")
+        return n.value, nf.value, bf.value
 
     def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):
         """jpk_dev_jam_decompress -> (raw bytes, frames, bad frame); check=False: (raw bytes, frames, bad frame, status), no exception

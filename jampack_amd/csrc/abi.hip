@@ -113,7 +113,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
     "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
     "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit", "k_enc_filters",
-    "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
+    "k_lzx_plan", "k_lzx_copy", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {
@@ -1857,4 +1857,54 @@ extern "C" int jpk_jam_cli_block_write_ex(const uint8_t *in, int32_t in_len, int
 extern "C" int jpk_jam_cli_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len)
 {
     return jpk_jam_cli_block_write_ex(in, in_len, block_size, out, out_cap, out_len, 0u);
+}
+
+// One staged frame ("Staged frames"): Jampack::Comp() (jampack.cpp:29-44) with the stage chain stopped at S2 -- no
+// LocalModel->Encode, no second Lz->Compress (jampack.cpp:38-39) --, the header of CompWriteBlock with JPK_JAM_STAGED in the BlockSize field.
+extern "C" int jpk_jam_staged_block_write(const uint8_t *in, int32_t in_len, int32_t block_size, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
+{
+    if (!out || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
+    if (!jpk_jam_block_size_ok(block_size) || in_len > block_size) return JPK_E_ARG;     // InitComp, jampack.cpp:70
+    if (out_cap < JPK_JAM_HEADER_BYTES) return JPK_E_CAPACITY;
+    const int32_t cap = (int32_t)jpk_cli_stages_bound(in_len);                       // |S2| <= n + 2 + 2 P, two below it
+    static thread_local std::vector<uint8_t> s2;
+    try { if (s2.size() < (size_t)cap) s2.resize((size_t)cap); } catch (...) { return JPK_E_ALLOC; }
+    int32_t m = 0, n = 0;
+    JPK_TRY(jpk_staged_s2_host(in, in_len, s2.data(), cap, &m, flags));
+    JPK_TRY(jpk_block_compress(s2.data(), m, out + JPK_JAM_HEADER_BYTES, out_cap - JPK_JAM_HEADER_BYTES, &n));
+    const uint32_t crc = jpk_checksum_host(in, in_len);
+    const int32_t field = block_size | JPK_JAM_STAGED;
+    memcpy(out, "JAM", 3);
+    memcpy(out + 3, &crc, 4);
+    memcpy(out + 7, &n, 4);
+    memcpy(out + 11, &field, 4);
+    *out_len = n + JPK_JAM_HEADER_BYTES;
+    return JPK_OK;
+}
+
+// The reader: Jampack::Decomp() (jampack.cpp:47-60) without its lines 51-52 -- Ans::Decode + InverseBwt on the GPU, Filter->Decode and
+// Lz->Decompress on the host, the crc check.  A header without JPK_JAM_STAGED is not a staged frame: JPK_E_CORRUPT.
+extern "C" int jpk_jam_staged_block_read(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len, int32_t *consumed)
+{
+    if (!in || !out || !out_len || in_len < 0 || out_cap < 0) return JPK_E_ARG;
+    if (in_len < JPK_JAM_HEADER_BYTES || (in[14] & 0xC0u) != 0x40u) return JPK_E_CORRUPT;   // bit 30 of the little-endian BlockSize field, bit 31 clear
+    uint8_t h[JPK_JAM_HEADER_BYTES];
+    memcpy(h, in, sizeof h);
+    h[14] &= 0xBFu;
+    uint32_t crc;
+    int32_t csize, block_size;
+    if (!jpk_jam_header_parse(h, in_len, &crc, &csize, &block_size)) return JPK_E_CORRUPT;
+    const int64_t cap64 = (int64_t)((double)block_size * 1.05) + 4096;             // the stage buffers of jpk_jam_cli_block_read
+    if (cap64 > 0x7fffffff) return JPK_E_ARG;
+    const int32_t cap = (int32_t)cap64;
+    static thread_local std::vector<uint8_t> a, b;
+    try { if (a.size() < (size_t)cap) a.resize((size_t)cap); if (b.size() < (size_t)cap) b.resize((size_t)cap); } catch (...) { return JPK_E_ALLOC; }
+    int32_t n = 0, m = 0;
+    JPK_TRY(jpk_block_decompress(in + JPK_JAM_HEADER_BYTES, csize, a.data(), cap, &n));     // Ans::Decode + InverseBwt
+    JPK_TRY(jpk_filters_decode(a.data(), n, b.data(), cap, &m));                             // Filter->Decode
+    JPK_TRY(jpk_lz77_decompress(b.data(), m, out, out_cap, &n));                             // Lz->Decompress
+    if (jpk_checksum_host(out, n) != crc) return JPK_E_CORRUPT;                              // "Detected corrupt block!"
+    *out_len = n;
+    if (consumed) *consumed = csize + JPK_JAM_HEADER_BYTES;
+    return JPK_OK;
 }

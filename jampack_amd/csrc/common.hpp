@@ -37,7 +37,7 @@ enum JpkProfId {
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
     PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM,
     PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT, PROF_ENC_FILTERS,
-    PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
+    PROF_LZX_PLAN, PROF_LZX_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 
@@ -105,6 +105,8 @@ struct jpk_ctx {
     uint8_t *jam_scratch = nullptr;
     size_t jam_scratch_cap = 0;
     jpk_stats stats;
+    // jpk_dev_blocks_lz77_expand: the blocks of the last call that took the parallel path and the serial one (jpk_debug_lz77_expand_last)
+    int32_t lzx_parallel = 0, lzx_serial = 0;
     // profiler
     bool prof_on = false;
     std::vector<JpkProfPending> prof_pending;
@@ -294,9 +296,10 @@ int jpk_ans_decoded_sizes(jpk_ctx *ctx, int nblk, const uint8_t *const *d_in, co
 // .jam archives (jam.hip).  One frame of the walk: where its payload starts, its header fields
 struct JamWalkFrame { uint64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int32_t pad; };
 // one wave walks up to max_frames frame headers of d_in[0..in_len) from `start`: table[0..count); mail[0] = count, mail[1] = 1 when
-// the walk stopped at a bad frame (index count), mail[2..3] = offset where it stopped.  Enqueued only.
+// the walk stopped at a bad frame (index count), mail[2..3] = offset where it stopped.  Enqueued only.  staged_ok: staged frames pass, and
+// their block_size in the table keeps JPK_JAM_STAGED
 int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
-                         uint32_t *d_mail);
+                         uint32_t *d_mail, bool staged_ok = false);
 // one frame of the pack: its payload slot, its offset in the pass's output, its payload size
 struct JamPackFrame { const uint8_t *slot; uint64_t off; int32_t psize; int32_t pad; };
 constexpr int JPK_JAM_PASS_FRAMES = 128;                     // frames per pass of the archive calls (and per pack launch)
@@ -314,3 +317,9 @@ int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_
 // flags & JPK_CLI_FILTERS: k_enc_filters in the place of k_enc_wrap, same sources, same lengths.
 int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out,
                           uint32_t flags, int32_t *s4_len);
+// the same chain stopped at S2, for staged frames: k_enc_lpx is not launched, d_mid[b] (required) receives S2 and s2_len[b] its length;
+// d_tmp[b] (jpk_cli_stages_bound bytes) is where the dedupe leaves S1'
+int jpk_staged_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_tmp,
+                             uint32_t flags, int32_t *s2_len);
+// S2 of the n bytes at in on the host (prestage.cpp): the stage chain of jpk_cli_stages_encode_ex in front of Lpx::Encode
+int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);

@@ -14,8 +14,9 @@ constexpr int PACK_TB = 256;
 // One wave.  A frame's 15 header bytes are loaded by lanes 0..14 at once; the chain of frames is serial by format (frame k + 1 starts
 // behind frame k's payload).  A frame is accepted as DecompReadBlock accepts it: magic "JAM", MIN_BLOCKSIZE <= BlockSize <=
 // MAX_BLOCKSIZE, 0 <= payload size <= MAX_BLOCKSIZE, and the payload ends inside the archive; 1..14 bytes left over are a bad frame too.
+// staged_ok: a BlockSize field with JPK_JAM_STAGED (bit 30) set is checked without it and goes into the table as it is.
 __global__ __launch_bounds__(64) void k_jam_walk(const uint8_t *__restrict__ in, uint64_t in_len, uint64_t start, uint32_t max_frames,
-                                                 JamWalkFrame *__restrict__ table, uint32_t *__restrict__ mail)
+                                                 JamWalkFrame *__restrict__ table, uint32_t *__restrict__ mail, uint32_t staged_ok)
 {
     const int l = (int)(threadIdx.x & 63u);
     uint64_t o = start;
@@ -28,12 +29,13 @@ __global__ __launch_bounds__(64) void k_jam_walk(const uint8_t *__restrict__ in,
         for (int j = 0; j < JPK_JAM_HEADER_BYTES; j++) h[j] = (uint32_t)__builtin_amdgcn_readlane(mine, j);
         const uint32_t crc = h[3] | (h[4] << 8) | (h[5] << 16) | (h[6] << 24);
         const int32_t psize = (int32_t)(h[7] | (h[8] << 8) | (h[9] << 16) | (h[10] << 24));
-        const int32_t bs = (int32_t)(h[11] | (h[12] << 8) | (h[13] << 16) | (h[14] << 24));
+        const int32_t field = (int32_t)(h[11] | (h[12] << 8) | (h[13] << 16) | (h[14] << 24));
+        const int32_t bs = (staged_ok && field > 0) ? (field & ~JPK_JAM_STAGED) : field;
         if (h[0] != 'J' || h[1] != 'A' || h[2] != 'M' || bs < JPK_MIN_BLOCKSIZE || bs > JPK_MAX_BLOCKSIZE || psize < 0 || psize > JPK_MAX_BLOCKSIZE ||
             (uint64_t)psize > in_len - o - JPK_JAM_HEADER_BYTES) { bad = 1; break; }
         if (l == 0) {
             JamWalkFrame f;
-            f.payload_off = o + JPK_JAM_HEADER_BYTES; f.psize = psize; f.crc = crc; f.block_size = bs; f.pad = 0;
+            f.payload_off = o + JPK_JAM_HEADER_BYTES; f.psize = psize; f.crc = crc; f.block_size = field; f.pad = 0;
             table[count] = f;
         }
         o += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)psize;
@@ -159,9 +161,9 @@ __global__ __launch_bounds__(PACK_TB) void k_jam_gather(const JamGatherPiece *__
 }  // namespace
 
 int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
-                         uint32_t *d_mail)
+                         uint32_t *d_mail, bool staged_ok)
 {
-    JPK_LAUNCH(ctx, PROF_JAM, 0, k_jam_walk, dim3(1), dim3(64), d_in, in_len, start, max_frames, d_table, d_mail);
+    JPK_LAUNCH(ctx, PROF_JAM, 0, k_jam_walk, dim3(1), dim3(64), d_in, in_len, start, max_frames, d_table, d_mail, staged_ok ? 1u : 0u);
     JPK_HIP(hipGetLastError());
     return JPK_OK;
 }

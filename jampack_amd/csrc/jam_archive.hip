@@ -20,12 +20,17 @@
 // of the raw slices.  With JPK_CLI_DEDUPE the k_dd_* launches come first (raw slice -> S1' in slot B), the pass's S1' lengths are read
 // on the host once, and the batch's input lengths are those of the S4 that k_enc_wrap / k_enc_lpx then make of them.  With JPK_CLI_FILTERS
 // k_enc_filters stands where k_enc_wrap does; the lengths are the same.
+// The writer of staged frames (jpk_dev_jam_staged_compress; DESIGN 4.6, "Staged frames") is that pass with the chain stopped at S2: no k_enc_lpx,
+// the A slots are the batch's inputs, and the pack writes BlockSize | JPK_JAM_STAGED.  Its reader takes plain and staged frames in one archive.
 
 // one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
-struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; };
+// (staged: a staged frame, DESIGN 4.6 -- block_size is the field without JPK_JAM_STAGED, raw the bytes of its S2)
+struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; bool staged = false; };
 
 namespace {
 constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
+// what an archive call reads or writes: plain frames, frames of the stock CLI, or (reading) plain and staged frames in any order
+constexpr int JAM_PLAIN = 0, JAM_CLI = 1, JAM_STAGED = 2;
 
 int jam_pass_frames(int32_t block_size)
 {
@@ -43,9 +48,20 @@ bool jam_decoded_ok(int64_t decoded, int32_t block_size, bool cli)
     return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= (cli ? jam_cli_cap(block_size) : block_size);
 }
 
-// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); cli: frames of the
-// stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders)
-void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
+// jpk_jam_header_parse with JPK_JAM_STAGED allowed (staged_ok) in a BlockSize field whose bit 31 is clear: f's header fields
+bool jam_header_parse(const uint8_t *h, int64_t avail, bool staged_ok, JamFrame *f)
+{
+    if (avail < JPK_JAM_HEADER_BYTES) return false;
+    uint8_t c[JPK_JAM_HEADER_BYTES];
+    memcpy(c, h, sizeof c);
+    f->staged = staged_ok && (c[14] & 0xC0u) == 0x40u;                 // the field is little-endian: byte 14 holds bits 24-31
+    if (f->staged) c[14] &= 0xBFu;
+    return jpk_jam_header_parse(c, avail, &f->crc, &f->psize, &f->block_size);
+}
+
+// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); JAM_CLI: frames of the
+// stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders), and so for the staged frames of JAM_STAGED
+void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN)
 {
     *bad = -1;
     int64_t o = 0;
@@ -54,8 +70,8 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
         f.payload_off = o + JPK_JAM_HEADER_BYTES;
         int64_t decoded = 0;
         // a bad header (1..14 trailing bytes are one), bad chunk headers in the payload, or a payload that declares too much
-        if (!jpk_jam_header_parse(in + o, in_len - o, &f.crc, &f.psize, &f.block_size) ||
-            jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size, cli)) {
+        if (!jam_header_parse(in + o, in_len - o, kind == JAM_STAGED, &f) ||
+            jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size, kind == JAM_CLI || f.staged)) {
             *bad = (int32_t)fr.size();
             return;
         }
@@ -66,7 +82,7 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
 }
 
 // the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
-int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, bool cli = false)
+int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN)
 {
     *bad = -1;
     JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
@@ -77,7 +93,7 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
     std::vector<int64_t> dec;
     uint64_t o = 0;
     while (o < (uint64_t)in_len) {
-        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail->read));
+        JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail->read, kind == JAM_STAGED));
         JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
         uint32_t m[4];
         JPK_TRY(jpk_read_mail(ctx, m, 4));                   // synchronises: the table is on the host too
@@ -86,8 +102,10 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
         for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
         JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
         for (int i = 0; i < n; i++) {
-            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], h[i].block_size, cli)) { *bad = (int32_t)fr.size(); return JPK_OK; }
-            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, h[i].block_size, dec[i] - JPK_TRAILER_BYTES});
+            const bool staged = (h[i].block_size & JPK_JAM_STAGED) != 0;       // (only a walk with staged_ok lets such a field through)
+            const int32_t bs = h[i].block_size & ~JPK_JAM_STAGED;
+            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], bs, kind == JAM_CLI || staged)) { *bad = (int32_t)fr.size(); return JPK_OK; }
+            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, bs, dec[i] - JPK_TRAILER_BYTES, staged});
         }
         if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
         o = ((uint64_t)m[3] << 32) | m[2];
@@ -106,7 +124,7 @@ template <class W> size_t jam_pass_end(size_t n, size_t k, W weight)
 }
 
 // what a frame weighs in a decompress pass and in the size answers: its raw bytes, or (cli: known only behind its last stage) its BlockSize
-int64_t jam_weight(const JamFrame &f, bool cli) { return cli ? f.block_size : f.raw; }
+int64_t jam_weight(const JamFrame &f, bool cli) { return (cli || f.staged) ? f.block_size : f.raw; }
 size_t jam_pass_end(const std::vector<JamFrame> &fr, size_t k, bool cli)
 {
     return jam_pass_end(fr.size(), k, [&](size_t i) { return jam_weight(fr[i], cli); });
@@ -174,13 +192,15 @@ int32_t jam_bwt_len(int32_t len, bool cli) { return cli ? (int32_t)jpk_cli_stage
 int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (int64_t)jpk_multi_comp_cap(jam_bwt_len(len, cli)); }
 
 // one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
-// of the stock CLI
+// of the stock CLI, or staged frames (kind): S2 in slot A is the BWT's input, slot B the dedupe's room (none without the dedupe)
 int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
-                      int32_t in_flight, bool cli, uint32_t flags)
+                      int32_t in_flight, int kind, uint32_t flags)
 {
+    const bool cli = kind != JAM_PLAIN;
+    const bool slot_b = kind == JAM_CLI || (flags & JPK_CLI_DEDUPE) != 0;
     const int n = (int)((len + block_size - 1) / block_size);
     std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
-    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n);
+    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n, nullptr);
     std::vector<int32_t> lens((size_t)n), blens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
     const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
     size_t need = o_slots;
@@ -190,7 +210,7 @@ int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t bl
         blens[i] = jam_bwt_len(lens[i], cli);
         caps[i] = (int32_t)jpk_multi_comp_cap(blens[i]);
         need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
-        if (cli) need += 2 * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
+        if (cli) need += (slot_b ? 2 : 1) * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
     }
     JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
     uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
@@ -201,13 +221,14 @@ int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t bl
         bwt_in[i] = ins[i];
         if (cli) {
             sa[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
-            sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
-            bwt_in[i] = sb[i];
+            if (slot_b) { sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64); }
+            bwt_in[i] = kind == JAM_STAGED ? sa[i] : sb[i];
         }
     }
     // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
     JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
-    if (cli) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
+    if (kind == JAM_CLI) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
+    if (kind == JAM_STAGED) JPK_TRY(jpk_staged_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
     JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
     for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
     std::vector<JamPackFrame> fr((size_t)n);
@@ -218,7 +239,7 @@ int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t bl
     }
     if ((int64_t)pos > out_room) return JPK_E_CAPACITY;
     JPK_HIP(hipMemcpyAsync(d_frames, fr.data(), (size_t)n * sizeof(JamPackFrame), hipMemcpyHostToDevice, ctx->stream));
-    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, block_size, d_out, pos));
+    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, kind == JAM_STAGED ? (block_size | JPK_JAM_STAGED) : block_size, d_out, pos));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     *pass_len = (int64_t)pos;
     return JPK_OK;
@@ -234,17 +255,18 @@ int64_t jam_compress_bound(int64_t in_len, int32_t block_size, bool cli)
 }
 
 int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                     int32_t in_flight, bool cli, uint32_t flags = 0u)
+                     int32_t in_flight, int kind, uint32_t flags = 0u)
 {
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
+    // (JPK_ENTER taken apart: the argument checks come before the first device call)
+    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!d_in || !d_out)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;                     // InitComp, jampack.cpp:70
+    JPK_HIP(hipSetDevice(ctx->device));
     *out_len = 0;
     const int64_t step = (int64_t)jam_pass_frames(block_size) * block_size;
     int64_t pos = 0;
     for (int64_t o = 0; o < in_len; o += step) {
         int64_t n = 0;
-        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, cli, flags));
+        JPK_TRY(jam_compress_pass(ctx, d_in + o, std::min(step, in_len - o), block_size, d_out + pos, out_cap - pos, &n, in_flight, kind, flags));
         pos += n;
     }
     *out_len = pos;
@@ -254,23 +276,30 @@ int jam_compress_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t 
 
 extern "C" int64_t jpk_jam_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, false); }
 extern "C" int64_t jpk_jam_cli_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, true); }
+extern "C" int64_t jpk_jam_staged_compress_bound(int64_t in_len, int32_t block_size) { return jam_compress_bound(in_len, block_size, true); }
 
 extern "C" int jpk_dev_jam_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
                                     int32_t in_flight)
 {
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, false);
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, JAM_PLAIN);
 }
 
 extern "C" int jpk_dev_jam_cli_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
                                         int64_t *out_len, int32_t in_flight)
 {
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true);
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, JAM_CLI);
 }
 
 extern "C" int jpk_dev_jam_cli_compress_ex(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
                                            int64_t *out_len, int32_t in_flight, uint32_t flags)
 {
-    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, true, flags);
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, JAM_CLI, flags);
+}
+
+extern "C" int jpk_dev_jam_staged_compress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t block_size, uint8_t *d_out, int64_t out_cap,
+                                           int64_t *out_len, int32_t in_flight, uint32_t flags)
+{
+    return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, JAM_STAGED, flags);
 }
 
 extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
@@ -318,21 +347,23 @@ extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t
 
 namespace {
 // jpk_jam_frames / jpk_jam_cli_frames: the host walk, *len = the raw bytes (cli: the sum of BlockSize) of the frames it found
-int jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *len, int32_t *bad_frame, bool cli)
+int jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *len, int32_t *bad_frame, int kind)
 {
+    const bool cli = kind == JAM_CLI;
     if (in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
     std::vector<JamFrame> fr;
     int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad, cli);
+    jam_walk_host(in, in_len, fr, &bad, kind);
     if (frames) *frames = (int32_t)fr.size();
     if (len) *len = jam_sum(fr, 0, fr.size(), cli);
     if (bad_frame) *bad_frame = bad;
     return bad >= 0 ? JPK_E_CORRUPT : JPK_OK;
 }
 
-int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, bool cli,
+int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight, int kind,
                       uint32_t flags = 0u)
 {
+    const bool cli = kind != JAM_PLAIN;
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && (!in || !out)) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
     if (!jpk_jam_block_size_ok(block_size)) return JPK_E_ARG;
     *out_len = 0;
@@ -347,7 +378,7 @@ int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uin
         JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)bound + 64));
         JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
         int64_t n = 0;
-        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, cli, flags));
+        JPK_TRY(jam_compress_dev(ctx, ctx->stage_in, len, block_size, ctx->stage_res, bound, &n, in_flight, kind, flags));
         if (n > out_cap - pos) return JPK_E_CAPACITY;
         JPK_HIP(hipMemcpyAsync(out + pos, ctx->stage_res, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         JPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -360,28 +391,39 @@ int jam_compress_host(const uint8_t *in, int64_t in_len, int32_t block_size, uin
 
 extern "C" int jpk_jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_len, int32_t *bad_frame)
 {
-    return jam_frames(in, in_len, frames, raw_len, bad_frame, false);
+    return jam_frames(in, in_len, frames, raw_len, bad_frame, JAM_PLAIN);
 }
 
 extern "C" int jpk_jam_cli_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame)
 {
-    return jam_frames(in, in_len, frames, raw_bound, bad_frame, true);
+    return jam_frames(in, in_len, frames, raw_bound, bad_frame, JAM_CLI);
+}
+
+extern "C" int jpk_jam_staged_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame)
+{
+    return jam_frames(in, in_len, frames, raw_bound, bad_frame, JAM_STAGED);
+}
+
+extern "C" int jpk_jam_staged_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
+                                       uint32_t flags)
+{
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, JAM_STAGED, flags);
 }
 
 extern "C" int jpk_jam_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
 {
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, false);
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, JAM_PLAIN);
 }
 
 extern "C" int jpk_jam_cli_compress(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight)
 {
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true);
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, JAM_CLI);
 }
 
 extern "C" int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t block_size, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t in_flight,
                                        uint32_t flags)
 {
-    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, true, flags);
+    return jam_compress_host(in, in_len, block_size, out, out_cap, out_len, in_flight, JAM_CLI, flags);
 }
 
 // the frame table behind jpk_jam_index (the range reads below; the stock-CLI calls make one from what they decode)
@@ -431,6 +473,8 @@ namespace {
 //   prefix  every stage runs on the frames in front of the first one that has failed so far (a whole archive stops there); otherwise
 //           on all surviving frames, compacted after every stage -- a frame that failed a stage has no lengths for the next one
 //   exact   a frame whose raw size is not dst_cap[i] is JPK_E_CORRUPT (the reader: dst_cap is the indexed raw size)
+//   staged  staged frames: the list without the first Lz77 and the Lpx stage -- stage 0 into A, Filters A -> B, and
+//           Lz77 B -> dst with the serial kernel (the parallel expander missed its condition: DESIGN 4.6, "Tried")
 struct CliPass {
     int n;
     const uint8_t *const *ins; const int32_t *lens;
@@ -438,6 +482,7 @@ struct CliPass {
     uint8_t *const *dst; const int32_t *dst_cap;
     const uint32_t *crc; uint32_t *d_crc;
     bool prefix, exact;
+    bool staged = false;
 };
 
 // st[i] = JPK_OK and raw[i] = the raw size of a frame that went through every stage and matches its crc -- it is at dst[i] --, else the
@@ -477,11 +522,11 @@ int jam_cli_pass(jpk_ctx *ctx, const CliPass &p, int32_t *raw, int32_t *st)
         JPK_TRY(jpk_dev_blocks_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));           // Ans::Decode + InverseBwt
         settle();
     }
-    if ((m = aim(p.a, p.b, p.caps))) {
+    if (!p.staged && (m = aim(p.a, p.b, p.caps))) {
         JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));      // Lz->Decompress
         settle();
     }
-    if ((m = aim(p.b, p.a, p.caps))) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, src.data(), len.data(), out.data(), s.data()));      // LocalModel->Decode (never fails)
+    if (!p.staged && (m = aim(p.b, p.a, p.caps))) JPK_TRY(jpk_dev_blocks_lpx_decode(ctx, m, src.data(), len.data(), out.data(), s.data()));      // LocalModel->Decode (never fails)
     if ((m = aim(p.a, p.b, p.caps))) {
         JPK_TRY(jpk_dev_blocks_filters_decode(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));       // Filter->Decode
         settle();
@@ -517,7 +562,7 @@ int jam_cli_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d
     if (in_len == 0) return JPK_OK;                        // an empty archive: no frame, no device call
     std::vector<JamFrame> fr;
     int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, true));
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, JAM_CLI));
     const int64_t raw_bound = jam_sum(fr, 0, fr.size(), true);
     const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
     int64_t pos = 0;
@@ -605,11 +650,124 @@ extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int
     return jpk_dev_jam_cli_decompress_ix(ctx, d_in, in_len, d_out, out_cap, out_len, frames, bad_frame, nullptr);
 }
 
-namespace {
-// jpk_jam_decompress / jpk_jam_cli_decompress: the archive staged one pass at a time -- the pass's frames are an archive of their own
-// for the device call
-int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame, bool cli)
+
+// ---- archives of plain and staged frames ("Staged frames") ---------------------------------------------------------------
+// Per pass: the staged frames first, through jam_cli_pass with the staged stage list -- every one ends verified in its slot A, and its
+// raw size is known; then the capacity answer for the pass; then the plain frames in front of the first bad staged one decode in their
+// places in d_out, which are known now, and meet their crcs; then one gather launch moves the staged frames to theirs.
+extern "C" int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                             int32_t *frames, int32_t *bad_frame)
 {
+    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    JPK_HIP(hipSetDevice(ctx->device));
+    const JamResult res{out_len, frames, bad_frame};
+    jam_result_zero(res);
+    if (in_len == 0) return JPK_OK;
+    std::vector<JamFrame> fr;
+    int32_t bad = -1;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, JAM_STAGED));
+    const int64_t raw_bound = jam_sum(fr, 0, fr.size(), false);
+    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
+    int64_t pos = 0;
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, false);
+        const int n = (int)(e - k);
+        // the staged frames of the pass: sidx[q] = its place in the pass
+        std::vector<int> sidx;
+        std::vector<const uint8_t *> sin;
+        std::vector<uint8_t *> a, b;
+        std::vector<int32_t> slens, caps, bsz;
+        std::vector<uint32_t> scrc;
+        std::vector<size_t> slot;
+        size_t need = o_slots;
+        for (int i = 0; i < n; i++) {
+            const JamFrame &f = fr[k + i];
+            if (!f.staged) continue;
+            sidx.push_back(i);
+            sin.push_back(d_in + f.payload_off); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
+            caps.push_back(jam_cli_cap(f.block_size));
+            slot.push_back(jpk_align((size_t)caps.back() + 64));      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+            need += 2 * slot.back();
+        }
+        const int ns = (int)sidx.size();
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
+        size_t off = o_slots;
+        a.resize((size_t)ns); b.resize((size_t)ns);
+        for (int q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
+        std::vector<int32_t> sraw((size_t)ns), sst((size_t)ns);
+        if (ns)
+            JPK_TRY(jam_cli_pass(ctx, CliPass{ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, true, false, true},
+                                 sraw.data(), sst.data()));
+        // m = the frames in front of the first one that has failed so far, rc = its status; raw[i] of the frames in front of it
+        std::vector<int64_t> raw((size_t)n);
+        int m = n, rc = JPK_OK;
+        for (int i = 0; i < n; i++) raw[i] = fr[k + i].raw;
+        for (int q = 0; q < ns; q++) {
+            if (sst[q] != JPK_OK) { m = sidx[q]; rc = sst[q]; break; }
+            raw[sidx[q]] = sraw[q];
+        }
+        int64_t sum = 0;
+        for (int i = 0; i < m; i++) sum += raw[i];
+        if (sum > out_cap - pos) {
+            *res.out_len = raw_bound;
+            if (res.frames) *res.frames = (int32_t)k;
+            return JPK_E_CAPACITY;
+        }
+        // the plain frames in front of frame m, in place
+        std::vector<int> pidx;
+        std::vector<const uint8_t *> pin;
+        std::vector<uint8_t *> pout;
+        std::vector<int32_t> plens, pcaps;
+        {
+            int64_t o = pos;
+            for (int i = 0; i < m; i++) {
+                const JamFrame &f = fr[k + i];
+                if (!f.staged) { pidx.push_back(i); pin.push_back(d_in + f.payload_off); plens.push_back(f.psize); pout.push_back(d_out + o); pcaps.push_back((int32_t)f.raw); }
+                o += raw[i];
+            }
+        }
+        if (!pidx.empty()) {
+            const int np = (int)pidx.size();
+            std::vector<int32_t> outl((size_t)np), st((size_t)np);
+            std::vector<uint32_t> crc((size_t)np);
+            JPK_TRY(jpk_dev_blocks_decompress(ctx, np, pin.data(), plens.data(), pout.data(), pcaps.data(), outl.data(), st.data()));
+            int fail = np;
+            for (int q = 0; q < np && fail == np; q++) if (st[q] != JPK_OK || outl[q] != pcaps[q]) { fail = q; rc = st[q] != JPK_OK ? st[q] : JPK_E_CORRUPT; }
+            if (fail > 0) {
+                JPK_TRY(jam_crcs(ctx, fail, pout.data(), pcaps.data(), d_crc, crc.data()));
+                for (int q = 0; q < fail; q++) if (crc[q] != fr[k + pidx[q]].crc) { fail = q; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
+            }
+            if (fail < np) m = pidx[fail];
+        }
+        // the staged frames in front of frame m, from their slots to their places
+        std::vector<JamGatherPiece> pieces;
+        uint64_t words = 0, gbytes = 0;
+        sum = 0;
+        for (int i = 0, q = 0; i < m; i++) {
+            if (fr[k + i].staged) {
+                if (raw[i]) { jam_piece_add(pieces, &words, a[q], d_out + pos + sum, (uint64_t)raw[i], a[q], a[q] + slot[q]); gbytes += (uint64_t)raw[i]; }
+                q++;
+            }
+            sum += raw[i];
+        }
+        JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, gbytes));
+        if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
+        pos += sum;
+        if (m < n) return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        k = e;
+    }
+    return jam_result_done(res, pos, fr.size(), bad);
+}
+
+namespace {
+// jpk_jam_decompress / jpk_jam_cli_decompress / jpk_jam_staged_decompress: the archive staged one pass at a time -- the pass's frames are an archive of their own
+// for the device call
+int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame, int kind)
+{
+    // (an archive that may hold staged frames is sized and reported like one of the stock CLI: a frame's raw size is known behind its last stage)
+    const bool cli = kind != JAM_PLAIN;
     if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
     const JamResult res{out_len, frames, bad_frame};
     jam_result_zero(res);
@@ -617,24 +775,25 @@ int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t
     JPK_TRY(jpk_host_enter(&ctx, 0));
     std::vector<JamFrame> fr;
     int32_t bad = -1;
-    jam_walk_host(in, in_len, fr, &bad, cli);
+    jam_walk_host(in, in_len, fr, &bad, kind);
     // plain: the raw bytes, known from the walk -- the capacity answer comes first and nothing is touched; cli: the raw bound
-    const int64_t total = jam_sum(fr, 0, fr.size(), cli);
+    const int64_t total = jam_sum(fr, 0, fr.size(), kind == JAM_CLI);
     if (!cli && total > out_cap) { *out_len = total; return JPK_E_CAPACITY; }
     int64_t pos = 0;
     for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k, cli);
+        const size_t e = jam_pass_end(fr, k, kind == JAM_CLI);
         const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
         // the pass decodes into its raw bytes; cli: into what is left of out_cap, at most the pass's BlockSize bytes
-        int64_t room = jam_sum(fr, k, e, cli);
+        int64_t room = jam_sum(fr, k, e, kind == JAM_CLI);
         if (cli) room = std::min(room, out_cap - pos);
         JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
         JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
         JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
         int64_t n = 0;
         int32_t nf = 0, bf = -1;
-        const int rc = cli ? jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
-                           : jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
+        const int rc = kind == JAM_STAGED ? jpk_dev_jam_staged_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
+                       : cli            ? jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
+                                        : jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
         if (cli && rc == JPK_E_CAPACITY) {
             JPK_HIP(hipStreamSynchronize(ctx->stream));
             *out_len = total;
@@ -659,12 +818,17 @@ int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t
 
 extern "C" int jpk_jam_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
 {
-    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, false);
+    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, JAM_PLAIN);
 }
 
 extern "C" int jpk_jam_cli_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
 {
-    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, true);
+    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, JAM_CLI);
+}
+
+extern "C" int jpk_jam_staged_decompress(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame)
+{
+    return jam_decompress_host(in, in_len, out, out_cap, out_len, frames, bad_frame, JAM_STAGED);
 }
 
 // ---- range reads of a .jam archive: jpk_jam_index + jpk_dev_jam_read / jpk_jam_read -----------------------------------------------
@@ -906,7 +1070,7 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
     if (in_len > 0) {
         jpk_ctx *ctx;
         JPK_TRY(jpk_host_enter(&ctx, 0));
-        jam_walk_host(in, in_len, fr, &bad, true);
+        jam_walk_host(in, in_len, fr, &bad, JAM_CLI);
         // staged one pass at a time, as jam_decompress_host: the pass's frames are an archive of their own for the device decode
         for (size_t k = 0; k < fr.size();) {
             const size_t e = jam_pass_end(fr, k, true);

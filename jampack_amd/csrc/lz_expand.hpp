@@ -1,0 +1,81 @@
+// lz_expand.hpp -- the rule of the parallel LZ77 expander (jpk_dev_blocks_lz77_expand; DESIGN 4.6, "Staged frames"), shared by its host
+// form (the stand-alone rule test) and the k_lzx_* kernels (prestage_dev.hip): the plan, which turns the token stream into one segment
+// record per literal run and per match with the checks of Lz77::Decompress in their order, and the chase, which finds the input byte
+// behind any output position from the records alone.  Pure functions of the stream, so the result depends on no launch order.
+#pragma once
+#include <stdint.h>
+
+#include "prestage_rules.hpp"
+
+namespace lzx {
+
+constexpr uint32_t MAX_CHASE = 8;           // match hops from an output byte to its literal; a block that needs more is decoded serially
+
+// `len` output bytes from `out`: input bytes from src (match == 0), or the bytes `src` in front of them, repeated with period src (match == 1)
+struct Seg { uint32_t out, len, src, match; };
+
+// records a block may use: the dedupe writes at most n / 256 + 2 tokens of two records each
+JPK_HD uint32_t seg_cap(int64_t in_len) { return (uint32_t)(in_len / 64 + 4); }
+
+// the walk over the tokens: pos / op as in jpk_lz77_decompress; serial = the block fails a check or needs more than `cap` records and
+// goes to the serial decoder, which gives it its status
+struct Plan { int64_t pos = 0, op = 0; uint32_t nseg = 0; bool done = false, serial = false; };
+
+JPK_HD bool more(const Plan &p, int64_t in_len) { return !p.done && p.pos < in_len; }
+
+// One token: t was parsed at p.pos (parsed == false: pre::parse_token refused it).  put(i, seg) stores record i.  No record is empty, the
+// records are in output order and the first one starts at 0.
+template <class Put> JPK_HD void step(Plan &p, bool parsed, const pre::Token &t, int64_t in_len, int64_t out_cap, uint32_t cap, Put put)
+{
+    auto fail = [&p]() { p.serial = true; p.done = true; };
+    auto add = [&](int64_t len, int64_t src, uint32_t match) {
+        if (len == 0) return true;
+        if (p.nseg >= cap) { fail(); return false; }
+        Seg s;
+        s.out = (uint32_t)p.op; s.len = (uint32_t)len; s.src = (uint32_t)src; s.match = match;     // all below 2^31: checked against in_len / out_cap
+        put(p.nseg++, s);
+        p.op += len;
+        return true;
+    };
+    if (!parsed) return fail();
+    p.pos += t.used;
+    if (t.off == 0) {                                                  // end marker: raw remainder
+        const int64_t rest = in_len - p.pos;
+        if (p.op + rest > out_cap) return fail();
+        add(rest, p.pos, 0u);
+        p.done = true;
+        return;
+    }
+    if (t.off < 0 || t.lit > in_len - p.pos) return fail();
+    if (t.lit + t.len > out_cap - p.op) return fail();
+    if (!add(t.lit, p.pos, 0u)) return;
+    p.pos += t.lit;
+    if ((int64_t)t.off > p.op) return fail();
+    add(t.len, t.off, 1u);
+}
+
+// the record of output position pos among s[0..n): the last one with out <= pos (n >= 1)
+JPK_HD uint32_t find(const Seg *s, uint32_t n, uint32_t pos)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (s[mid].out <= pos) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// where a position of match sg reads: in front of the match in one step, however long an overlapping match is
+JPK_HD uint32_t back(const Seg &sg, uint32_t pos) { return sg.out - sg.src + (pos - sg.out) % sg.src; }
+
+// The input byte behind output position pos, which lies in record idx = sg: *in_off.  Every hop lands in an earlier record (a match is
+// never record 0: its offset would exceed the output so far), so the chase ends; false: it needs more than MAX_CHASE hops.
+JPK_HD bool source(const Seg *s, uint32_t idx, Seg sg, uint32_t pos, uint32_t *in_off)
+{
+    for (uint32_t k = 0;; k++) {
+        if (!sg.match) { *in_off = sg.src + (pos - sg.out); return true; }
+        if (k == MAX_CHASE) return false;
+        pos = back(sg, pos);
+        idx = find(s, idx, pos);
+        sg = s[idx];
+    }
+}
+
+}  // namespace lzx

@@ -203,34 +203,45 @@ extern "C" int64_t jpk_cli_stages_bound(int64_t n)
     return pre::s4_of_s1(n + 2);
 }
 
-// S4 of S1 = head | body (DESIGN 4.7): the filter pieces, Lpx::Encode, the second end token
-static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len,
-                           bool filters)
+// S2 of S1 = head | body into buf[0..s2): the filter pieces, stored or chosen
+static int cli_s2_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *buf, int64_t s2, bool filters)
 {
     constexpr int64_t FBS = pre::FBS;
-    const int64_t s1 = nhead + nbody, total = pre::s4_of_s1(s1), s2 = total - 2;
-    if (total > 0x7fffffff) return JPK_E_ARG;
-    if (total > out_cap) return JPK_E_CAPACITY;
-    std::vector<uint8_t> buf, piece;
-    try { buf.resize((size_t)s2); if (filters) piece.resize((size_t)FBS); } catch (...) { return JPK_E_ALLOC; }
+    const int64_t s1 = nhead + nbody;
+    std::vector<uint8_t> piece;
+    try { if (filters) piece.resize((size_t)FBS); } catch (...) { return JPK_E_ALLOC; }
     int64_t op = 0;
     for (int64_t i = 0; i < s1;) {                                     // byte i of S1: head[i], then body[i - nhead]
         const int64_t len = (i + FBS < s1) ? FBS : s1 - i;
         if (op + 2 + len > s2) return JPK_E_CAPACITY;                  // cannot happen: s2 counts exactly these bytes
-        buf[(size_t)op] = 0; buf[(size_t)op + 1] = 0;
+        buf[op] = 0; buf[op + 1] = 0;
         op += 2;
         int64_t k = 0;
-        for (; i + k < nhead && k < len; k++) buf[(size_t)(op + k)] = head[i + k];
-        if (len > k) memcpy(buf.data() + op + k, body + (i + k - nhead), (size_t)(len - k));
+        for (; i + k < nhead && k < len; k++) buf[op + k] = head[i + k];
+        if (len > k) memcpy(buf + op + k, body + (i + k - nhead), (size_t)(len - k));
         if (filters) {
-            memcpy(piece.data(), buf.data() + op, (size_t)len);
-            filters_encode_piece(piece.data(), (uint32_t)len, buf.data() + op - 2);
+            memcpy(piece.data(), buf + op, (size_t)len);
+            filters_encode_piece(piece.data(), (uint32_t)len, buf + op - 2);
         }
         op += len;
         i += len;
     }
+    return JPK_OK;
+}
+
+// S4 of S1 = head | body (DESIGN 4.7): the filter pieces, Lpx::Encode, the second end token
+static int cli_stages_from(const uint8_t *head, int64_t nhead, const uint8_t *body, int64_t nbody, uint8_t *out, int32_t out_cap, int32_t *out_len,
+                           bool filters)
+{
+    const int64_t s1 = nhead + nbody, total = pre::s4_of_s1(s1), s2 = total - 2;
+    if (total > 0x7fffffff) return JPK_E_ARG;
+    if (total > out_cap) return JPK_E_CAPACITY;
+    std::vector<uint8_t> buf;
+    try { buf.resize((size_t)s2); } catch (...) { return JPK_E_ALLOC; }
+    int rc = cli_s2_from(head, nhead, body, nbody, buf.data(), s2, filters);
+    if (rc != JPK_OK) return rc;
     out[0] = pre::END_TOKEN[0]; out[1] = pre::END_TOKEN[1];
-    const int rc = jpk_lpx_encode(buf.data(), (int32_t)s2, out + 2);
+    rc = jpk_lpx_encode(buf.data(), (int32_t)s2, out + 2);
     if (rc != JPK_OK) return rc;
     *out_len = (int32_t)total;
     return JPK_OK;
@@ -299,6 +310,29 @@ extern "C" int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *o
     const int rc = jpk_lz77_dedupe(in, n, s1.data(), n + 2, &m);       // |S1'| <= n + 2: every token pays for itself
     if (rc != JPK_OK) return rc;
     return cli_stages_from(nullptr, 0, s1.data(), m, out, out_cap, out_len, filters);
+}
+
+// The same chain stopped at S2, which is what a staged frame hands to the BWT ("Staged frames"); |S2| = jpk_cli_stages_bound - 2
+// at most.  Declared in common.hpp for abi.hip.
+int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
+int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
+{
+    if (!out_len || n < 0 || out_cap < 0 || (n > 0 && !in) || (out_cap > 0 && !out) || !JPK_CLI_FLAGS_OK(flags)) return JPK_E_ARG;
+    if (jpk_cli_stages_bound(n) > 0x7fffffff) return JPK_E_ARG;
+    const bool filters = (flags & JPK_CLI_FILTERS) != 0;
+    std::vector<uint8_t> s1;
+    int32_t m = 0;
+    if (flags & JPK_CLI_DEDUPE) {
+        try { s1.resize((size_t)n + 2); } catch (...) { return JPK_E_ALLOC; }
+        const int rc = jpk_lz77_dedupe(in, n, s1.data(), n + 2, &m);
+        if (rc != JPK_OK) return rc;
+    }
+    const int64_t s2 = pre::s4_of_s1((flags & JPK_CLI_DEDUPE) ? m : (int64_t)n + 2) - 2;
+    if (s2 > out_cap) return JPK_E_CAPACITY;
+    const int rc = (flags & JPK_CLI_DEDUPE) ? cli_s2_from(nullptr, 0, s1.data(), m, out, s2, filters) : cli_s2_from(pre::END_TOKEN, 2, in, n, out, s2, filters);
+    if (rc != JPK_OK) return rc;
+    *out_len = (int32_t)s2;
+    return JPK_OK;
 }
 
 extern "C" int jpk_cli_stages_encode(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len)

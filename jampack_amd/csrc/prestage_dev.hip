@@ -1,6 +1,8 @@
 // prestage_dev.hip -- the decoders of the three stages the stock CLI runs in front of the BWT (Jampack::Decomp, jampack.cpp:47-60), on gfx950,
 // for batches of blocks that already sit in HBM behind the batched rANS decode + inverse BWT:
 //   k_pre_lz77     Lz77::Decompress (lz77.cpp:678-714)   one workgroup per block: every lane parses the token, all lanes copy
+//   k_lzx_plan     the same stage as two launches (jpk_dev_blocks_lz77_expand; the rule is lz_expand.hpp): one wave per block turns the
+//   k_lzx_copy     tokens into segment records, then every thread fills aligned 16-byte words of the output from the records
 //   k_lpx<false>   Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
 //                  (k_pre_lpx in the profiler's table and in DESIGN 4.7)
 //   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
@@ -28,6 +30,7 @@
 
 #include "common.hpp"
 #include "dedupe.hpp"
+#include "lz_expand.hpp"
 #include "prestage_rules.hpp"
 
 namespace {
@@ -108,6 +111,116 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_lz77(const PreJob *__restrict__ 
         op += len;
     }
     if (tid == 0) { res[0] = (uint32_t)status; res[1] = status == JPK_OK ? (uint32_t)op : 0u; }
+}
+
+// ---- the parallel LZ77 expander ------------------------------------------------------------------------------------------------
+// Two launches for a batch ("Staged frames"); what decides a byte or a status is lz_expand.hpp.  A block that fails a check
+// of the plan, needs more records than it has, or holds a byte more than lzx::MAX_CHASE matches away from its literal is left to
+// k_pre_lz77, which gives it its bytes and its status: nothing here loops on a hostile stream, and no workgroup waits for another.
+struct LzxJob { const uint8_t *in; uint8_t *out; lzx::Seg *segs; int32_t in_len; int32_t out_cap; uint32_t cap; uint32_t pad; };
+constexpr uint32_t LZX_WORDS = 4;                                     // 16-byte words per thread, as k_enc_wrap
+constexpr uint32_t LZX_INFO = 4;                                      // info words per block: serial (plan), out_len, records, serial (copy)
+
+// One wave per block: the token walk of k_pre_lz77 without its copies; lane 0 stores the records.
+__global__ __launch_bounds__(64) void k_lzx_plan(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+{
+    const LzxJob jb = jobs[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    const int64_t in_len = jb.in_len;
+    lzx::Seg *segs = jb.segs;
+    lzx::Plan p;
+    while (lzx::more(p, in_len)) {
+        const int64_t wi = p.pos + (int64_t)(tid & 15u);
+        const uint32_t w = wi < in_len ? jb.in[wi] : 0u;
+        pre::Token t;
+        const bool parsed = pre::parse_token([w](int j) { return win_byte(w, j); }, in_len - p.pos, &t);
+        lzx::step(p, parsed, t, in_len, (int64_t)jb.out_cap, jb.cap, [segs, tid](uint32_t i, const lzx::Seg &sg) { if (tid == 0) segs[i] = sg; });
+    }
+    if (tid == 0) {
+        uint32_t *r = info + LZX_INFO * (size_t)blockIdx.x;
+        r[0] = p.serial ? 1u : 0u;
+        r[1] = p.serial ? 0u : (uint32_t)p.op;
+        r[2] = p.nseg;
+    }
+}
+
+// Organised by destination as k_dd_emit: grid (workgroups of the largest out_cap, blocks), a workgroup owns LZX_WORDS * PRE_TB aligned
+// 16-byte words of its block's output.  A word that lies inside one record follows the matches as a whole -- lzx::back of its first byte,
+// while its 16 bytes stay inside one record and inside one period -- down to a literal run, which it reads through two aligned loads when
+// both lie inside the input; every other word resolves its bytes one by one (lzx::source).  Whole words are stored once, the partial words
+// at the two ends with byte stores: nothing outside [out, out + out_len) is written, and every read is of an input byte a record covers.
+__global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+{
+    const LzxJob jb = jobs[blockIdx.y];
+    uint32_t *inf = info + LZX_INFO * (size_t)blockIdx.y;
+    const uint32_t total = inf[1], nseg = inf[2];
+    if (inf[0] || total == 0u) return;
+    const lzx::Seg *__restrict__ segs = jb.segs;
+    const uintptr_t base = (uintptr_t)jb.out & ~(uintptr_t)15, r_lo = (uintptr_t)jb.in, r_hi = r_lo + (uint32_t)jb.in_len;
+    const uint32_t lead = (uint32_t)((uintptr_t)jb.out - base);
+    const uint64_t words = ((uint64_t)lead + total + 15u) / 16u;
+    const uint64_t w0 = (uint64_t)blockIdx.x * (LZX_WORDS * PRE_TB) + threadIdx.x;
+#pragma unroll 1
+    for (uint32_t t = 0; t < LZX_WORDS; t++) {
+        const uint64_t w = w0 + (uint64_t)t * PRE_TB;
+        if (w >= words) break;
+        const int64_t p0 = (int64_t)(w * 16u) - (int64_t)lead;
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
+        const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
+        const uint32_t first = p0 < 0 ? 0u : (uint32_t)p0;
+        uint32_t idx = lzx::find(segs, nseg, first);
+        lzx::Seg sg = segs[idx];
+        if (whole) {
+            uint32_t p = first, i = idx;
+            lzx::Seg s = sg;
+            bool word = true, deep = false;
+            for (uint32_t k = 0;; k++) {
+                if ((uint64_t)p + 16u > (uint64_t)s.out + s.len) { word = false; break; }       // the word crosses into the next record
+                if (!s.match) break;
+                if (k == lzx::MAX_CHASE) { deep = true; break; }
+                const uint32_t r = (p - s.out) % s.src;
+                if ((uint64_t)r + 16u > s.src) { word = false; break; }                         // the word crosses the period's end
+                p = s.out - s.src + r;
+                i = lzx::find(segs, i, p);
+                s = segs[i];
+            }
+            if (deep) { inf[3] = 1u; continue; }
+            if (word) {
+                const uint8_t *src = jb.in + s.src + (p - s.out);
+                const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
+                uint4 v;
+                if (a >= r_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= r_hi) {
+                    v = load16_unaligned(src);
+                } else {
+                    uint32_t b[16];
+#pragma unroll
+                    for (int j = 0; j < 16; j++) b[j] = src[j];
+                    v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+                    v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+                    v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+                    v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+                }
+                *reinterpret_cast<uint4 *>(dst) = v;
+                continue;
+            }
+        }
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+        bool deep = false;
+#pragma unroll 1
+        for (uint32_t j = 0; j < 16u; j++) {
+            const int64_t p = p0 + (int64_t)j;
+            if (p < 0 || (uint64_t)p >= total) continue;
+            while (idx + 1 < nseg && (uint64_t)p >= (uint64_t)sg.out + sg.len) sg = segs[++idx];
+            uint32_t io = 0;
+            if (!lzx::source(segs, idx, sg, (uint32_t)p, &io)) { deep = true; break; }
+            const uint32_t byte = jb.in[io];
+            if (!whole) dst[j] = (uint8_t)byte;
+            const uint32_t sh = byte << (8u * (j & 3u)), q = j >> 2;
+            v[0] |= q == 0u ? sh : 0u; v[1] |= q == 1u ? sh : 0u; v[2] |= q == 2u ? sh : 0u; v[3] |= q == 3u ? sh : 0u;
+        }
+        if (deep) { inf[3] = 1u; continue; }
+        if (whole) *reinterpret_cast<uint4 *>(dst) = make_uint4(v[0], v[1], v[2], v[3]);
+    }
 }
 
 // ---- LPX -----------------------------------------------------------------------------------------------------------------------
@@ -717,13 +830,11 @@ int dd_emit(jpk_ctx *ctx, int n, DdCall *dc, uint8_t *const *outs, const int32_t
 
 }  // namespace
 
-extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
-                                              const int32_t *out_cap, int32_t *out_len, int32_t *status)
+namespace {
+// k_pre_lz77 on n blocks, one launch: stp[b] and out_len[b] as jpk_lz77_decompress gives them
+int lz77_serial(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out, const int32_t *out_cap, int32_t *out_len,
+                int32_t *stp)
 {
-    JPK_TRY(pre_enter(ctx));
-    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
-    if (n == 0) return JPK_OK;
-    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
     std::vector<PreJob> jobs((size_t)n);
     uint64_t bytes = 0;
     for (int b = 0; b < n; b++) {
@@ -735,13 +846,96 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
     JPK_LAUNCH(ctx, PROF_PRE_LZ77, bytes, k_pre_lz77, dim3((unsigned)n), dim3(PRE_TB), pc.d_jobs, pc.d_mail);
     std::vector<uint32_t> mail(2 * (size_t)n);
     JPK_TRY(pre_finish(ctx, pc.d_mail, mail));
-    std::vector<int32_t> st_local((size_t)n);
-    int32_t *stp = status ? status : st_local.data();
     for (int b = 0; b < n; b++) {
         stp[b] = (int32_t)mail[2 * (size_t)b];
         out_len[b] = stp[b] == JPK_OK ? (int32_t)mail[2 * (size_t)b + 1] : 0;
     }
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                              const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    if (n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (n == 0) return JPK_OK;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    JPK_TRY(lz77_serial(ctx, n, d_in, in_len, d_out, out_cap, out_len, stp));
     return finish_statuses(n, status, stp);
+}
+
+// The same stage through k_lzx_plan + k_lzx_copy, and k_pre_lz77 for the blocks they leave to it: one host read of the plan's lengths and
+// both kernels' flags, a second one only when a block went the serial way.  The records (lzx::seg_cap per block) live in ctx's arena.
+extern "C" int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                          const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    JPK_TRY(pre_enter(ctx));
+    ctx->lzx_parallel = 0; ctx->lzx_serial = 0;
+    if (n == 0) return JPK_OK;
+    std::vector<LzxJob> jobs((size_t)n);
+    size_t seg_recs = 0;
+    uint64_t bytes = 0, max_words = 0;
+    for (int b = 0; b < n; b++) {
+        const uint32_t cap = lzx::seg_cap(in_len[b]);
+        jobs[(size_t)b] = LzxJob{d_in[b], d_out[b], nullptr, in_len[b], out_cap[b], cap, 0u};
+        seg_recs += cap;
+        bytes += (uint32_t)in_len[b];
+        max_words = std::max<uint64_t>(max_words, (((uintptr_t)d_out[b] & 15u) + (uint64_t)out_cap[b] + 15u) / 16u);
+    }
+    Arena plan(ctx, true);
+    plan.get<LzxJob>((size_t)n);
+    plan.get<uint32_t>(LZX_INFO * (size_t)n);
+    plan.get<lzx::Seg>(seg_recs);
+    JPK_TRY(jpk_arena_ensure(ctx, plan.need));
+    Arena real(ctx, false);
+    LzxJob *d_jobs = real.get<LzxJob>((size_t)n);
+    uint32_t *d_info = real.get<uint32_t>(LZX_INFO * (size_t)n);
+    lzx::Seg *segs = real.get<lzx::Seg>(seg_recs);
+    size_t so = 0;
+    for (int b = 0; b < n; b++) { jobs[(size_t)b].segs = segs + so; so += jobs[(size_t)b].cap; }
+    JPK_HIP(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(LzxJob), hipMemcpyHostToDevice, ctx->stream));
+    JPK_HIP(hipMemsetAsync(d_info, 0, LZX_INFO * (size_t)n * 4, ctx->stream));
+    JPK_LAUNCH(ctx, PROF_LZX_PLAN, bytes, k_lzx_plan, dim3((unsigned)n), dim3(64), d_jobs, d_info);
+    if (max_words)
+        for (int b0 = 0; b0 < n; b0 += DD_GRID_Y)
+            JPK_LAUNCH(ctx, PROF_LZX_COPY, bytes, k_lzx_copy, dim3(jpk_grid(max_words, LZX_WORDS * PRE_TB), (unsigned)std::min(DD_GRID_Y, n - b0)), dim3(PRE_TB),
+                       d_jobs + b0, d_info + LZX_INFO * (size_t)b0);
+    std::vector<uint32_t> info(LZX_INFO * (size_t)n);
+    JPK_TRY(pre_finish(ctx, d_info, info));
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    std::vector<int> ser;
+    for (int b = 0; b < n; b++) {
+        const uint32_t *r = &info[LZX_INFO * (size_t)b];
+        if (r[0] || r[3]) { ser.push_back(b); continue; }
+        stp[b] = JPK_OK;
+        out_len[b] = (int32_t)r[1];
+    }
+    if (!ser.empty()) {
+        const size_t m = ser.size();
+        std::vector<const uint8_t *> sin(m);
+        std::vector<uint8_t *> sout(m);
+        std::vector<int32_t> slen(m), scap(m), sgot(m), sst(m);
+        for (size_t q = 0; q < m; q++) { sin[q] = d_in[ser[q]]; sout[q] = d_out[ser[q]]; slen[q] = in_len[ser[q]]; scap[q] = out_cap[ser[q]]; }
+        JPK_TRY(lz77_serial(ctx, (int32_t)m, sin.data(), slen.data(), sout.data(), scap.data(), sgot.data(), sst.data()));
+        for (size_t q = 0; q < m; q++) { stp[ser[q]] = sst[q]; out_len[ser[q]] = sgot[q]; }
+    }
+    ctx->lzx_serial = (int32_t)ser.size();
+    ctx->lzx_parallel = n - ctx->lzx_serial;
+    return finish_statuses(n, status, stp);
+}
+
+extern "C" int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial)
+{
+    if (!ctx || !parallel || !serial) return JPK_E_ARG;
+    *parallel = ctx->lzx_parallel;
+    *serial = ctx->lzx_serial;
+    return JPK_OK;
 }
 
 extern "C" int jpk_dev_blocks_lz77_dedupe(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
@@ -813,8 +1007,10 @@ namespace {
 using pre::s4_of_s1;
 
 // found != nullptr: dd_find has run for these blocks (its scratch is still in the arena) and found_s1[] holds its lengths
+// lpx == false: the chain ends at S2 in d_mid[b] (staged frames), d_out[b] is the dedupe's room alone -- without the dedupe it is not
+// read and may be null -- and s4_len[b] = |S2|
 int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_out, uint32_t flags,
-                   int32_t *s4_len, DdCall *found, const int32_t *found_s1)
+                   int32_t *s4_len, DdCall *found, const int32_t *found_s1, bool lpx = true)
 {
     const bool dedupe = (flags & JPK_CLI_DEDUPE) != 0, filters = (flags & JPK_CLI_FILTERS) != 0;
     std::vector<int32_t> s1((size_t)n);
@@ -843,7 +1039,7 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
     uint8_t *mids = real.get<uint8_t>(mid_bytes);
     uint64_t wwg = 0, lwg = 0, bytes = 0;
     for (int b = 0; b < n; b++) {
-        if (s4_len) s4_len[b] = in_len[b] < 0 ? 0 : (int32_t)s4_of_s1(s1[(size_t)b]);
+        if (s4_len) s4_len[b] = in_len[b] < 0 ? 0 : (int32_t)s4_of_s1(s1[(size_t)b]) - (lpx ? 0 : 2);
         if (in_len[b] < 0) {
             wj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)wwg, 0u};
             lj[(size_t)b] = PreJob{nullptr, nullptr, 0, 0, (uint32_t)lwg, 0u};
@@ -852,7 +1048,7 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
         const int32_t s2 = (int32_t)(s4_of_s1(s1[(size_t)b]) - 2);
         uint8_t *mid = d_mid ? d_mid[b] : mids + moff[(size_t)b];
         wj[(size_t)b] = dedupe ? PreJob{d_out[b], mid, s1[(size_t)b], s2, (uint32_t)wwg, 0u} : PreJob{d_in[b], mid, in_len[b], s2, (uint32_t)wwg, 0u};
-        lj[(size_t)b] = PreJob{mid, d_out[b] + 2, s2, s2, (uint32_t)lwg, 0u};
+        lj[(size_t)b] = PreJob{mid, lpx ? d_out[b] + 2 : nullptr, s2, s2, (uint32_t)lwg, 0u};
         const uint64_t words = (((uintptr_t)mid & 15u) + (uint64_t)s2 + 15u) / 16u;
         wwg += filters ? filter_pieces(s1[(size_t)b]) : (words + WRAP_WORDS * PRE_TB - 1) / (WRAP_WORDS * PRE_TB);
         lwg += pre::parts((uint32_t)s2);
@@ -866,7 +1062,7 @@ int cli_stages_run(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_
         else if (filters) JPK_LAUNCH(ctx, PROF_ENC_FILTERS, bytes, k_enc_filters<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         else if (dedupe) JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<false>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
         else JPK_LAUNCH(ctx, PROF_ENC_WRAP, bytes, k_enc_wrap<true>, dim3((unsigned)wwg), dim3(PRE_TB), d_jobs, (uint32_t)n);
-        JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_lpx<true>, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
+        if (lpx) JPK_LAUNCH(ctx, PROF_ENC_LPX, bytes, k_lpx<true>, dim3((unsigned)lwg), dim3(PRE_TB), d_jobs + n, (uint32_t)n, 1u);
     }
     return pre_finish(ctx);
 }
@@ -876,6 +1072,13 @@ int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const
                           uint32_t flags, int32_t *s4_len)
 {
     return cli_stages_run(ctx, n, d_in, in_len, d_mid, d_out, flags, s4_len, nullptr, nullptr);
+}
+
+int jpk_staged_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_tmp,
+                             uint32_t flags, int32_t *s2_len)
+{
+    if (!d_mid) return JPK_E_ARG;
+    return cli_stages_run(ctx, n, d_in, in_len, d_mid, d_tmp, flags, s2_len, nullptr, nullptr, false);
 }
 
 // With the dedupe a block's |S4| is known when its S1' is: dd_find for all blocks, the capacity answer, then the rest for those that fit
