@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "ans_common.hpp"
+#include "chain_pool.hpp"
 #include "common.hpp"
 
 using namespace jpk;
@@ -1778,6 +1779,9 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
     };
     auto chain = [&](const EncDims &g) -> int {
         JPK_LAUNCH(ctx, PROF_ENC_RANS, 0, k_rans_lanes, dim3(g.ncl), dim3(64), b.recs, stride, g, b.rlen, b.x16, b.emask, b.fstate, b.stamp);
+        return JPK_OK;
+    };
+    auto post_chain = [&](const EncDims &g) -> int {
         const uint32_t etpc = emit_tiles_per_chunk(stride);
         JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_emit_count, dim3(etpc, g.ncl), dim3(TB), b.emask, stride, g, b.rlen, b.etsum, etpc);
         JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_emit_prefix, dim3(g.ncl), dim3(64), g, b.rlen, b.etsum, etpc, b.csize);
@@ -1826,6 +1830,7 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
             ctx->stream = gs;
             rc = pre_chain(gd);
             if (rc == JPK_OK) rc = chain(gd);
+            if (rc == JPK_OK) rc = post_chain(gd);
             ctx->stream = st;
             if (rc == JPK_OK && gs != st && hipEventRecord(ctx->ev_done[g], gs) != hipSuccess) rc = JPK_E_DEVICE;
         }
@@ -1838,8 +1843,28 @@ int encode_core(jpk_ctx *ctx, const uint8_t *d_in, EncDims &d, EncBufs &b, int i
             return rc;
         }
     } else {
+        // One group: the chain -- one wave per chunk, milliseconds long -- goes to a high-priority stream of the device's chain pool
+        // (chain_pool.hpp), whose hardware queues are not the ones the wide kernels of the other blocks wait in.  The two streams are
+        // ordered through the HOST, which is blocked in this call anyway: a hipStreamWaitEvent would put a barrier into the waiting
+        // stream's hardware queue and stall the streams that share it, which is what the pool is there to avoid.  No pool
+        // (JPK_CHAIN_STREAMS=0, no stream priorities): everything on the context's stream, as before.
         JPK_TRY(pre_chain(d));
-        JPK_TRY(chain(d));
+        JpkChainLease lease(ctx);      // an early return below synchronises the pool stream and gives it back (~JpkChainLease)
+        if (lease.held()) {
+            JPK_HIP(hipEventRecord(ctx->ev_pre[0], st));
+            JPK_HIP(hipEventSynchronize(ctx->ev_pre[0]));               // the model pass is done: the chain's input is in place
+            ctx->stream = lease.stream;                                 // (the profiler's events follow the launch)
+            const int rc = chain(d);
+            ctx->stream = st;
+            JPK_TRY(rc);
+            JPK_HIP(hipGetLastError());
+            JPK_HIP(hipEventRecord(ctx->ev_done[0], lease.stream));
+            JPK_HIP(hipEventSynchronize(ctx->ev_done[0]));              // the chain is done: the pool stream goes back idle
+            lease.done();
+        } else {
+            JPK_TRY(chain(d));
+        }
+        JPK_TRY(post_chain(d));
     }
     JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_headers, dim3(d.nch), dim3(256), d, b.freq, b.csize, b.rlen, b.hdr, b.hsize);
     JPK_LAUNCH(ctx, PROF_ENC_EMIT, 0, k_out_offsets, dim3(1), dim3(64), d, b.csize, b.rlen, b.hsize, b.outoff, ctx->d_mail->read, b.stamp);

@@ -82,6 +82,8 @@ struct jpk_ctx {
     static constexpr int ENC_GROUPS = 4;
     hipStream_t aux[ENC_GROUPS - 1] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_pre[ENC_GROUPS] = {nullptr, nullptr, nullptr, nullptr}, ev_done[ENC_GROUPS] = {nullptr, nullptr, nullptr, nullptr};
+    // one group: the chain runs on a stream of the device's chain pool (chain_pool.hpp), ordered through the host with ev_pre[0] / ev_done[0]
+    bool chain_on_pool = false;      // a chain of this context is on a pool stream: the arena must stay (jpk_arena_ensure asserts it)
     // jpk_dev_blocks_decompress of many SMALL blocks: more inverse BWTs side by side than the three of a batch of large ones (an inverse
     // BWT of a 1 MiB block is ~30 dependent launches, each a fraction of the chip).  Streams and events made on first use.
     static constexpr int INV_LANES_MAX = 16;
