@@ -63,7 +63,7 @@ typedef struct jpk_stats {
                                    * histograms, blocks above 2^28 bytes, JPK_VARKEYS=0): 7 above 128 byte values */
     int64_t sa_sorted_elems;      /* sum over rounds of active suffixes that went through a sort */
     int64_t inv_splitters;        /* walkers used by the last inverse BWT */
-    int64_t inv_overflow_slots;   /* sub-lists that exceeded one scratch slot */
+    int64_t inv_overflow_slots;   /* overflow slots chained by the last inverse BWT: a sub-list of L bytes adds (L - 1) / 256 */
     int64_t workspace_bytes;      /* HBM arena currently held by the context */
     int64_t ans_chunks;           /* 1 MiB chunks in the last entropy call */
     int64_t ans_rle_symbols;      /* RLE0 symbols in the last entropy call */
