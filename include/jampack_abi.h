@@ -421,8 +421,9 @@ JPK_API int jpk_jam_cli_compress_ex(const uint8_t *in, int64_t in_len, int32_t b
  * header's BlockSize field carries JPK_JAM_STAGED (bit 30; JPK_MAX_BLOCKSIZE is below 2^30): the stock DecompReadBlock (jampack.cpp:150),
  * jpk_jam_frames, jpk_jam_cli_frames and the plain and stock-CLI decoders refuse such a header, so no decoder takes a staged frame for
  * another kind.  The flags (JPK_CLI_DEDUPE, JPK_CLI_FILTERS; accepted values 0, 1, 4, 5, anything else JPK_E_ARG) decide only whether the
- * writer's stages are stored or real: the decoder always runs Filters::Decode, then Lz77::Decompress.  Range reads and an index of staged
- * archives do not exist (a staged frame's raw size is known only behind its last stage). */
+ * writer's stages are stored or real: the decoder always runs Filters::Decode, then Lz77::Decompress.  A staged frame's raw size is in no
+ * header, but it is a function of the tokens of its S1 alone: jpk_(dev_)jam_staged_index_create (below, with the range reads) index an
+ * archive of plain and staged frames without expanding a frame, and jpk_dev_jam_read / jpk_jam_read read byte ranges through that index. */
 #define JPK_JAM_STAGED (1 << 30)
 /* one frame, host buffers (the stages on the host, the BWT and the entropy coder on the GPU): arguments and statuses as
  * jpk_jam_cli_block_write_ex / jpk_jam_cli_block_read; the reader takes staged frames only (any other header is JPK_E_CORRUPT) */
@@ -462,6 +463,17 @@ JPK_API int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *c
                                        const int32_t *out_cap, int32_t *out_len, int32_t *status);
 /* how many blocks of ctx's last jpk_dev_blocks_lz77_expand call took the two parallel launches and how many the serial kernel */
 JPK_API int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial);
+/* The raw size of an Lz77 stream without its bytes: the token walk of Lz77::Decompress (lz77.cpp:678-714) with the checks of
+ * jpk_lz77_decompress in their order and no copy.  Returns the status jpk_lz77_decompress gives the same stream at the same out_cap, for
+ * every stream, valid or not (a token that does not parse, a negative offset, literals beyond the input or an offset beyond the output
+ * so far JPK_E_CORRUPT; more than out_cap bytes JPK_E_CAPACITY), and *out_len = its *out_len on JPK_OK, 0 otherwise.  No device call,
+ * no output buffer; in may be NULL when in_len == 0. */
+JPK_API int jpk_lz77_size(const uint8_t *in, int32_t in_len, int32_t out_cap, int32_t *out_len);
+/* the same for n blocks in HBM, one launch (k_lz77_sizes: one wave per block, one load per token, two result words per block and no
+ * other store) and one read-back: out_len[b] and status[b] are those of jpk_dev_blocks_lz77_decompress on the same inputs and capacities,
+ * the inputs stay as they are.  status may be NULL as there; the arguments are checked before a device is looked for. */
+JPK_API int jpk_dev_blocks_lz77_sizes(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, const int32_t *out_cap, int32_t *out_len,
+                                      int32_t *status);
 
 /* ---- byte ranges of a .jam archive without decoding all of it ------------------------------------------------------------------- */
 /* The frame table of one archive: per frame the payload offset and size, the header crc, BlockSize, the raw (decoded) size and the
@@ -494,13 +506,42 @@ JPK_API void jpk_jam_index_destroy(jpk_jam_index *index);
 #define JPK_JAM_INDEX_CLI 1
 JPK_API int jpk_dev_jam_cli_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
 JPK_API int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame);
-/* JPK_JAM_INDEX_PLAIN for an index of jpk_(dev_)jam_index_create, JPK_JAM_INDEX_CLI for one of the stock-CLI creators; JPK_E_ARG for NULL */
+/* JPK_JAM_INDEX_PLAIN for an index of jpk_(dev_)jam_index_create, JPK_JAM_INDEX_CLI for one of the stock-CLI creators,
+ * JPK_JAM_INDEX_STAGED (below) for one of the staged creators; JPK_E_ARG for NULL */
 JPK_API int jpk_jam_index_kind(const jpk_jam_index *index);
 /* jpk_dev_jam_cli_decompress that also hands back the index of the frames it delivered (the whole archive on JPK_OK, the frames in
  * front of the bad one on JPK_E_CORRUPT): a caller who decodes an archive once has its index for free.  index == NULL is allowed and
  * makes this the plain call; *index is NULL after JPK_E_CAPACITY and every other failure. */
 JPK_API int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
                                           int32_t *bad_frame, jpk_jam_index **index);
+/* The index of an archive of plain and staged frames in any order (the archives jpk_dev_jam_staged_decompress reads), kind
+ * JPK_JAM_INDEX_STAGED.  The frame walk is that call's.  A plain frame keeps the raw size of the walk and is not decoded.  A staged
+ * frame's raw size comes per pass (at most 128 frames and 4 GiB, a staged frame counted at its BlockSize; two slots of 1.05 x BlockSize
+ * + 4096 per staged frame in the scratch buffer of ctx):
+ *   verify == 0  jpk_dev_blocks_decompress -> slot A, k_pre_filters -> slot B, jpk_dev_blocks_lz77_sizes on B with out_cap = BlockSize:
+ *                no expansion, no checksum, no gather.  A frame is bad when its header or payload is bad, a stage refuses its stream, or
+ *                it declares more than BlockSize raw bytes.  THE FRAMES OF SUCH AN INDEX ARE NOT VERIFIED against their crcs -- as those
+ *                of a plain index are not, whose sizes come from unverified headers too.  A read verifies every frame it touches.
+ *   verify == 1  the whole stage list of jpk_dev_jam_staged_decompress into slot A and the batched checksum against the header crcs, as
+ *                jpk_dev_jam_cli_index_create does for its kind: every STAGED frame in the index has been verified.
+ *   any other value is JPK_E_ARG.
+ * A bad frame is handled as by the other creators: JPK_OK, an index over the frames in front of the first bad one, *bad_frame = its
+ * position (-1: none; may be NULL); a stage's JPK_E_CAPACITY counts as JPK_E_CORRUPT.  The arguments are checked before a device is
+ * looked for, and in_len == 0 gives an empty index of this kind without a device.  The host-buffer form walks the archive on the host
+ * and makes NO device call for an archive without a staged frame (such an index can be made on a machine without a GPU); otherwise it
+ * stages the archive one pass at a time through the calling thread's pooled context.  jpk_jam_index_create and the stock-CLI creators
+ * go on refusing staged frames.  jpk_jam_index_info / _frame / _kind / _destroy work on this kind unchanged. */
+#define JPK_JAM_INDEX_STAGED 2
+JPK_API int jpk_dev_jam_staged_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t verify, jpk_jam_index **index, int32_t *bad_frame);
+JPK_API int jpk_jam_staged_index_create(const uint8_t *in, int64_t in_len, int32_t verify, jpk_jam_index **index, int32_t *bad_frame);
+/* frame k of an index: JPK_JAM_INDEX_PLAIN or JPK_JAM_INDEX_STAGED for a frame of a JPK_JAM_INDEX_STAGED index, the index's own kind
+ * for the other two kinds; JPK_E_ARG for NULL or k out of range */
+JPK_API int jpk_jam_index_frame_kind(const jpk_jam_index *index, int32_t k);
+/* jpk_dev_jam_staged_decompress that also hands back the index (kind JPK_JAM_INDEX_STAGED) of the frames it delivered (the whole
+ * archive on JPK_OK, the frames in front of the bad one on JPK_E_CORRUPT): a caller who decodes an archive once has its index for free.
+ * index == NULL is allowed and makes this the plain call; *index is NULL after JPK_E_CAPACITY and every other failure. */
+JPK_API int jpk_dev_jam_staged_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                             int32_t *frames, int32_t *bad_frame, jpk_jam_index **index);
 /* n ranges in raw coordinates, [off[r], off[r] + len[r]) delivered at d_out[r] (a device pointer of any alignment; the buffers must
  * not overlap).  in_len must be the index's archive length and every range must satisfy 0 <= off, 0 <= len, off + len <= raw_len:
  * JPK_E_ARG otherwise, before any device work, nothing written.  len == 0 is legal anywhere in [0, raw_len] and touches no frame.
@@ -523,7 +564,14 @@ JPK_API int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int
  * to the frames that passed it, a stage that runs out of its slot is JPK_E_CORRUPT (never JPK_E_CAPACITY), and the last stage's
  * capacity is the indexed raw size exactly -- a frame that decodes to another size belongs to an archive that is not the indexed one and
  * is JPK_E_CORRUPT.  The crc a frame must meet is the one in its header in the archive being read (four bytes per touched frame are
- * read for it), so a header damaged after indexing fails its frame too. */
+ * read for it), so a header damaged after indexing fails its frame too.
+ * With an index of kind JPK_JAM_INDEX_STAGED the contract is the same again, and a pass of touched frames (a staged one counted at its
+ * BlockSize, a plain one at its raw size) holds two groups.  Its plain frames go through jpk_dev_blocks_decompress exactly as under a
+ * plain index: in place or in a slot of their raw size, against the indexed crc.  Its staged frames go through the stage list of
+ * jpk_dev_jam_staged_decompress as the frames of a stock-CLI index go through theirs: two slots of 1.05 x BlockSize + 4096 per frame,
+ * compacted after every stage, the last stage into the range that holds the frame whole or into slot A at exactly the indexed raw size
+ * (any other size is JPK_E_CORRUPT), against the crc in the header of the archive being read.  One gather launch per pass delivers the
+ * pieces of both groups.  Whether the index was made with verify 0 or 1, every touched frame is verified by the read. */
 JPK_API int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
                              uint8_t *const *d_out, int32_t *status, int32_t *bad_frame);
 /* host-buffer form through the calling thread's pooled context: only the payloads of the touched frames are staged to the device,

@@ -216,10 +216,14 @@ def jam_decompress(stream) -> np.ndarray:
     return out[: n.value]
 
 
+JAM_INDEX_PLAIN, JAM_INDEX_CLI, JAM_INDEX_STAGED = 0, 1, 2    # JPK_JAM_INDEX_*: the kinds of an index (and, for kind 2, of its frames)
+
+
 class JamIndex:
     """jpk_jam_index: the frame table of one archive -- `frames`, `raw_len`, `archive_len`, `bad_frame` (-1: the whole archive is
     indexed; otherwise the index covers the frames in front of that one), `kind` (0: a plain archive, 1: an archive of the stock CLI,
-    indexed by decoding it) and `frame(k)`.  Keeps no reference to the archive."""
+    indexed by decoding it, 2: an archive of plain and staged frames, a staged frame sized by the token walk of its first stage or by a
+    decode), `frame(k)` and `frame_kind(k)`.  Keeps no reference to the archive."""
 
     def __init__(self, handle, bad_frame: int):
         self._h = handle
@@ -233,6 +237,12 @@ class JamIndex:
         ro, raw, po, ps = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
         _chk(lib().jpk_jam_index_frame(self._h, k, C.byref(ro), C.byref(raw), C.byref(po), C.byref(ps)), "jpk_jam_index_frame")
         return ro.value, raw.value, po.value, ps.value
+
+    def frame_kind(self, k: int) -> int:
+        """jpk_jam_index_frame_kind: 0 (plain) or 2 (staged) for frame k of an index of kind 2, the index's kind otherwise"""
+        rc = int(lib().jpk_jam_index_frame_kind(self._h, k))
+        _chk(min(rc, 0), "jpk_jam_index_frame_kind")
+        return rc
 
     def close(self):
         if self._h:
@@ -263,6 +273,25 @@ def jam_cli_index(stream) -> JamIndex:
     return JamIndex(h, bad.value)
 
 
+def jam_staged_index(stream, verify: bool = False) -> JamIndex:
+    """jpk_jam_staged_index_create: the index (kind 2) of an archive of plain and staged frames in host memory.  A staged frame's raw size
+    comes from the token walk of its first stage on the device -- no expansion and no checksum; verify=True decodes and checks every
+    staged frame instead.  An archive without a staged frame is indexed on the host alone.  jam_read takes it like a plain index."""
+    c = _np_u8(stream)
+    h, bad = C.c_void_p(), C.c_int32(-1)
+    _chk(lib().jpk_jam_staged_index_create(_ptr(c), len(c), int(verify), C.byref(h), C.byref(bad)), "jpk_jam_staged_index_create")
+    return JamIndex(h, bad.value)
+
+
+def lz77_size(stream, cap: int) -> int:
+    """jpk_lz77_size: what Lz77().Decompress(stream, cap) would be long, from the tokens alone (host code, no output buffer); raises
+    JampackError with the status Decompress would raise"""
+    t = _np_u8(stream)
+    n = C.c_int32(0)
+    _chk(lib().jpk_lz77_size(_ptr(t), len(t), cap, C.byref(n)), "jpk_lz77_size")
+    return n.value
+
+
 def _ranges(ranges):
     n = len(ranges)
     L = C.c_int64 * max(n, 1)
@@ -272,7 +301,8 @@ def _ranges(ranges):
 def jam_read(stream, ranges, index: JamIndex | None = None):
     """jpk_jam_read: the byte ranges [(raw offset, length), ...] of an archive in host memory -> list of numpy arrays.  Only the frames
     the ranges touch are staged and decoded.  Raises JampackError with the first failing range's status.  Without an index the archive
-    is taken for a plain one; a stock-CLI archive is read through the index of jam_cli_index."""
+    is taken for a plain one; a stock-CLI archive is read through the index of jam_cli_index, an archive with staged frames through
+    the index of jam_staged_index."""
     c = _np_u8(stream)
     ix = index if index is not None else jam_index(c)
     try:
@@ -651,6 +681,15 @@ class Context:
         they leave to it) -> (out_len list, status list); lz77_expand_last() says which way the blocks went"""
         return self._batch(lib().jpk_dev_blocks_lz77_expand, "jpk_dev_blocks_lz77_expand", d_ins, in_lens, d_outs, out_caps)
 
+    def blocks_lz77_sizes(self, d_ins, in_lens, out_caps):
+        """jpk_dev_blocks_lz77_sizes: the out_len and status lists of blocks_lz77_decompress from the tokens alone, one launch, no
+        output buffers -> (out_len list, status list)"""
+        n = len(d_ins)
+        P, I = C.c_void_p * n, C.c_int32 * n
+        ol, st = I(), I()
+        _chk(lib().jpk_dev_blocks_lz77_sizes(self._h, n, P(*[_dptr(x) for x in d_ins]), I(*in_lens), I(*out_caps), ol, st), "jpk_dev_blocks_lz77_sizes")
+        return list(ol), list(st)
+
     def lz77_expand_last(self):
         """jpk_debug_lz77_expand_last -> (blocks of the last blocks_lz77_expand call on the parallel path, on the serial path)"""
         p, q = C.c_int32(0), C.c_int32(0)
@@ -771,8 +810,20 @@ class Context:
         _chk(rc, "jpk_dev_jam_staged_decompress")
         return n.value, nf.value, bf.value
 
+    def jam_staged_decompress_ix(self, d_in, in_len, d_out, out_cap, check: bool = True):
+        """jpk_dev_jam_staged_decompress_ix: jam_staged_decompress that also returns the index (kind 2) of the frames it delivered ->
+        (raw bytes, frames, bad frame, JamIndex); check=False: (raw bytes, frames, bad frame, status, JamIndex or None), no exception
+        (no index on JPK_E_CAPACITY)"""
+        n, nf, bf, h = C.c_int64(0), C.c_int32(0), C.c_int32(-1), C.c_void_p()
+        rc = lib().jpk_dev_jam_staged_decompress_ix(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf), C.byref(h))
+        ix = JamIndex(h, bf.value) if h else None
+        if not check:
+            return n.value, nf.value, bf.value, int(rc), ix
+        _chk(rc, "jpk_dev_jam_staged_decompress_ix")
+        return n.value, nf.value, bf.value, ix
+
     def jam_decompress(self, d_in, in_len, d_out, out_cap, check: bool = True):
-        """jpk_dev_jam_decompress -> (raw bytes, frames, bad frame); check=False: (raw bytes, frames, bad frame, status), no exception
+        """jpk_dev_jam_decompress ->(raw bytes, frames, bad frame); check=False: (raw bytes, frames, bad frame, status), no exception
         (out_len is the bytes needed on JPK_E_CAPACITY, the verified bytes in front of the bad frame on JPK_E_CORRUPT)"""
         n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
         rc = lib().jpk_dev_jam_decompress(self._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), C.byref(nf), C.byref(bf))
@@ -791,6 +842,13 @@ class Context:
         """jpk_dev_jam_cli_index_create: the index of a stock-CLI archive in HBM, made by decoding it once (no output buffer)"""
         h, bad = C.c_void_p(), C.c_int32(-1)
         _chk(lib().jpk_dev_jam_cli_index_create(self._h, _dptr(d_in), in_len, C.byref(h), C.byref(bad)), "jpk_dev_jam_cli_index_create")
+        return JamIndex(h, bad.value)
+
+    def jam_staged_index(self, d_in, in_len, verify: bool = False) -> JamIndex:
+        """jpk_dev_jam_staged_index_create: the index (kind 2) of an archive of plain and staged frames in HBM; a staged frame's raw size
+        from the token walk of its first stage (no expansion, no checksum), or with verify=True from a decode that checks its crc"""
+        h, bad = C.c_void_p(), C.c_int32(-1)
+        _chk(lib().jpk_dev_jam_staged_index_create(self._h, _dptr(d_in), in_len, int(verify), C.byref(h), C.byref(bad)), "jpk_dev_jam_staged_index_create")
         return JamIndex(h, bad.value)
 
     def jam_read(self, index: JamIndex, d_in, in_len, ranges, d_outs, check: bool = True):

@@ -37,7 +37,7 @@ enum JpkProfId {
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
     PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM,
     PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT, PROF_ENC_FILTERS,
-    PROF_LZX_PLAN, PROF_LZX_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
+    PROF_LZX_PLAN, PROF_LZ77_SIZES, PROF_LZX_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 

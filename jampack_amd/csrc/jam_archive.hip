@@ -433,6 +433,7 @@ struct jpk_jam_index {
     int64_t archive_len = 0;
     int32_t bad = -1;
     int32_t kind = JPK_JAM_INDEX_PLAIN;    // JPK_JAM_INDEX_CLI: frames of the stock CLI, fr[k].raw from a decode (jam_cli_decode)
+                                           // JPK_JAM_INDEX_STAGED: plain and staged frames (fr[k].staged), a staged one's raw from its token walk or a decode
 };
 
 namespace {
@@ -475,6 +476,8 @@ namespace {
 //   exact   a frame whose raw size is not dst_cap[i] is JPK_E_CORRUPT (the reader: dst_cap is the indexed raw size)
 //   staged  staged frames: the list without the first Lz77 and the Lpx stage -- stage 0 into A, Filters A -> B, and
 //           Lz77 B -> dst with the serial kernel (the parallel expander missed its condition: DESIGN 4.6, "Tried")
+//   sizes   the last stage is k_lz77_sizes: raw[i] is what that Lz77::Decompress would give within dst_cap[i], nothing is expanded and
+//           nothing is checked against a crc (dst, crc and d_crc are not looked at) -- the index of staged frames that does not verify
 struct CliPass {
     int n;
     const uint8_t *const *ins; const int32_t *lens;
@@ -482,7 +485,7 @@ struct CliPass {
     uint8_t *const *dst; const int32_t *dst_cap;
     const uint32_t *crc; uint32_t *d_crc;
     bool prefix, exact;
-    bool staged = false;
+    bool staged = false, sizes = false;
 };
 
 // st[i] = JPK_OK and raw[i] = the raw size of a frame that went through every stage and matches its crc -- it is at dst[i] --, else the
@@ -533,11 +536,12 @@ int jam_cli_pass(jpk_ctx *ctx, const CliPass &p, int32_t *raw, int32_t *st)
     }
     if ((m = aim(p.b, p.dst, p.dst_cap))) {
         // Lz->Decompress; a frame that decodes to more than dst_cap (its BlockSize, or its indexed raw size) is a bad frame
-        JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));
+        if (p.sizes) JPK_TRY(jpk_dev_blocks_lz77_sizes(ctx, m, src.data(), len.data(), cap.data(), got.data(), s.data()));
+        else JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));
         if (p.exact) for (int32_t q = 0; q < m; q++) if (s[(size_t)q] == JPK_OK && got[(size_t)q] != cap[(size_t)q]) s[(size_t)q] = JPK_E_CORRUPT;
         settle();
     }
-    if ((m = (int32_t)live.size())) {
+    if (!p.sizes && (m = (int32_t)live.size())) {
         std::vector<uint32_t> crc((size_t)m);
         for (int32_t q = 0; q < m; q++) src[(size_t)q] = p.dst[live[(size_t)q]];
         JPK_TRY(jam_crcs(ctx, m, src.data(), len.data(), p.d_crc, crc.data()));
@@ -655,13 +659,14 @@ extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int
 // Per pass: the staged frames first, through jam_cli_pass with the staged stage list -- every one ends verified in its slot A, and its
 // raw size is known; then the capacity answer for the pass; then the plain frames in front of the first bad staged one decode in their
 // places in d_out, which are known now, and meet their crcs; then one gather launch moves the staged frames to theirs.
-extern "C" int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                             int32_t *frames, int32_t *bad_frame)
+namespace {
+// jpk_dev_jam_staged_decompress(_ix).  done (nullable) receives the frames that were delivered, f.raw = their raw size, and *done_bad the
+// first bad frame (-1: none) -- what an index of the archive holds.
+int jam_staged_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, std::vector<JamFrame> *done,
+                      int32_t *done_bad)
 {
-    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    JPK_HIP(hipSetDevice(ctx->device));
-    const JamResult res{out_len, frames, bad_frame};
     jam_result_zero(res);
+    *done_bad = -1;
     if (in_len == 0) return JPK_OK;
     std::vector<JamFrame> fr;
     int32_t bad = -1;
@@ -754,11 +759,41 @@ extern "C" int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, 
         }
         JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, gbytes));
         if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
+        if (done)
+            for (int i = 0; i < m; i++) {
+                done->push_back(fr[k + i]);
+                done->back().raw = raw[i];
+            }
         pos += sum;
-        if (m < n) return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        if (m < n) {
+            *done_bad = (int32_t)k + m;
+            return jam_result_stop(res, pos, (int32_t)k + m, rc);
+        }
         k = e;
     }
+    *done_bad = bad;
     return jam_result_done(res, pos, fr.size(), bad);
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_staged_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                                int32_t *frames, int32_t *bad_frame, jpk_jam_index **index)
+{
+    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    if (index) *index = nullptr;
+    JPK_HIP(hipSetDevice(ctx->device));
+    std::vector<JamFrame> done;
+    int32_t done_bad = -1;
+    const int rc = jam_staged_decode(ctx, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, index ? &done : nullptr, &done_bad);
+    // the index of what was delivered: the whole archive, or the frames in front of the bad one
+    if (index && (rc == JPK_OK || rc == JPK_E_CORRUPT) && !(*index = jam_index_make(done, in_len, done_bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
+    return rc;
+}
+
+extern "C" int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                             int32_t *frames, int32_t *bad_frame)
+{
+    return jpk_dev_jam_staged_decompress_ix(ctx, d_in, in_len, d_out, out_cap, out_len, frames, bad_frame, nullptr);
 }
 
 namespace {
@@ -839,6 +874,9 @@ extern "C" int jpk_jam_staged_decompress(const uint8_t *in, int64_t in_len, uint
 // An index of a stock-CLI archive (kind JPK_JAM_INDEX_CLI) can only come from a decode -- a frame's raw size is in no header -- and a
 // read through it is the same plan with jam_cli_pass as the decoder: two slots of 1.05 x BlockSize + 4096 per touched frame, passes
 // bounded by BlockSize, and the last stage writes a frame that a range holds whole straight into that range at exactly its indexed size.
+// An index of plain and staged frames (kind JPK_JAM_INDEX_STAGED) takes a staged frame's raw size from the token walk of its S1
+// (k_lz77_sizes: no expansion, no checksum) or from a decode; a pass of a read through it holds two groups behind the one plan, the
+// plain frames for the batch decoder and the staged ones for jam_cli_pass with the staged stage list, and one gather for both.
 namespace {
 // the argument checks of both read entries: nothing is touched before they pass
 int jam_read_check(const jpk_jam_index *ix, const void *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out)
@@ -890,9 +928,20 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
     }
     std::vector<int32_t> fstat(F, JPK_OK);
     const bool cli = ix->kind == JPK_JAM_INDEX_CLI;
+    // the frames that go through the stage chain (jam_cli_pass): all of a stock-CLI index, the staged ones of a JPK_JAM_INDEX_STAGED index
+    // (no other index holds one); the other frames are plain ones for the batch decoder alone
+    auto chained = [&](size_t f) { return cli || ix->fr[f].staged; };
     // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
     auto cli_slot = [&](size_t f) { return jpk_align((size_t)jam_cli_cap(ix->fr[f].block_size) + 64); };
     const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    // the jobs of one decoder in a pass: at[q] = the frame's place in the pass; sa / sb / scap / crcs of the chain's frames only
+    struct Group {
+        std::vector<int> at;
+        std::vector<const uint8_t *> ins;
+        std::vector<uint8_t *> outs, sa, sb;
+        std::vector<int32_t> lens, caps, scap;
+        std::vector<uint32_t> crcs;
+    };
     for (size_t k = 0; k < touched.size();) {
         const size_t e = jam_pass_end(touched.size(), k, [&](size_t i) { return jam_weight(ix->fr[touched[i]], cli); });
         const int m = (int)(e - k);
@@ -900,7 +949,7 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             npieces += start[f + 1] - start[f];
-            if (cli) slot_bytes += 2 * cli_slot(f);                                 // the stages' slots A and B, whatever the frame's raw size
+            if (chained(f)) slot_bytes += 2 * cli_slot(f);                          // the stages' slots A and B, whatever the frame's raw size
             else if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);
             stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
         }
@@ -909,57 +958,66 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
         if (!d_in) JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
         uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
         JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
-        std::vector<const uint8_t *> ins((size_t)m), hi((size_t)m);           // hi[i]: the end of what is readable around the decoded frame
-        std::vector<uint8_t *> outs((size_t)m), sa, sb;
-        std::vector<int32_t> lens((size_t)m), caps((size_t)m), outl((size_t)m), st((size_t)m), scap;
-        std::vector<uint32_t> crcs;
-        if (cli) { sa.resize((size_t)m); sb.resize((size_t)m); scap.resize((size_t)m); crcs.resize((size_t)m); }
+        std::vector<const uint8_t *> hi((size_t)m);                           // hi[i]: the end of what is readable around the decoded frame
+        std::vector<uint8_t *> outs((size_t)m);
+        Group chain, plain;
+        chain.crcs.resize((size_t)m);                                         // (filled by copies in stream order: the words must stay where they are)
         size_t slot = o_slots, stage = 0;
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             const JamFrame &fr = ix->fr[f];
-            if (d_in) ins[i] = d_in + fr.payload_off;
+            Group &g = chained(f) ? chain : plain;
+            if (d_in) g.ins.push_back(d_in + fr.payload_off);
             else {
                 JPK_HIP(hipMemcpyAsync(ctx->stage_in + stage, h_in + fr.payload_off, (size_t)fr.psize, hipMemcpyHostToDevice, ctx->stream));
-                ins[i] = ctx->stage_in + stage;
+                g.ins.push_back(ctx->stage_in + stage);
                 stage += jpk_align((size_t)fr.psize + 64);
             }
-            lens[i] = fr.psize; caps[i] = (int32_t)fr.raw;
-            if (cli) {
-                sa[i] = ctx->jam_scratch + slot; sb[i] = sa[i] + cli_slot(f); slot += 2 * cli_slot(f);
-                scap[i] = jam_cli_cap(fr.block_size);
+            g.at.push_back(i); g.lens.push_back(fr.psize); g.caps.push_back((int32_t)fr.raw);
+            if (chained(f)) {
+                uint8_t *sa = ctx->jam_scratch + slot;
+                slot += 2 * cli_slot(f);
+                g.sa.push_back(sa); g.sb.push_back(sa + cli_slot(f)); g.scap.push_back(jam_cli_cap(fr.block_size));
                 // the crc to meet is the one in the header of the archive being read, which need not be the indexed one any more
-                if (d_in) JPK_HIP(hipMemcpyAsync(&crcs[i], d_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
-                else memcpy(&crcs[i], h_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4);
-                outs[i] = home[f] ? home[f] : sa[i];
-                hi[i] = home[f] ? outs[i] + fr.raw : sa[i] + cli_slot(f);
-                continue;
+                uint32_t *crc = &g.crcs[g.at.size() - 1];
+                if (d_in) JPK_HIP(hipMemcpyAsync(crc, d_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
+                else memcpy(crc, h_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4);
+                outs[i] = home[f] ? home[f] : sa;
+                hi[i] = home[f] ? outs[i] + fr.raw : sa + cli_slot(f);
+            } else {
+                if (home[f]) outs[i] = home[f];
+                else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
+                hi[i] = home[f] ? outs[i] + fr.raw : outs[i] + ((fr.raw + 15) & ~(int64_t)15) + 16;
             }
-            if (home[f]) outs[i] = home[f];
-            else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
-            hi[i] = home[f] ? outs[i] + fr.raw : outs[i] + ((fr.raw + 15) & ~(int64_t)15) + 16;
+            g.outs.push_back(outs[i]);
         }
-        // one batched checksum of the frames that decoded, against their header crcs
-        std::vector<int> dec;
-        std::vector<const uint8_t *> cin;
-        std::vector<int32_t> clen;
-        if (cli) {
+        if (!chain.at.empty()) {
             // the stage chain on the touched frames alone, the last stage at the indexed raw size; the checksum is the pass's
-            JPK_TRY(jam_cli_pass(ctx, CliPass{m, ins.data(), lens.data(), sa.data(), sb.data(), scap.data(), outs.data(), caps.data(), crcs.data(), d_crc, false, true},
+            const int nc = (int)chain.at.size();
+            std::vector<int32_t> outl((size_t)nc), st((size_t)nc);
+            JPK_TRY(jam_cli_pass(ctx, CliPass{nc, chain.ins.data(), chain.lens.data(), chain.sa.data(), chain.sb.data(), chain.scap.data(), chain.outs.data(),
+                                              chain.caps.data(), chain.crcs.data(), d_crc, false, true, !cli},
                                  outl.data(), st.data()));
-            for (int i = 0; i < m; i++) fstat[touched[k + i]] = st[i];
-        } else {
-            JPK_TRY(jpk_dev_blocks_decompress(ctx, m, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
-            for (int i = 0; i < m; i++) {
-                if (st[i] != JPK_OK || outl[i] != caps[i]) { fstat[touched[k + i]] = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; continue; }
-                dec.push_back(i); cin.push_back(outs[i]); clen.push_back(caps[i]);
-            }
+            for (int q = 0; q < nc; q++) fstat[touched[k + (size_t)chain.at[q]]] = st[q];
         }
-        if (!dec.empty()) {
-            std::vector<uint32_t> crc(dec.size());
-            JPK_TRY(jam_crcs(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc, crc.data()));
-            for (size_t q = 0; q < dec.size(); q++)
-                if (crc[q] != ix->fr[touched[k + (size_t)dec[q]]].crc) fstat[touched[k + (size_t)dec[q]]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
+        if (!plain.at.empty()) {
+            // the batch decoder, then one batched checksum of the frames that decoded, against their header crcs
+            const int np = (int)plain.at.size();
+            std::vector<int32_t> outl((size_t)np), st((size_t)np), clen;
+            std::vector<size_t> dec;
+            std::vector<const uint8_t *> cin;
+            JPK_TRY(jpk_dev_blocks_decompress(ctx, np, plain.ins.data(), plain.lens.data(), plain.outs.data(), plain.caps.data(), outl.data(), st.data()));
+            for (int q = 0; q < np; q++) {
+                const size_t f = touched[k + (size_t)plain.at[q]];
+                if (st[q] != JPK_OK || outl[q] != plain.caps[q]) { fstat[f] = st[q] != JPK_OK ? st[q] : JPK_E_CORRUPT; continue; }
+                dec.push_back(f); cin.push_back(plain.outs[q]); clen.push_back(plain.caps[q]);
+            }
+            if (!dec.empty()) {
+                std::vector<uint32_t> crc(dec.size());
+                JPK_TRY(jam_crcs(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc, crc.data()));
+                for (size_t q = 0; q < dec.size(); q++)
+                    if (crc[q] != ix->fr[dec[q]].crc) fstat[dec[q]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
+            }
         }
         // the pieces of the verified frames (the one a frame was decoded into in place is already where it belongs)
         std::vector<JamGatherPiece> tab;
@@ -1093,7 +1151,116 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
     return JPK_OK;
 }
 
+namespace {
+// The frames of an index of kind JPK_JAM_INDEX_STAGED for an archive in HBM: the walk, then per pass (the limits of
+// jpk_dev_jam_staged_decompress) the staged frames through jam_cli_pass without an output -- verify: the whole staged stage list and the
+// header crcs; otherwise its sizes form, which stops in front of the expansion.  Plain frames keep the raw size of the walk and are not
+// decoded.  done = the frames in front of the first bad one, *bad = its position (-1: none).
+int jam_staged_sizes(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, bool verify, std::vector<JamFrame> &done, int32_t *bad)
+{
+    std::vector<JamFrame> fr;
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, bad, JAM_STAGED));
+    const size_t o_slots = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, false);
+        std::vector<size_t> sidx, slot;
+        std::vector<const uint8_t *> sin;
+        std::vector<int32_t> slens, caps, bsz;
+        std::vector<uint32_t> scrc;
+        size_t need = o_slots;
+        for (size_t i = k; i < e; i++) {
+            const JamFrame &f = fr[i];
+            if (!f.staged) continue;
+            sidx.push_back(i);
+            sin.push_back(d_in + f.payload_off); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
+            caps.push_back(jam_cli_cap(f.block_size));
+            slot.push_back(jpk_align((size_t)caps.back() + 64));
+            need += 2 * slot.back();
+        }
+        const size_t ns = sidx.size();
+        size_t stop = e;
+        if (ns) {
+            JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+            uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+            std::vector<uint8_t *> a(ns), b(ns);
+            size_t off = o_slots;
+            for (size_t q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
+            std::vector<int32_t> sraw(ns), sst(ns);
+            // a frame that declares more than its BlockSize is a bad frame, expanded or not
+            JPK_TRY(jam_cli_pass(ctx, CliPass{(int)ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, true, false,
+                                              true, !verify},
+                                 sraw.data(), sst.data()));
+            for (size_t q = 0; q < ns; q++) {
+                if (sst[q] != JPK_OK) { stop = sidx[q]; break; }
+                fr[sidx[q]].raw = sraw[q];
+            }
+        }
+        done.insert(done.end(), fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)stop);
+        if (stop < e) { *bad = (int32_t)stop; return JPK_OK; }
+        k = e;
+    }
+    return JPK_OK;
+}
+
+bool jam_verify_ok(int32_t verify) { return verify == 0 || verify == 1; }
+}  // namespace
+
+extern "C" int jpk_dev_jam_staged_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t verify, jpk_jam_index **index, int32_t *bad_frame)
+{
+    // (the argument checks come before the first device call, and an empty archive makes none)
+    if (!ctx || !index || in_len < 0 || (in_len > 0 && !d_in) || !jam_verify_ok(verify)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> done;
+    int32_t bad = -1;
+    if (in_len > 0) {
+        JPK_HIP(hipSetDevice(ctx->device));
+        JPK_TRY(jam_staged_sizes(ctx, d_in, in_len, verify != 0, done, &bad));
+    }
+    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
+extern "C" int jpk_jam_staged_index_create(const uint8_t *in, int64_t in_len, int32_t verify, jpk_jam_index **index, int32_t *bad_frame)
+{
+    if (!index || in_len < 0 || (in_len > 0 && !in) || !jam_verify_ok(verify)) return JPK_E_ARG;
+    *index = nullptr;
+    std::vector<JamFrame> fr, done;
+    int32_t bad = -1;
+    jam_walk_host(in, in_len, fr, &bad, JAM_STAGED);
+    auto staged_in = [&fr](size_t k, size_t e) { return std::any_of(fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e, [](const JamFrame &f) { return f.staged; }); };
+    // an archive of plain frames is indexed by the walk alone: no device is looked for
+    jpk_ctx *ctx = nullptr;
+    if (staged_in(0, fr.size())) JPK_TRY(jpk_host_enter(&ctx, 0));
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_pass_end(fr, k, false);
+        if (!staged_in(k, e)) { done.insert(done.end(), fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e); k = e; continue; }
+        // staged one pass at a time, as jpk_jam_cli_index_create: the pass's frames are an archive of their own for the device
+        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+        std::vector<JamFrame> got;
+        int32_t pass_bad = -1;
+        const int rc = jam_staged_sizes(ctx, ctx->stage_in, a1 - a0, verify != 0, got, &pass_bad);
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+        JPK_TRY(rc);
+        for (JamFrame &f : got) { f.payload_off += a0; done.push_back(f); }
+        if (pass_bad >= 0) { bad = (int32_t)k + pass_bad; break; }
+        k = e;
+    }
+    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
+}
+
 extern "C" int jpk_jam_index_kind(const jpk_jam_index *index) { return index ? index->kind : JPK_E_ARG; }
+
+extern "C" int jpk_jam_index_frame_kind(const jpk_jam_index *index, int32_t k)
+{
+    if (!index || k < 0 || (size_t)k >= index->fr.size()) return JPK_E_ARG;
+    if (index->kind != JPK_JAM_INDEX_STAGED) return index->kind;
+    return index->fr[(size_t)k].staged ? JPK_JAM_INDEX_STAGED : JPK_JAM_INDEX_PLAIN;
+}
 
 extern "C" int jpk_jam_index_info(const jpk_jam_index *index, int32_t *frames, int64_t *raw_len, int64_t *archive_len)
 {

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/jampack_abi.h"
 #include "prestage_rules.hpp"
 
 namespace lzx {
@@ -53,6 +54,37 @@ template <class Put> JPK_HD void step(Plan &p, bool parsed, const pre::Token &t,
     if ((int64_t)t.off > p.op) return fail();
     add(t.len, t.off, 1u);
 }
+
+// ---- the size rule: the same walk for the raw size alone (jpk_lz77_size, k_lz77_sizes) ---------------------------------------------------
+// What jpk_lz77_decompress / k_pre_lz77 answer for a stream without its bytes: the status by their checks in their order -- the two
+// failures apart, and no record cap, which is why this is not lzx::step -- and op, the sum of the literal and match lengths.
+struct Size { int64_t pos = 0, op = 0; int32_t status = JPK_OK; bool done = false; };
+
+JPK_HD bool more(const Size &s, int64_t in_len) { return !s.done && s.pos < in_len; }
+
+// One token: t was parsed at s.pos (parsed == false: pre::parse_token refused it).  s.pos grows by the token's bytes at least.
+JPK_HD void step(Size &s, bool parsed, const pre::Token &t, int64_t in_len, int64_t out_cap)
+{
+    auto fail = [&s](int32_t status) { s.status = status; s.done = true; };
+    if (!parsed) return fail(JPK_E_CORRUPT);
+    s.pos += t.used;
+    if (t.off == 0) {                                                  // end marker: raw remainder
+        const int64_t rest = in_len - s.pos;
+        if (s.op + rest > out_cap) return fail(JPK_E_CAPACITY);
+        s.op += rest;
+        s.done = true;
+        return;
+    }
+    if (t.off < 0 || t.lit > in_len - s.pos) return fail(JPK_E_CORRUPT);
+    if (t.lit + t.len > out_cap - s.op) return fail(JPK_E_CAPACITY);
+    s.op += t.lit;
+    s.pos += t.lit;
+    if ((int64_t)t.off > s.op) return fail(JPK_E_CORRUPT);
+    s.op += t.len;
+}
+
+// the out_len of both decoders: 0 unless the stream is good (op <= out_cap < 2^31)
+JPK_HD int32_t out_len(const Size &s) { return s.status == JPK_OK ? (int32_t)s.op : 0; }
 
 // the record of output position pos among s[0..n): the last one with out <= pos (n >= 1)
 JPK_HD uint32_t find(const Seg *s, uint32_t n, uint32_t pos)

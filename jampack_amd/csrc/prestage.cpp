@@ -17,6 +17,7 @@
 
 #include "../../include/jampack_abi.h"
 #include "dedupe.hpp"
+#include "lz_expand.hpp"
 
 // Lz77::Decompress (lz77.cpp:678-714); the token is pre::parse_token.  Offset 0 ends the LZ code: the rest of the input is copied through.
 extern "C" int jpk_lz77_decompress(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len)
@@ -48,6 +49,22 @@ extern "C" int jpk_lz77_decompress(const uint8_t *in, int32_t in_len, uint8_t *o
     }
     *out_len = (int32_t)op;
     return JPK_OK;
+}
+
+// The raw size of a stream without its bytes: the status jpk_lz77_decompress gives it at this out_cap and, when that is JPK_OK, its
+// *out_len (0 otherwise).  The rule is lzx::step(lzx::Size) of lz_expand.hpp, which k_lz77_sizes compiles too.  No device call.
+extern "C" int jpk_lz77_size(const uint8_t *in, int32_t in_len, int32_t out_cap, int32_t *out_len)
+{
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
+    lzx::Size s;
+    while (lzx::more(s, in_len)) {
+        pre::Token t;
+        const uint8_t *at = in + s.pos;
+        const bool parsed = pre::parse_token([at](int j) { return (uint32_t)at[j]; }, in_len - s.pos, &t);
+        lzx::step(s, parsed, t, in_len, out_cap);
+    }
+    *out_len = lzx::out_len(s);
+    return s.status;
 }
 
 namespace {

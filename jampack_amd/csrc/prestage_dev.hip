@@ -1,6 +1,7 @@
 // prestage_dev.hip -- the decoders of the three stages the stock CLI runs in front of the BWT (Jampack::Decomp, jampack.cpp:47-60), on gfx950,
 // for batches of blocks that already sit in HBM behind the batched rANS decode + inverse BWT:
 //   k_pre_lz77     Lz77::Decompress (lz77.cpp:678-714)   one workgroup per block: every lane parses the token, all lanes copy
+//   k_lz77_sizes   the raw size of that stage's output alone (jpk_dev_blocks_lz77_sizes): one wave per block walks the tokens, no copies
 //   k_lzx_plan     the same stage as two launches (jpk_dev_blocks_lz77_expand; the rule is lz_expand.hpp): one wave per block turns the
 //   k_lzx_copy     tokens into segment records, then every thread fills aligned 16-byte words of the output from the records
 //   k_lpx<false>   Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
@@ -111,6 +112,30 @@ __global__ __launch_bounds__(PRE_TB) void k_pre_lz77(const PreJob *__restrict__ 
         op += len;
     }
     if (tid == 0) { res[0] = (uint32_t)status; res[1] = status == JPK_OK ? (uint32_t)op : 0u; }
+}
+
+// The raw size of a block without its bytes (jpk_dev_blocks_lz77_sizes; the rule is lzx::Size of lz_expand.hpp, which jpk_lz77_size
+// compiles too): one wave per block walks the tokens as k_pre_lz77 does, with its checks in its order, and copies nothing.  mail as
+// k_pre_lz77, the two words stored by lane 0 -- the only stores; jb.out is not looked at.  No LDS, no barrier.  Every iteration moves
+// pos by the token's bytes (two at least) or ends the walk, so the loop ends at in_len on any stream.
+__global__ __launch_bounds__(64) void k_lz77_sizes(const PreJob *__restrict__ jobs, uint32_t *__restrict__ mail)
+{
+    const PreJob jb = jobs[blockIdx.x];
+    const uint32_t tid = threadIdx.x;
+    const int64_t in_len = jb.in_len;
+    lzx::Size s;
+    while (lzx::more(s, in_len)) {
+        const int64_t wi = s.pos + (int64_t)(tid & 15u);
+        const uint32_t w = wi < in_len ? jb.in[wi] : 0u;
+        pre::Token t;
+        const bool parsed = pre::parse_token([w](int j) { return win_byte(w, j); }, in_len - s.pos, &t);
+        lzx::step(s, parsed, t, in_len, (int64_t)jb.out_cap);
+    }
+    if (tid == 0) {
+        uint32_t *res = mail + 2 * (size_t)blockIdx.x;
+        res[0] = (uint32_t)s.status;
+        res[1] = (uint32_t)lzx::out_len(s);
+    }
 }
 
 // ---- the parallel LZ77 expander ------------------------------------------------------------------------------------------------
@@ -864,6 +889,35 @@ extern "C" int jpk_dev_blocks_lz77_decompress(jpk_ctx *ctx, int32_t n, const uin
     std::vector<int32_t> st_local((size_t)n);
     int32_t *stp = status ? status : st_local.data();
     JPK_TRY(lz77_serial(ctx, n, d_in, in_len, d_out, out_cap, out_len, stp));
+    return finish_statuses(n, status, stp);
+}
+
+// The raw sizes of n blocks without their bytes: k_lz77_sizes in one launch, one read-back of the results.
+extern "C" int jpk_dev_blocks_lz77_sizes(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, const int32_t *out_cap, int32_t *out_len,
+                                         int32_t *status)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !out_cap || !out_len))) return JPK_E_ARG;
+    for (int b = 0; b < n; b++)
+        if (in_len[b] < 0 || out_cap[b] < 0 || (in_len[b] > 0 && !d_in[b])) return JPK_E_ARG;
+    JPK_TRY(pre_enter(ctx));
+    if (n == 0) return JPK_OK;
+    std::vector<PreJob> jobs((size_t)n);
+    uint64_t bytes = 0;
+    for (int b = 0; b < n; b++) {
+        jobs[(size_t)b] = PreJob{d_in[b], nullptr, in_len[b], out_cap[b], (uint32_t)b, 0u};
+        bytes += (uint32_t)in_len[b];
+    }
+    PreCall pc;
+    JPK_TRY(pre_upload(ctx, jobs, 2 * (size_t)n, 0, &pc));
+    JPK_LAUNCH(ctx, PROF_LZ77_SIZES, bytes, k_lz77_sizes, dim3((unsigned)n), dim3(64), pc.d_jobs, pc.d_mail);
+    std::vector<uint32_t> mail(2 * (size_t)n);
+    JPK_TRY(pre_finish(ctx, pc.d_mail, mail));
+    std::vector<int32_t> st_local((size_t)n);
+    int32_t *stp = status ? status : st_local.data();
+    for (int b = 0; b < n; b++) {
+        stp[b] = (int32_t)mail[2 * (size_t)b];
+        out_len[b] = stp[b] == JPK_OK ? (int32_t)mail[2 * (size_t)b + 1] : 0;
+    }
     return finish_statuses(n, status, stp);
 }
 
