@@ -579,6 +579,58 @@ JPK_API int jpk_dev_jam_read(jpk_ctx *ctx, const jpk_jam_index *index, const uin
 JPK_API int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len, uint8_t *const *out,
                          int32_t *status, int32_t *bad_frame);
 
+/* ---- damaged archives: an index past the damage, and everything recoverable ("Damaged archives") ----
+ * The creators above stop at the first bad frame, and so do the whole-archive decoders; their contracts stay as they are.  These
+ * entries go on behind the damage.  The rule (jampack_amd/csrc/jam_resync.hpp, one source for both forms): a frame is STRUCTURALLY VALID
+ * at offset o when its header is plausible -- "JAM", BlockSize in [JPK_MIN_BLOCKSIZE, JPK_MAX_BLOCKSIZE] (kind JPK_JAM_INDEX_STAGED:
+ * JPK_JAM_STAGED allowed), 0 <= payload size <= JPK_MAX_BLOCKSIZE, header and payload inside the archive --, jpk_ans_decoded_size
+ * accepts its payload and the size that declares fits its BlockSize: the checks of the frame walks, no more and no fewer.  From g = 0:
+ * o = the smallest offset >= g at which a structurally valid frame starts (none: in_len); the bytes [g, o) in front of it, if any, are
+ * a gap; the frame at o is taken and g moves behind its payload.  Frames and gaps tile [0, in_len) in order and without overlap; on an
+ * undamaged archive the result is the frame table of the creators above, no gap, and for an archive in HBM no launch beyond theirs.
+ * The index is a pure function of the archive bytes, kind and verify.  A header-shaped decoy inside a lost payload is taken only if
+ * its chunk headers walk too; one that does is a frame of the index, and a read of it fails its crc (or, rarely, its decode).
+ * A gap is {archive_off, archive_len, frame = the number of recovered frames in front of it, why}:
+ *   JPK_JAM_GAP_NOFRAME  no structurally valid frame starts in these archive bytes
+ *   JPK_JAM_GAP_STAGE    (kind JPK_JAM_INDEX_STAGED) a structurally valid staged frame whose stages -- or, verify = 1, crc -- refuse it:
+ *                        its raw size is unknown, so it cannot be a frame of the index; the gap is its span, header + payload
+ * kind JPK_JAM_INDEX_PLAIN: verify must be 0; frames are unverified as in a plain index; the host form makes no device call.
+ * kind JPK_JAM_INDEX_STAGED: staged frames are sized pass by pass as by jpk_dev_jam_staged_index_create (verify as there); a pass holds
+ * frames that lie back to back; the host form looks for a device only when the walk found a staged frame.
+ * kind JPK_JAM_INDEX_CLI: JPK_E_ARG -- a stock-CLI index comes from a decode that stops at a bad frame; continuing it is future work.
+ * The index has the requested kind, no bad frame (jpk_jam_index_info and the readers see a plain table), raw offsets that count the
+ * recovered frames only -- a gap holds no raw bytes --, and jpk_jam_index_info / _frame / _kind / _frame_kind / _destroy,
+ * jpk_dev_jam_read and jpk_jam_read take it unchanged.  *gaps (may be NULL) = the number of gaps.  Arguments are checked before a
+ * device is looked for; in_len == 0 gives an empty index.  Cost on hostile input: every archive byte is scanned once per search that
+ * reaches it, every plausible header costs one chunk-header walk of its payload (DESIGN 4.6 has the bound). */
+#define JPK_JAM_GAP_NOFRAME 0   /* no structurally valid frame starts in these archive bytes */
+#define JPK_JAM_GAP_STAGE   1   /* a structurally valid staged frame whose stages (or, verify = 1, crc) refuse it: its raw size is unknown */
+JPK_API int jpk_dev_jam_index_recover(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps);
+JPK_API int jpk_jam_index_recover(const uint8_t *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps);
+JPK_API int jpk_jam_index_gaps(const jpk_jam_index *index);   /* count; 0 for an index of the existing creators; JPK_E_ARG for NULL */
+/* gap g of an index (JPK_E_ARG outside [0, jpk_jam_index_gaps)); every output pointer may be NULL */
+JPK_API int jpk_jam_index_gap(const jpk_jam_index *index, int32_t g, int64_t *archive_off, int64_t *archive_len, int32_t *frame, int32_t *why);
+/* Everything an index can deliver of its archive, in one call: frame k at d_out + its raw offset, *out_len = the index's raw_len.  Takes
+ * any index -- recovered or not, any kind.  A frame that fails its decode or its crc gets frame_status[k] = JPK_E_CORRUPT and its place
+ * filled with zeros; *failed = the number of such frames; the call returns JPK_OK whenever it ran, however many frames failed.  A frame of
+ * 0 raw bytes is reported JPK_OK and is not verified.  frame_status (one entry per frame of the index) and failed may be NULL.
+ * out_cap < raw_len: JPK_E_CAPACITY, *out_len = raw_len, nothing written.  in_len must be the index's archive length (JPK_E_ARG).
+ * It is one range per frame handed to the reader of jpk_dev_jam_read -- its passes, its decoders, every frame in place --, then a memset
+ * per failed frame.  Nothing outside [d_out, d_out + raw_len) is written. */
+JPK_API int jpk_dev_jam_salvage(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                int32_t *frame_status, int32_t *failed);
+/* host-buffer form through the calling thread's pooled context (the arguments and the capacity are checked before a device is looked for) */
+JPK_API int jpk_jam_salvage(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frame_status,
+                            int32_t *failed);
+/* probe: the offsets of the first max_cands (1..65536) plausible frame headers that start in [start, start + window) of d_in[0..in_len),
+ * ascending, from one run of k_jam_scan_count / the prefix scan / k_jam_scan_emit; window <= 2^30; stateless, reads only.  offsets holds
+ * max_cands entries */
+JPK_API int jpk_debug_jam_scan(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t window, int32_t staged_ok, int32_t max_cands,
+                               int64_t *offsets, int32_t *count);
+/* test hook (JPK_DEBUG_HOOKS=1 only, JPK_E_ARG otherwise): the window (bytes) and the candidates per round of the search of both recover
+ * entries in this process; 0, 0 restores the defaults (256 MiB, 4096).  The index does not depend on either. */
+JPK_API int jpk_debug_jam_recover_limits(int64_t window, int32_t max_cands);
+
 /* ---- kernel-level probes used by tests/ and bench.py (device buffers) ------------------------------------ */
 /* Comparator for BASELINE config 3 ("120-way parallel LF-map"): the reference's own GPU kernel shape -- 120 threads, one per
  * stored index, p = Map[p-1] (CUDAInverse<<<40,3>>>, bwt.cpp:8-19, 176-183, 226-229) -- on the same Map.  Same bytes as

@@ -149,6 +149,14 @@ _SIGS = {
     "jpk_jam_staged_index_create": (C.c_int, [_vp, C.c_int64, C.c_int32, C.POINTER(_vp), _i32p]),
     "jpk_jam_index_frame_kind": (C.c_int, [_vp, C.c_int32]),
     "jpk_dev_jam_staged_decompress_ix": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(_vp)]),
+    "jpk_dev_jam_index_recover": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_vp), _i32p]),
+    "jpk_jam_index_recover": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(_vp), _i32p]),
+    "jpk_jam_index_gaps": (C.c_int, [_vp]),
+    "jpk_jam_index_gap": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_dev_jam_salvage": (C.c_int, [_vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_jam_salvage": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
+    "jpk_debug_jam_scan": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _i32p]),
+    "jpk_debug_jam_recover_limits": (C.c_int, [C.c_int64, C.c_int32]),
     "jpk_dev_suffix_array": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "jpk_dev_sort_pairs_u64": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32]),
     "jpk_dev_exclusive_scan_u32": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_uint32)]),

@@ -217,13 +217,15 @@ def jam_decompress(stream) -> np.ndarray:
 
 
 JAM_INDEX_PLAIN, JAM_INDEX_CLI, JAM_INDEX_STAGED = 0, 1, 2    # JPK_JAM_INDEX_*: the kinds of an index (and, for kind 2, of its frames)
+JAM_GAP_NOFRAME, JAM_GAP_STAGE = 0, 1                         # JPK_JAM_GAP_*: why a recovered index skipped archive bytes
 
 
 class JamIndex:
     """jpk_jam_index: the frame table of one archive -- `frames`, `raw_len`, `archive_len`, `bad_frame` (-1: the whole archive is
     indexed; otherwise the index covers the frames in front of that one), `kind` (0: a plain archive, 1: an archive of the stock CLI,
     indexed by decoding it, 2: an archive of plain and staged frames, a staged frame sized by the token walk of its first stage or by a
-    decode), `frame(k)` and `frame_kind(k)`.  Keeps no reference to the archive."""
+    decode), `frame(k)` and `frame_kind(k)`; `gaps`, the archive bytes a recovered index (jam_recover_index) skipped, a list of
+    (archive_off, archive_len, frame, why) -- empty for every other index.  Keeps no reference to the archive."""
 
     def __init__(self, handle, bad_frame: int):
         self._h = handle
@@ -231,6 +233,11 @@ class JamIndex:
         _chk(lib().jpk_jam_index_info(self._h, C.byref(k), C.byref(raw), C.byref(alen)), "jpk_jam_index_info")
         self.frames, self.raw_len, self.archive_len, self.bad_frame = k.value, raw.value, alen.value, int(bad_frame)
         self.kind = int(lib().jpk_jam_index_kind(self._h))
+        self.gaps = []
+        for g in range(int(lib().jpk_jam_index_gaps(self._h))):
+            o, n, f, w = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+            _chk(lib().jpk_jam_index_gap(self._h, g, C.byref(o), C.byref(n), C.byref(f), C.byref(w)), "jpk_jam_index_gap")
+            self.gaps.append((o.value, n.value, f.value, w.value))
 
     def frame(self, k: int):
         """(raw offset, raw size, payload offset, payload size) of frame k"""
@@ -281,6 +288,33 @@ def jam_staged_index(stream, verify: bool = False) -> JamIndex:
     h, bad = C.c_void_p(), C.c_int32(-1)
     _chk(lib().jpk_jam_staged_index_create(_ptr(c), len(c), int(verify), C.byref(h), C.byref(bad)), "jpk_jam_staged_index_create")
     return JamIndex(h, bad.value)
+
+
+def jam_recover_index(stream, kind: int = JAM_INDEX_PLAIN, verify: bool = False) -> JamIndex:
+    """jpk_jam_index_recover: the index of a damaged archive in host memory -- the walk goes on behind a bad frame at the next offset
+    where a structurally valid frame starts, and what it skipped is in `gaps`.  kind 0: plain frames, no device call; kind 2: plain and
+    staged frames, a staged frame sized (verify=True: decoded and checked) on the device, one its stages refuse becomes a gap."""
+    c = _np_u8(stream)
+    h, g = C.c_void_p(), C.c_int32(0)
+    _chk(lib().jpk_jam_index_recover(_ptr(c), len(c), int(kind), int(verify), C.byref(h), C.byref(g)), "jpk_jam_index_recover")
+    return JamIndex(h, -1)
+
+
+def jam_salvage(stream, index: JamIndex | None = None, kind: int = JAM_INDEX_PLAIN):
+    """jpk_jam_salvage: everything recoverable of an archive in host memory -> (bytes, frame_status).  Frame k of the index lies at its
+    raw offset; a frame that fails its decode or its crc has status -3 and zeros in its place.  Without an index the archive is
+    recovered first (jam_recover_index(stream, kind))."""
+    c = _np_u8(stream)
+    ix = index if index is not None else jam_recover_index(c, kind)
+    try:
+        out = np.zeros(max(ix.raw_len, 1), dtype=np.uint8)
+        st = (C.c_int32 * max(ix.frames, 1))()
+        n, failed = C.c_int64(0), C.c_int32(0)
+        _chk(lib().jpk_jam_salvage(ix._h, _ptr(c), len(c), out.ctypes.data, ix.raw_len, C.byref(n), st, C.byref(failed)), "jpk_jam_salvage")
+        return out[: n.value], list(st)[: ix.frames]
+    finally:
+        if index is None:
+            ix.close()
 
 
 def lz77_size(stream, cap: int) -> int:
@@ -850,6 +884,27 @@ class Context:
         h, bad = C.c_void_p(), C.c_int32(-1)
         _chk(lib().jpk_dev_jam_staged_index_create(self._h, _dptr(d_in), in_len, int(verify), C.byref(h), C.byref(bad)), "jpk_dev_jam_staged_index_create")
         return JamIndex(h, bad.value)
+
+    def jam_recover_index(self, d_in, in_len, kind: int = JAM_INDEX_PLAIN, verify: bool = False) -> JamIndex:
+        """jpk_dev_jam_index_recover: the index of a damaged archive in HBM, past its damage (see jam_recover_index); where the frame walk
+        stops, k_jam_scan_* look for the next frame"""
+        h, g = C.c_void_p(), C.c_int32(0)
+        _chk(lib().jpk_dev_jam_index_recover(self._h, _dptr(d_in), in_len, int(kind), int(verify), C.byref(h), C.byref(g)), "jpk_dev_jam_index_recover")
+        return JamIndex(h, -1)
+
+    def jam_salvage(self, index: JamIndex, d_in, in_len, d_out, out_cap):
+        """jpk_dev_jam_salvage: every frame of the index into d_out at its raw offset -> (raw_len, frame_status); a failed frame has
+        status -3 and zeros in its place.  Raises JampackError(-2) when out_cap is below the index's raw_len (nothing is written)."""
+        st = (C.c_int32 * max(index.frames, 1))()
+        n, failed = C.c_int64(0), C.c_int32(0)
+        _chk(lib().jpk_dev_jam_salvage(self._h, index._h, _dptr(d_in), in_len, _dptr(d_out), out_cap, C.byref(n), st, C.byref(failed)), "jpk_dev_jam_salvage")
+        return n.value, list(st)[: index.frames]
+
+    def jam_scan(self, d_in, in_len, start: int, window: int, staged_ok: bool = False, max_cands: int = 4096):
+        """jpk_debug_jam_scan (probe): the offsets of the first max_cands plausible frame headers that start in [start, start + window)"""
+        offs, n = (C.c_int64 * max_cands)(), C.c_int32(0)
+        _chk(lib().jpk_debug_jam_scan(self._h, _dptr(d_in), in_len, start, window, int(staged_ok), max_cands, offs, C.byref(n)), "jpk_debug_jam_scan")
+        return list(offs)[: n.value]
 
     def jam_read(self, index: JamIndex, d_in, in_len, ranges, d_outs, check: bool = True):
         """jpk_dev_jam_read: the ranges [(raw offset, length), ...] of the archive d_in[0..in_len) into the device buffers d_outs

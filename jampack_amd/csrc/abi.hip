@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "chain_pool.hpp"
 #include "prestage_rules.hpp"
+#include "jam_resync.hpp"
 
 // Independent blocks run on separate contexts (= HIP streams).  ROCm multiplexes streams onto GPU_MAX_HW_QUEUES
 // hardware queues, round robin in creation order (default 4: tools/conctest.hip shows exactly four kernels at a time whatever
@@ -184,7 +185,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_rs_hist/k_os_digits", "k_rs_scatter/k_os_scatter", "k_scan_*/k_tab_*/k_win_*", "k_gather_win", "k_seg_round", "k_r0_*/k_lg_finish/k_cmp_*", "k_bwt_image",
     "k_hist", "k_build_nxt", "k_walk", "k_rank_jump", "k_copy_out",
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
-    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack",
+    "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack", "k_jam_scan_*",
     "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit", "k_enc_filters",
     "k_lzx_plan", "k_lz77_sizes", "k_lzx_copy", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
@@ -774,8 +775,7 @@ bool jpk_jam_header_parse(const uint8_t *h, int64_t avail, uint32_t *crc, int32_
     memcpy(psize, h + 7, 4);
     memcpy(block_size, h + 11, 4);
     // "Refusing to read from corrupt header!", jampack.cpp:150 -- and the payload fits in what is left
-    return memcmp(h, "JAM", 3) == 0 && jpk_jam_block_size_ok(*block_size) && *psize >= 0 && *psize <= JPK_MAX_BLOCKSIZE &&
-           (int64_t)*psize <= avail - JPK_JAM_HEADER_BYTES;
+    return jrs::magic_ok(h[0], h[1], h[2]) && jrs::fields_ok(*psize, *block_size, avail, false);
 }
 
 extern "C" int jpk_dev_jam_block_write(jpk_ctx *ctx, const uint8_t *d_in, int32_t in_len, int32_t block_size, uint8_t *d_out, int32_t out_cap,
@@ -1782,27 +1782,7 @@ extern "C" int jpk_ans_decode(const uint8_t *in, int32_t in_len, uint8_t *out, i
 extern "C" int jpk_ans_decoded_size(const uint8_t *in, int32_t in_len, int64_t *decoded_len, int32_t *chunks)
 {
     if (!decoded_len || in_len < 0 || (in_len > 0 && !in)) return JPK_E_ARG;
-    int64_t ip = 0, total = 0;
-    int32_t nch = 0;
-    while (ip < in_len) {
-        int64_t fsum = 0;
-        uint32_t v = 0, olen = 0;
-        for (int s = 0; s < 259; s++) {                 // 256 frequencies, olen, clen, rlen (ans.cpp:272-302)
-            const int n = pre::leb_read(in + ip, (int64_t)in_len - ip, &v);
-            if (n < 0) return JPK_E_CORRUPT;
-            ip += n;
-            if (s < 256) { if (v > (uint32_t)JPK_ANS_CHUNK) return JPK_E_CORRUPT; fsum += v; }
-            else if (s == 256) { if (v > (uint32_t)JPK_ANS_CHUNK || (int64_t)v != fsum) return JPK_E_CORRUPT; total += v; olen = v; }
-            else if (s == 257) { if (v < 16 || (int64_t)v > (int64_t)in_len - ip) return JPK_E_CORRUPT; fsum = v; }   // clen, payload follows rlen
-            else { if (v > olen) return JPK_E_CORRUPT; }     // RLE0 never has more symbols than bytes ("rle mismatch!", rle.cpp:73)
-        }
-        if (fsum > (int64_t)in_len - ip) return JPK_E_CORRUPT;
-        ip += fsum;                                      // skip the payload
-        nch++;
-    }
-    *decoded_len = total;
-    if (chunks) *chunks = nch;
-    return JPK_OK;
+    return jrs::ans_decoded_size(in, in_len, decoded_len, chunks);          // the chunk-header walk is part of the resync rule (jam_resync.hpp)
 }
 
 extern "C" int jpk_block_compress(const uint8_t *in, int32_t in_len, uint8_t *out, int32_t out_cap, int32_t *out_len)

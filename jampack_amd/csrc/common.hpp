@@ -35,7 +35,7 @@ enum JpkProfId {
     PROF_RS_HIST = 0, PROF_RS_SCATTER, PROF_SCAN, PROF_SA_KEYS, PROF_SA_SEG, PROF_SA_RERANK, PROF_BWT_GATHER,
     PROF_INV_HIST, PROF_INV_BUILD, PROF_INV_WALK, PROF_INV_RANK, PROF_INV_COPY,
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
-    PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM,
+    PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM, PROF_JAM_SCAN,
     PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT, PROF_ENC_FILTERS,
     PROF_LZX_PLAN, PROF_LZ77_SIZES, PROF_LZX_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
@@ -302,6 +302,13 @@ struct JamWalkFrame { uint64_t payload_off; int32_t psize; uint32_t crc; int32_t
 // their block_size in the table keeps JPK_JAM_STAGED
 int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
                          uint32_t *d_mail, bool staged_ok = false);
+// The plausible frame headers that start in [start, end) of d_in[0..in_len) (jam_resync.hpp), 0 <= start < end <= in_len, in two launches
+// around a scan of d_counts (jpk_jam_scan_tiles(d_in, start, end) + 1 words): the count leaves the hits per tile; the emit takes their
+// exclusive prefix sums and writes the first max_cands candidates to d_out in ascending order (block_size: the field as it is).  Enqueued.
+uint32_t jpk_jam_scan_tiles(const uint8_t *d_in, int64_t start, int64_t end);
+int jpk_jam_scan_count_enqueue(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, uint32_t *d_counts);
+int jpk_jam_scan_emit_enqueue(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, uint32_t *d_counts,
+                              JamWalkFrame *d_out, uint32_t max_cands);
 // one frame of the pack: its payload slot, its offset in the pass's output, its payload size
 struct JamPackFrame { const uint8_t *slot; uint64_t off; int32_t psize; int32_t pad; };
 constexpr int JPK_JAM_PASS_FRAMES = 128;                     // frames per pass of the archive calls (and per pack launch)

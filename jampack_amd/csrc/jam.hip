@@ -4,8 +4,11 @@
 //                from payload slots in scratch, organised by destination: a thread owns aligned 16-byte words of the output
 //   k_jam_gather delivers the pieces of a range read -- (source, destination, length) of decoded bytes -- organised by destination
 //                in the same way: a thread owns aligned 16-byte words of a piece's destination
+//   k_jam_scan_* the plausible frame headers of a window of an archive, in ascending order: where a walk past damage looks for the next
+//                frame (jam_resync.hpp; DESIGN 4.6, "Damaged archives")
 // The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress / jpk_dev_jam_read (jam_archive.hip).
 #include "common.hpp"
+#include "jam_resync.hpp"
 
 namespace {
 
@@ -30,9 +33,7 @@ __global__ __launch_bounds__(64) void k_jam_walk(const uint8_t *__restrict__ in,
         const uint32_t crc = h[3] | (h[4] << 8) | (h[5] << 16) | (h[6] << 24);
         const int32_t psize = (int32_t)(h[7] | (h[8] << 8) | (h[9] << 16) | (h[10] << 24));
         const int32_t field = (int32_t)(h[11] | (h[12] << 8) | (h[13] << 16) | (h[14] << 24));
-        const int32_t bs = (staged_ok && field > 0) ? (field & ~JPK_JAM_STAGED) : field;
-        if (h[0] != 'J' || h[1] != 'A' || h[2] != 'M' || bs < JPK_MIN_BLOCKSIZE || bs > JPK_MAX_BLOCKSIZE || psize < 0 || psize > JPK_MAX_BLOCKSIZE ||
-            (uint64_t)psize > in_len - o - JPK_JAM_HEADER_BYTES) { bad = 1; break; }
+        if (!jrs::magic_ok(h[0], h[1], h[2]) || !jrs::fields_ok(psize, field, (int64_t)(in_len - o), staged_ok != 0)) { bad = 1; break; }
         if (l == 0) {
             JamWalkFrame f;
             f.payload_off = o + JPK_JAM_HEADER_BYTES; f.psize = psize; f.crc = crc; f.block_size = field; f.pad = 0;
@@ -158,6 +159,128 @@ __global__ __launch_bounds__(PACK_TB) void k_jam_gather(const JamGatherPiece *__
     }
 }
 
+// ---- k_jam_scan_count / k_jam_scan_emit: the plausible headers (jrs::magic_ok + jrs::fields_ok) that start in [start, end) -----------
+// A streaming read.  Word w is the aligned 16 bytes at base + 16 w, base = `in` rounded down to 16; a lane loads SCAN_ROWS words per tile,
+// 64 words apart, so a wave's loads are 1 KiB each and a tile is SCAN_TILE = 4 KiB of one wave's own.  A lane tests the 16 offsets of a
+// word for the magic in registers; the two bytes behind its word are the first dword of its neighbour's word (the last lane's: the
+// first lane's next row, and behind the tile one overlapping dword load).  The other 12 header bytes are read only on a magic hit.
+// Only words that hold a byte of the archive are loaded (an aligned word lies in one page), and no offset o with o + 15 > in_len is
+// looked at, so nothing at or behind in + in_len reaches the result; `in` and start may have any alignment.
+// The order comes from position alone: k_jam_scan_count leaves the hits of tile t in counts[t] (ballot + popcount per offset column, and
+// only in a row that has a hit), the host scans them (jpk_dev_exclusive_scan_u32 over ntiles + 1 words), and k_jam_scan_emit walks the
+// tiles that hold a rank below K again and writes candidate r to out[r]: rank = the tile's prefix + the hits of the rows and lanes in
+// front + the hits below in the lane's own word.  No atomics, no LDS; the grid is capped and strides by waves.
+constexpr int SCAN_TB = 256, SCAN_ROWS = 4, SCAN_TILE = SCAN_ROWS * 64 * 16;
+
+// the hits among the 16 offsets of the lane's word x (nxt: the dword behind it); o0 = the archive offset of the word's first byte
+__device__ __forceinline__ uint32_t scan_word(const uint8_t *__restrict__ in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, int64_t o0, uint4 x,
+                                              uint32_t nxt)
+{
+    // offsets [lo, hi) of the word are in the window and leave room for a header
+    const int64_t top = end < in_len - (JPK_JAM_HEADER_BYTES - 1) ? end : in_len - (JPK_JAM_HEADER_BYTES - 1);
+    const int64_t lo64 = start - o0, hi64 = top - o0;
+    if (hi64 <= 0 || lo64 >= 16) return 0u;
+    const uint32_t lo = lo64 < 0 ? 0u : (uint32_t)lo64, hi = hi64 > 16 ? 16u : (uint32_t)hi64;
+    const uint32_t v[5] = {x.x, x.y, x.z, x.w, nxt};
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const uint32_t t = __builtin_amdgcn_alignbyte(v[j / 4 + 1], v[j / 4], j & 3) & 0xFFFFFFu;
+        m |= (t == ('J' | ('A' << 8) | ('M' << 16)) ? 1u : 0u) << j;
+    }
+    m &= (0xFFFFu << lo) & (0xFFFFu >> (16u - hi));
+    uint32_t hits = 0;
+    while (m) {                                                                // rare: a magic in the window
+        const uint32_t j = (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+        const uint8_t *h = in + (o0 + j);
+        const int32_t psize = (int32_t)((uint32_t)h[7] | ((uint32_t)h[8] << 8) | ((uint32_t)h[9] << 16) | ((uint32_t)h[10] << 24));
+        const int32_t field = (int32_t)((uint32_t)h[11] | ((uint32_t)h[12] << 8) | ((uint32_t)h[13] << 16) | ((uint32_t)h[14] << 24));
+        if (jrs::fields_ok(psize, field, in_len - (o0 + j), staged_ok)) hits |= 1u << j;
+    }
+    return hits;
+}
+
+template <bool EMIT>
+__device__ __forceinline__ void scan_tiles(const uint8_t *__restrict__ in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, uint32_t ntiles,
+                                           uint32_t *__restrict__ counts, JamWalkFrame *__restrict__ out, uint32_t K)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * SCAN_TB + threadIdx.x) >> 6, nwaves = gridDim.x * (SCAN_TB / 64);
+    const int64_t lead = (int64_t)((uintptr_t)in & 15u);
+    const uint8_t *base = in - lead;
+    const int64_t w_lo = (lead + start) >> 4, w_hi = (lead + in_len + 15) >> 4;   // the window's first word; the words with a byte of the archive
+    for (uint32_t tile = wave; tile < ntiles; tile += nwaves) {                    // (wave-uniform)
+        uint32_t rank = 0;
+        if (EMIT) {
+            rank = (uint32_t)__builtin_amdgcn_readfirstlane((int)counts[tile]);
+            const uint32_t next = (uint32_t)__builtin_amdgcn_readfirstlane((int)counts[tile + 1]);
+            if (next == rank || rank >= K) continue;
+        }
+        const int64_t w0 = w_lo + (int64_t)tile * (SCAN_ROWS * 64) + lane;
+        uint4 x[SCAN_ROWS];
+#pragma unroll
+        for (int u = 0; u < SCAN_ROWS; u++) {
+            const int64_t w = w0 + u * 64;
+            x[u] = make_uint4(0u, 0u, 0u, 0u);
+            if (w < w_hi) x[u] = *reinterpret_cast<const uint4 *>(base + w * 16);
+        }
+        uint32_t behind = 0;                                                       // the dword behind the tile, for its last lane
+        if (lane == 63u && w0 + (SCAN_ROWS - 1) * 64 + 1 < w_hi) behind = *reinterpret_cast<const uint32_t *>(base + (w0 + (SCAN_ROWS - 1) * 64 + 1) * 16);
+        uint32_t total = 0;
+#pragma unroll
+        for (int u = 0; u < SCAN_ROWS; u++) {
+            uint32_t nxt = (uint32_t)__shfl_down((int)x[u].x, 1);
+            const uint32_t row_next = (uint32_t)__builtin_amdgcn_readfirstlane((int)x[(u + 1) % SCAN_ROWS].x);   // the first lane's word of the next row
+            if (lane == 63u) nxt = u + 1 < SCAN_ROWS ? row_next : behind;
+            const int64_t o0 = (w0 + u * 64) * 16 - lead;
+            const uint32_t hits = scan_word(in, in_len, start, end, staged_ok, o0, x[u], nxt);
+            if (__ballot(hits != 0u) == 0ull) continue;                           // (wave-uniform)
+            uint32_t before = 0, row = 0;                                          // hits of the lanes in front; of the row
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const uint64_t b = __ballot((hits >> j) & 1u);
+                before += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+                row += (uint32_t)__popcll(b);
+            }
+            if (EMIT) {
+                uint32_t m = hits, r = rank + total + before;
+                while (m) {
+                    const uint32_t j = (uint32_t)__builtin_ctz(m);
+                    m &= m - 1u;
+                    if (r < K) {
+                        const uint8_t *h = in + (o0 + j);
+                        JamWalkFrame f;
+                        f.payload_off = (uint64_t)(o0 + j) + JPK_JAM_HEADER_BYTES;
+                        f.crc = (uint32_t)h[3] | ((uint32_t)h[4] << 8) | ((uint32_t)h[5] << 16) | ((uint32_t)h[6] << 24);
+                        f.psize = (int32_t)((uint32_t)h[7] | ((uint32_t)h[8] << 8) | ((uint32_t)h[9] << 16) | ((uint32_t)h[10] << 24));
+                        f.block_size = (int32_t)((uint32_t)h[11] | ((uint32_t)h[12] << 8) | ((uint32_t)h[13] << 16) | ((uint32_t)h[14] << 24));
+                        f.pad = 0;
+                        out[r] = f;
+                    }
+                    r++;
+                }
+            }
+            total += row;
+        }
+        if (!EMIT && lane == 0u) counts[tile] = total;
+    }
+    if (!EMIT && blockIdx.x == 0 && threadIdx.x == 0) counts[ntiles] = 0u;        // the scan's last word: its prefix is the total
+}
+
+__global__ __launch_bounds__(SCAN_TB) void k_jam_scan_count(const uint8_t *__restrict__ in, int64_t in_len, int64_t start, int64_t end, uint32_t staged_ok,
+                                                            uint32_t ntiles, uint32_t *__restrict__ counts)
+{
+    scan_tiles<false>(in, in_len, start, end, staged_ok != 0u, ntiles, counts, nullptr, 0u);
+}
+
+// counts: the exclusive prefix sums of k_jam_scan_count's, ntiles + 1 words
+__global__ __launch_bounds__(SCAN_TB) void k_jam_scan_emit(const uint8_t *__restrict__ in, int64_t in_len, int64_t start, int64_t end, uint32_t staged_ok,
+                                                           uint32_t ntiles, uint32_t *__restrict__ counts, JamWalkFrame *__restrict__ out, uint32_t K)
+{
+    scan_tiles<true>(in, in_len, start, end, staged_ok != 0u, ntiles, counts, out, K);
+}
+
 }  // namespace
 
 int jpk_jam_walk_enqueue(jpk_ctx *ctx, const uint8_t *d_in, uint64_t in_len, uint64_t start, uint32_t max_frames, JamWalkFrame *d_table,
@@ -186,6 +309,38 @@ int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_
     uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
     if (grid > 8192) grid = 8192;                                              // grid-stride beyond, as k_jam_pack
     JPK_LAUNCH(ctx, PROF_JAM, bytes, k_jam_gather, dim3((unsigned)grid), dim3(PACK_TB), d_pieces, n, words);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
+
+uint32_t jpk_jam_scan_tiles(const uint8_t *d_in, int64_t start, int64_t end)
+{
+    const int64_t lead = (int64_t)((uintptr_t)d_in & 15u);
+    const int64_t words = ((lead + end + 15) >> 4) - ((lead + start) >> 4);
+    return (uint32_t)((words * 16 + SCAN_TILE - 1) / SCAN_TILE);
+}
+
+static unsigned scan_grid(uint32_t ntiles)
+{
+    const uint32_t blocks = (ntiles + SCAN_TB / 64 - 1) / (SCAN_TB / 64);
+    return blocks > 2048u ? 2048u : blocks;                                        // waves stride over the tiles beyond
+}
+
+int jpk_jam_scan_count_enqueue(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, uint32_t *d_counts)
+{
+    const uint32_t ntiles = jpk_jam_scan_tiles(d_in, start, end);
+    JPK_LAUNCH(ctx, PROF_JAM_SCAN, end - start, k_jam_scan_count, dim3(scan_grid(ntiles)), dim3(SCAN_TB), d_in, in_len, start, end, staged_ok ? 1u : 0u, ntiles,
+               d_counts);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
+
+int jpk_jam_scan_emit_enqueue(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, uint32_t *d_counts,
+                              JamWalkFrame *d_out, uint32_t max_cands)
+{
+    const uint32_t ntiles = jpk_jam_scan_tiles(d_in, start, end);
+    JPK_LAUNCH(ctx, PROF_JAM_SCAN, 0, k_jam_scan_emit, dim3(scan_grid(ntiles)), dim3(SCAN_TB), d_in, in_len, start, end, staged_ok ? 1u : 0u, ntiles, d_counts,
+               d_out, max_cands);
     JPK_HIP(hipGetLastError());
     return JPK_OK;
 }

@@ -1,11 +1,14 @@
 // jam_archive.hip -- whole .jam archives of the C ABI (include/jampack_abi.h): the frame walks, the batched compress and decompress
-// calls of plain and stock-CLI archives with their host-buffer forms, and the index + range reads.  Host drivers only: the kernels
+// calls of plain and stock-CLI archives with their host-buffer forms, the index + range reads, and the index and the salvage of damaged
+// archives (the rule they share with the kernels: jam_resync.hpp).  Host drivers only: the kernels
 // are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines and the context pool in abi.hip.
 #include <algorithm>
+#include <atomic>
 #include <new>
 #include <vector>
 
 #include "common.hpp"
+#include "jam_resync.hpp"
 
 // ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
 // Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
@@ -23,9 +26,7 @@
 // The writer of staged frames (jpk_dev_jam_staged_compress; DESIGN 4.6, "Staged frames") is that pass with the chain stopped at S2: no k_enc_lpx,
 // the A slots are the batch's inputs, and the pack writes BlockSize | JPK_JAM_STAGED.  Its reader takes plain and staged frames in one archive.
 
-// one frame of an archive as the walks see it: where its payload is, its header fields and its raw (decompressed) size
-// (staged: a staged frame, DESIGN 4.6 -- block_size is the field without JPK_JAM_STAGED, raw the bytes of its S2)
-struct JamFrame { int64_t payload_off; int32_t psize; uint32_t crc; int32_t block_size; int64_t raw; bool staged = false; };
+// (JamFrame, one frame of an archive as the walks see it, and the checks a walk applies to it: jam_resync.hpp)
 
 namespace {
 constexpr uint64_t JAM_PASS_RAW = 4ull << 30;
@@ -38,28 +39,11 @@ int jam_pass_frames(int32_t block_size)
     return k < (uint64_t)JPK_JAM_PASS_FRAMES ? (int)k : JPK_JAM_PASS_FRAMES;
 }
 
-// the checks of the frame walk beyond its header (k_jam_walk / jam_walk_host): the payload declares at least the BWT trailer and at
-// most BlockSize raw bytes (the reference decodes into buffers of 1.05 x BlockSize, jampack.cpp:156-159) -- for a frame of the stock
-// CLI, whose entropy-decoded bytes are the output of its pre-stages (filter headers and LZ tokens add bytes), at most the reference's
-// stage buffers, 1.05 x BlockSize + 4096 (jampack.cpp:156), as jpk_jam_cli_block_read has them
-int32_t jam_cli_cap(int32_t block_size) { return (int32_t)((int64_t)((double)block_size * 1.05) + 4096); }
-bool jam_decoded_ok(int64_t decoded, int32_t block_size, bool cli)
-{
-    return decoded >= JPK_TRAILER_BYTES && decoded - JPK_TRAILER_BYTES <= (cli ? jam_cli_cap(block_size) : block_size);
-}
+// the slots of a frame that goes through pre-stage decoders: the reference's stage buffers, 1.05 x BlockSize + 4096 (jampack.cpp:156)
+int32_t jam_cli_cap(int32_t block_size) { return jrs::cli_cap(block_size); }
 
-// jpk_jam_header_parse with JPK_JAM_STAGED allowed (staged_ok) in a BlockSize field whose bit 31 is clear: f's header fields
-bool jam_header_parse(const uint8_t *h, int64_t avail, bool staged_ok, JamFrame *f)
-{
-    if (avail < JPK_JAM_HEADER_BYTES) return false;
-    uint8_t c[JPK_JAM_HEADER_BYTES];
-    memcpy(c, h, sizeof c);
-    f->staged = staged_ok && (c[14] & 0xC0u) == 0x40u;                 // the field is little-endian: byte 14 holds bits 24-31
-    if (f->staged) c[14] &= 0xBFu;
-    return jpk_jam_header_parse(c, avail, &f->crc, &f->psize, &f->block_size);
-}
-
-// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none); JAM_CLI: frames of the
+// host walk of an archive in host memory: the frames in front of the first bad one (*bad = its index, -1: none) -- a bad header (1..14
+// trailing bytes are one), bad chunk headers in the payload, or a payload that declares too much (jrs::frame_at); JAM_CLI: frames of the
 // stock CLI, f.raw = the entropy-decoded bytes (the input of the pre-stage decoders), and so for the staged frames of JAM_STAGED
 void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN)
 {
@@ -67,31 +51,26 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
     int64_t o = 0;
     while (o < in_len) {
         JamFrame f;
-        f.payload_off = o + JPK_JAM_HEADER_BYTES;
-        int64_t decoded = 0;
-        // a bad header (1..14 trailing bytes are one), bad chunk headers in the payload, or a payload that declares too much
-        if (!jam_header_parse(in + o, in_len - o, kind == JAM_STAGED, &f) ||
-            jpk_ans_decoded_size(in + f.payload_off, f.psize, &decoded, nullptr) != JPK_OK || !jam_decoded_ok(decoded, f.block_size, kind == JAM_CLI || f.staged)) {
-            *bad = (int32_t)fr.size();
-            return;
-        }
-        f.raw = decoded - JPK_TRAILER_BYTES;
+        if (!jrs::frame_at(in, in_len, o, kind == JAM_STAGED, kind == JAM_CLI, &f)) { *bad = (int32_t)fr.size(); return; }
         fr.push_back(f);
         o = f.payload_off + f.psize;
     }
 }
 
-// the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch
-int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN)
+// the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch.  It starts at
+// offset `start`; *stop (nullable) = the offset of the frame it stopped at, in_len when it reached the end
+int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN, int64_t start = 0,
+                 int64_t *stop = nullptr)
 {
     *bad = -1;
+    if (stop) *stop = in_len;
     JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * sizeof(JamWalkFrame)));
     JamWalkFrame *d_tab = reinterpret_cast<JamWalkFrame *>(ctx->jam_scratch);
     std::vector<JamWalkFrame> h(JPK_JAM_PASS_FRAMES);
     std::vector<const uint8_t *> ins;
     std::vector<int32_t> lens, st;
     std::vector<int64_t> dec;
-    uint64_t o = 0;
+    uint64_t o = (uint64_t)start;
     while (o < (uint64_t)in_len) {
         JPK_TRY(jpk_jam_walk_enqueue(ctx, d_in, (uint64_t)in_len, o, JPK_JAM_PASS_FRAMES, d_tab, ctx->d_mail->read, kind == JAM_STAGED));
         JPK_HIP(hipMemcpyAsync(h.data(), d_tab, h.size() * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
@@ -104,11 +83,15 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
         for (int i = 0; i < n; i++) {
             const bool staged = (h[i].block_size & JPK_JAM_STAGED) != 0;       // (only a walk with staged_ok lets such a field through)
             const int32_t bs = h[i].block_size & ~JPK_JAM_STAGED;
-            if (st[i] != JPK_OK || !jam_decoded_ok(dec[i], bs, kind == JAM_CLI || staged)) { *bad = (int32_t)fr.size(); return JPK_OK; }
+            if (st[i] != JPK_OK || !jrs::decoded_ok(dec[i], bs, kind == JAM_CLI || staged)) {
+                *bad = (int32_t)fr.size();
+                if (stop) *stop = (int64_t)h[i].payload_off - JPK_JAM_HEADER_BYTES;
+                return JPK_OK;
+            }
             fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, bs, dec[i] - JPK_TRAILER_BYTES, staged});
         }
-        if (m[1]) { *bad = (int32_t)fr.size(); return JPK_OK; }
         o = ((uint64_t)m[3] << 32) | m[2];
+        if (m[1]) { *bad = (int32_t)fr.size(); if (stop) *stop = (int64_t)o; return JPK_OK; }
     }
     return JPK_OK;
 }
@@ -434,6 +417,10 @@ struct jpk_jam_index {
     int32_t bad = -1;
     int32_t kind = JPK_JAM_INDEX_PLAIN;    // JPK_JAM_INDEX_CLI: frames of the stock CLI, fr[k].raw from a decode (jam_cli_decode)
                                            // JPK_JAM_INDEX_STAGED: plain and staged frames (fr[k].staged), a staged one's raw from its token walk or a decode
+    // what a recovered index skipped (jpk_(dev_)jam_index_recover), in archive order: `frame` recovered frames lie in front of the gap; with
+    // the frames' spans [payload_off - 15, payload_off + psize) the gaps tile [0, archive_len).  Empty for every other creator.
+    struct Gap { int64_t archive_off, archive_len; int32_t frame, why; };
+    std::vector<Gap> gaps;
 };
 
 namespace {
@@ -1152,49 +1139,60 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
 }
 
 namespace {
-// The frames of an index of kind JPK_JAM_INDEX_STAGED for an archive in HBM: the walk, then per pass (the limits of
-// jpk_dev_jam_staged_decompress) the staged frames through jam_cli_pass without an output -- verify: the whole staged stage list and the
-// header crcs; otherwise its sizes form, which stops in front of the expansion.  Plain frames keep the raw size of the walk and are not
-// decoded.  done = the frames in front of the first bad one, *bad = its position (-1: none).
+// The staged frames among fr[k, e) (one pass: the limits of jpk_dev_jam_staged_decompress) through jam_cli_pass without an output -- verify:
+// the whole staged stage list and the header crcs; otherwise its sizes form, which stops in front of the expansion.  The payload of a frame
+// is at d_in + (payload_off - a0).  st[i - k] = JPK_OK and fr[i].raw = its raw size, or the status of the stage it failed (prefix: also of
+// every staged frame behind the first failing one); a plain frame keeps the raw size of the walk, is not decoded and is JPK_OK.
+int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool verify, bool prefix, int32_t *st)
+{
+    const size_t o_slots = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    std::vector<size_t> sidx, slot;
+    std::vector<const uint8_t *> sin;
+    std::vector<int32_t> slens, caps, bsz;
+    std::vector<uint32_t> scrc;
+    size_t need = o_slots;
+    for (size_t i = k; i < e; i++) {
+        const JamFrame &f = fr[i];
+        st[i - k] = JPK_OK;
+        if (!f.staged) continue;
+        sidx.push_back(i);
+        sin.push_back(d_in + (f.payload_off - a0)); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
+        caps.push_back(jam_cli_cap(f.block_size));
+        slot.push_back(jpk_align((size_t)caps.back() + 64));
+        need += 2 * slot.back();
+    }
+    const size_t ns = sidx.size();
+    if (!ns) return JPK_OK;
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
+    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    std::vector<uint8_t *> a(ns), b(ns);
+    size_t off = o_slots;
+    for (size_t q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
+    std::vector<int32_t> sraw(ns), sst(ns);
+    // a frame that declares more than its BlockSize is a bad frame, expanded or not
+    JPK_TRY(jam_cli_pass(ctx, CliPass{(int)ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, prefix, false,
+                                      true, !verify},
+                         sraw.data(), sst.data()));
+    for (size_t q = 0; q < ns; q++) {
+        st[sidx[q] - k] = sst[q];
+        if (sst[q] == JPK_OK) fr[sidx[q]].raw = sraw[q];
+    }
+    return JPK_OK;
+}
+
+// The frames of an index of kind JPK_JAM_INDEX_STAGED for an archive in HBM: the walk, then jam_staged_size_pass per pass.
+// done = the frames in front of the first bad one, *bad = its position (-1: none).
 int jam_staged_sizes(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, bool verify, std::vector<JamFrame> &done, int32_t *bad)
 {
     std::vector<JamFrame> fr;
     JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, bad, JAM_STAGED));
-    const size_t o_slots = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
+    std::vector<int32_t> st;
     for (size_t k = 0; k < fr.size();) {
         const size_t e = jam_pass_end(fr, k, false);
-        std::vector<size_t> sidx, slot;
-        std::vector<const uint8_t *> sin;
-        std::vector<int32_t> slens, caps, bsz;
-        std::vector<uint32_t> scrc;
-        size_t need = o_slots;
-        for (size_t i = k; i < e; i++) {
-            const JamFrame &f = fr[i];
-            if (!f.staged) continue;
-            sidx.push_back(i);
-            sin.push_back(d_in + f.payload_off); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
-            caps.push_back(jam_cli_cap(f.block_size));
-            slot.push_back(jpk_align((size_t)caps.back() + 64));
-            need += 2 * slot.back();
-        }
-        const size_t ns = sidx.size();
-        size_t stop = e;
-        if (ns) {
-            JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-            uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-            std::vector<uint8_t *> a(ns), b(ns);
-            size_t off = o_slots;
-            for (size_t q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
-            std::vector<int32_t> sraw(ns), sst(ns);
-            // a frame that declares more than its BlockSize is a bad frame, expanded or not
-            JPK_TRY(jam_cli_pass(ctx, CliPass{(int)ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, true, false,
-                                              true, !verify},
-                                 sraw.data(), sst.data()));
-            for (size_t q = 0; q < ns; q++) {
-                if (sst[q] != JPK_OK) { stop = sidx[q]; break; }
-                fr[sidx[q]].raw = sraw[q];
-            }
-        }
+        st.resize(e - k);
+        JPK_TRY(jam_staged_size_pass(ctx, d_in, 0, fr, k, e, verify, true, st.data()));
+        size_t stop = k;
+        while (stop < e && st[stop - k] == JPK_OK) stop++;
         done.insert(done.end(), fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)stop);
         if (stop < e) { *bad = (int32_t)stop; return JPK_OK; }
         k = e;
@@ -1330,4 +1328,322 @@ extern "C" int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64
             if (len[r] > 0 && st[(size_t)r] == JPK_OK) memcpy(out[r], all.data() + (d_out[(size_t)r] - ctx->stage_res), (size_t)len[r]);
     }
     return jam_read_result(n, st.data(), status);
+}
+
+// ---- damaged archives: an index past the damage, and everything recoverable ("Damaged archives") ------------------------
+// jpk_(dev_)jam_index_recover run the resync walk of jam_resync.hpp -- one loop for both forms, over JamDevSrc or jrs::HostSrc: where
+// the frame walk stops, the first structurally valid frame behind it is searched (in HBM: k_jam_scan_* for the plausible headers of a
+// window, jpk_ans_decoded_sizes for a batch of them), and what lies between becomes a gap of the index.  An undamaged archive is one run
+// of the frame walk and launches no scan.  jpk_(dev_)jam_salvage is one range per frame through the reader above.
+namespace {
+std::atomic<int64_t> g_recover_window{jrs::DEFAULT_WINDOW};
+std::atomic<int32_t> g_recover_cands{jrs::DEFAULT_CANDS};
+constexpr int64_t JAM_SCAN_MAX_WINDOW = 1ll << 30;      // tiles and their prefix sums stay 32-bit
+constexpr int32_t JAM_SCAN_MAX_CANDS = 1 << 16;
+
+// the first max_cands plausible headers that start in [start, end) of an archive in HBM, ascending: count, scan, emit, one read-back.
+// Scratch: a word per tile and max_cands table entries in ctx->jam_scratch
+int jam_scan_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t end, bool staged_ok, int32_t max_cands, std::vector<JamWalkFrame> &out)
+{
+    out.clear();
+    if (start >= end) return JPK_OK;
+    const uint32_t ntiles = jpk_jam_scan_tiles(d_in, start, end);
+    const size_t o_cands = jpk_align(((size_t)ntiles + 1) * 4);
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, o_cands + (size_t)max_cands * sizeof(JamWalkFrame)));
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    JamWalkFrame *d_cands = reinterpret_cast<JamWalkFrame *>(ctx->jam_scratch + o_cands);
+    JPK_TRY(jpk_jam_scan_count_enqueue(ctx, d_in, in_len, start, end, staged_ok, d_counts));
+    uint32_t total = 0;
+    JPK_TRY(jpk_dev_exclusive_scan_u32(ctx, d_counts, (int32_t)ntiles + 1, &total));     // synchronises
+    const size_t n = std::min<size_t>(total, (size_t)max_cands);
+    if (n) {
+        out.resize(n);
+        JPK_TRY(jpk_jam_scan_emit_enqueue(ctx, d_in, in_len, start, end, staged_ok, d_counts, d_cands, (uint32_t)max_cands));
+        JPK_HIP(hipMemcpyAsync(out.data(), d_cands, n * sizeof(JamWalkFrame), hipMemcpyDeviceToHost, ctx->stream));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (ctx->prof_on) jpk_prof_resolve(ctx);
+    return JPK_OK;
+}
+
+// jrs::walk's source for an archive in HBM
+struct JamDevSrc {
+    jpk_ctx *ctx;
+    const uint8_t *d_in;
+    int64_t in_len;
+    int kind;                                         // JAM_PLAIN or JAM_STAGED
+    std::vector<JamWalkFrame> c;                      // the candidates of the last cands()
+    template <class OnFrame> int run(int64_t g, OnFrame on_frame, int64_t *stop)
+    {
+        std::vector<JamFrame> fr;
+        int32_t bad = -1;
+        JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, kind, g, stop));
+        for (const JamFrame &f : fr) on_frame(f);
+        return JPK_OK;
+    }
+    int cands(int64_t from, int64_t to, int32_t K, int32_t *n)
+    {
+        JPK_TRY(jam_scan_dev(ctx, d_in, in_len, from, to, kind == JAM_STAGED, K, c));
+        *n = (int32_t)c.size();
+        return JPK_OK;
+    }
+    int64_t cand(int32_t i) const { return (int64_t)c[(size_t)i].payload_off - JPK_JAM_HEADER_BYTES; }
+    int first_valid(int32_t n, int32_t *hit, JamFrame *f)
+    {
+        std::vector<const uint8_t *> ins((size_t)n);
+        std::vector<int32_t> lens((size_t)n), st((size_t)n);
+        std::vector<int64_t> dec((size_t)n);
+        for (int32_t i = 0; i < n; i++) { ins[(size_t)i] = d_in + c[(size_t)i].payload_off; lens[(size_t)i] = c[(size_t)i].psize; }
+        JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
+        *hit = -1;
+        for (int32_t i = 0; i < n && *hit < 0; i++) {
+            const JamWalkFrame &w = c[(size_t)i];
+            const bool staged = (w.block_size & JPK_JAM_STAGED) != 0;            // (only a scan with staged_ok lets such a field through)
+            const int32_t bs = w.block_size & ~JPK_JAM_STAGED;
+            if (st[(size_t)i] != JPK_OK || !jrs::decoded_ok(dec[(size_t)i], bs, staged)) continue;
+            *f = JamFrame{(int64_t)w.payload_off, w.psize, w.crc, bs, dec[(size_t)i] - JPK_TRAILER_BYTES, staged};
+            *hit = i;
+        }
+        return JPK_OK;
+    }
+};
+
+using JamGap = jpk_jam_index::Gap;
+
+// the resync walk of either form: the frames it found and the gaps between them (why = JPK_JAM_GAP_NOFRAME)
+template <class Src> int jam_recover_walk(Src &src, int64_t in_len, std::vector<JamFrame> &fr, std::vector<JamGap> &gaps)
+{
+    return jrs::walk(src, in_len, g_recover_window.load(), g_recover_cands.load(), [&](const JamFrame &f) { fr.push_back(f); },
+                     [&](int64_t o, int64_t n) { gaps.push_back(JamGap{o, n, (int32_t)fr.size(), JPK_JAM_GAP_NOFRAME}); });
+}
+
+// frames [k, e) form the sizing pass that starts at frame k: the limits of jam_pass_end, and frames that lie back to back in the
+// archive -- a pass never spans a gap, so the host form can stage it as one piece
+size_t jam_recover_pass_end(const std::vector<JamFrame> &fr, size_t k)
+{
+    const size_t lim = jam_pass_end(fr, k, false);
+    size_t e = k + 1;
+    while (e < lim && fr[e].payload_off - JPK_JAM_HEADER_BYTES == fr[e - 1].payload_off + fr[e - 1].psize) e++;
+    return e;
+}
+
+// what the index holds: frames whose status is JPK_OK, every other one a gap over its own span (why = JPK_JAM_GAP_STAGE) among the
+// gaps of the walk, and `frame` of every gap counted in the frames that stay
+jpk_jam_index *jam_recover_make(const std::vector<JamFrame> &fr, const std::vector<int32_t> &st, const std::vector<JamGap> &gaps, int64_t in_len, int32_t kind)
+{
+    std::vector<JamFrame> keep;
+    std::vector<JamGap> all;
+    size_t gi = 0;
+    for (size_t i = 0; i <= fr.size(); i++) {
+        for (; gi < gaps.size() && (size_t)gaps[gi].frame == i; gi++) all.push_back(JamGap{gaps[gi].archive_off, gaps[gi].archive_len, (int32_t)keep.size(), gaps[gi].why});
+        if (i == fr.size()) break;
+        if (st[i] == JPK_OK) keep.push_back(fr[i]);
+        else all.push_back(JamGap{fr[i].payload_off - JPK_JAM_HEADER_BYTES, (int64_t)JPK_JAM_HEADER_BYTES + fr[i].psize, (int32_t)keep.size(), JPK_JAM_GAP_STAGE});
+    }
+    jpk_jam_index *ix = jam_index_make(keep, in_len, -1, kind);
+    if (ix) ix->gaps = std::move(all);
+    return ix;
+}
+
+bool jam_recover_args_ok(const void *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index)
+{
+    // (an index of a stock-CLI archive comes from a decode that stops at a bad frame: not recovered here)
+    return index && in_len >= 0 && (in_len == 0 || in) && (kind == JPK_JAM_INDEX_PLAIN || kind == JPK_JAM_INDEX_STAGED) && jam_verify_ok(verify) &&
+           !(kind == JPK_JAM_INDEX_PLAIN && verify);
+}
+
+int jam_recover_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *ngaps)
+{
+    std::vector<JamFrame> fr;
+    std::vector<JamGap> gaps;
+    std::vector<int32_t> st;
+    if (in_len > 0) {
+        JPK_HIP(hipSetDevice(ctx->device));
+        JamDevSrc src{ctx, d_in, in_len, kind == JPK_JAM_INDEX_STAGED ? JAM_STAGED : JAM_PLAIN, {}};
+        JPK_TRY(jam_recover_walk(src, in_len, fr, gaps));
+        st.assign(fr.size(), JPK_OK);
+        for (size_t k = 0; k < fr.size();) {
+            const size_t e = jam_recover_pass_end(fr, k);
+            JPK_TRY(jam_staged_size_pass(ctx, d_in, 0, fr, k, e, verify != 0, false, st.data() + k));
+            k = e;
+        }
+    }
+    if (!(*index = jam_recover_make(fr, st, gaps, in_len, kind))) return JPK_E_ALLOC;
+    if (ngaps) *ngaps = (int32_t)(*index)->gaps.size();
+    return JPK_OK;
+}
+
+int jam_recover_host(const uint8_t *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *ngaps)
+{
+    std::vector<JamFrame> fr;
+    std::vector<JamGap> gaps;
+    const int32_t K = g_recover_cands.load();
+    std::vector<int64_t> offs((size_t)(K < 1 ? jrs::DEFAULT_CANDS : K));
+    jrs::HostSrc src{in, in_len, kind == JPK_JAM_INDEX_STAGED, offs.data()};
+    JPK_TRY(jam_recover_walk(src, in_len, fr, gaps));
+    std::vector<int32_t> st(fr.size(), JPK_OK);
+    // an archive without a staged frame is indexed by the walk alone: no device is looked for
+    jpk_ctx *ctx = nullptr;
+    if (std::any_of(fr.begin(), fr.end(), [](const JamFrame &f) { return f.staged; })) JPK_TRY(jpk_host_enter(&ctx, 0));
+    for (size_t k = 0; k < fr.size();) {
+        const size_t e = jam_recover_pass_end(fr, k);
+        if (std::any_of(fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e, [](const JamFrame &f) { return f.staged; })) {
+            // staged one pass at a time, as jpk_jam_staged_index_create: the pass's frames lie back to back
+            const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
+            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
+            JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+            const int rc = jam_staged_size_pass(ctx, ctx->stage_in, a0, fr, k, e, verify != 0, false, st.data() + k);
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+            JPK_TRY(rc);
+        }
+        k = e;
+    }
+    if (!(*index = jam_recover_make(fr, st, gaps, in_len, kind))) return JPK_E_ALLOC;
+    if (ngaps) *ngaps = (int32_t)(*index)->gaps.size();
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_index_recover(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps)
+{
+    // (the argument checks come before the first device call, and an empty archive makes none)
+    if (!ctx || !jam_recover_args_ok(d_in, in_len, kind, verify, index)) return JPK_E_ARG;
+    *index = nullptr;
+    try {
+        return jam_recover_dev(ctx, d_in, in_len, kind, verify, index, gaps);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_jam_index_recover(const uint8_t *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps)
+{
+    if (!jam_recover_args_ok(in, in_len, kind, verify, index)) return JPK_E_ARG;
+    *index = nullptr;
+    try {
+        return jam_recover_host(in, in_len, kind, verify, index, gaps);
+    } catch (const std::bad_alloc &) {
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_jam_index_gaps(const jpk_jam_index *index) { return index ? (int)index->gaps.size() : JPK_E_ARG; }
+
+extern "C" int jpk_jam_index_gap(const jpk_jam_index *index, int32_t g, int64_t *archive_off, int64_t *archive_len, int32_t *frame, int32_t *why)
+{
+    if (!index || g < 0 || (size_t)g >= index->gaps.size()) return JPK_E_ARG;
+    const JamGap &x = index->gaps[(size_t)g];
+    if (archive_off) *archive_off = x.archive_off;
+    if (archive_len) *archive_len = x.archive_len;
+    if (frame) *frame = x.frame;
+    if (why) *why = x.why;
+    return JPK_OK;
+}
+
+extern "C" int jpk_debug_jam_scan(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int64_t start, int64_t window, int32_t staged_ok, int32_t max_cands,
+                                  int64_t *offsets, int32_t *count)
+{
+    if (!ctx || !count || in_len < 0 || (in_len > 0 && !d_in) || start < 0 || start > in_len || window < 0 || window > JAM_SCAN_MAX_WINDOW || max_cands < 1 ||
+        max_cands > JAM_SCAN_MAX_CANDS || !offsets)
+        return JPK_E_ARG;
+    JPK_HIP(hipSetDevice(ctx->device));
+    *count = 0;
+    try {
+        std::vector<JamWalkFrame> c;
+        JPK_TRY(jam_scan_dev(ctx, d_in, in_len, start, std::min(in_len, start + window), staged_ok != 0, max_cands, c));
+        for (size_t i = 0; i < c.size(); i++) offsets[i] = (int64_t)c[i].payload_off - JPK_JAM_HEADER_BYTES;
+        *count = (int32_t)c.size();
+    } catch (const std::bad_alloc &) {
+        return JPK_E_ALLOC;
+    }
+    return JPK_OK;
+}
+
+// test hook (JPK_DEBUG_HOOKS=1 only): the window and the candidates per round of the resync search of this process; 0, 0: the defaults
+extern "C" int jpk_debug_jam_recover_limits(int64_t window, int32_t max_cands)
+{
+    if (jpk_env_long("JPK_DEBUG_HOOKS", 0) == 0) return JPK_E_ARG;
+    if (window < 0 || window > JAM_SCAN_MAX_WINDOW || max_cands < 0 || max_cands > JAM_SCAN_MAX_CANDS) return JPK_E_ARG;
+    g_recover_window.store(window ? window : jrs::DEFAULT_WINDOW);
+    g_recover_cands.store(max_cands ? max_cands : jrs::DEFAULT_CANDS);
+    return JPK_OK;
+}
+
+namespace {
+// the checks of both salvage entries, and the capacity answer: nothing is touched before they pass
+int jam_salvage_check(const jpk_jam_index *ix, const void *in, int64_t in_len, const void *out, int64_t out_cap, int64_t *out_len)
+{
+    if (!ix || !out_len || in_len != ix->archive_len || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    *out_len = ix->raw_off.back();
+    return *out_len > out_cap ? JPK_E_CAPACITY : JPK_OK;
+}
+
+// one range per frame that has bytes -- every frame whole inside its range, so it decodes in its place -- through the reader's passes, then
+// zeros where a frame failed.  The archive is d_in or (NULL) h_in, as in jam_read_run; d_out holds raw_len bytes
+int jam_salvage_run(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, const uint8_t *h_in, uint8_t *d_out, int32_t *frame_status, int32_t *failed)
+{
+    const size_t F = ix->fr.size();
+    std::vector<int64_t> off, len;
+    std::vector<uint8_t *> outs;
+    std::vector<size_t> of;
+    for (size_t k = 0; k < F; k++) {
+        if (frame_status) frame_status[k] = JPK_OK;
+        if (ix->fr[k].raw == 0) continue;                     // no range touches it: reported JPK_OK, not verified
+        of.push_back(k); off.push_back(ix->raw_off[k]); len.push_back(ix->fr[k].raw); outs.push_back(d_out + ix->raw_off[k]);
+    }
+    int32_t nfail = 0;
+    if (!of.empty()) {
+        std::vector<int32_t> st(of.size());
+        JPK_TRY(jam_read_run(ctx, ix, d_in, h_in, (int32_t)of.size(), off.data(), len.data(), outs.data(), st.data(), nullptr));
+        for (size_t r = 0; r < of.size(); r++) {
+            if (st[r] == JPK_OK) continue;
+            nfail++;
+            if (frame_status) frame_status[of[r]] = JPK_E_CORRUPT;
+            JPK_HIP(hipMemsetAsync(outs[r], 0, (size_t)len[r], ctx->stream));
+        }
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (failed) *failed = nfail;
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_salvage(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                   int32_t *frame_status, int32_t *failed)
+{
+    // (the argument checks and the capacity answer come before the first device call)
+    if (!ctx) return JPK_E_ARG;
+    JPK_TRY(jam_salvage_check(index, d_in, in_len, d_out, out_cap, out_len));
+    JPK_HIP(hipSetDevice(ctx->device));
+    try {
+        return jam_salvage_run(ctx, index, d_in, nullptr, d_out, frame_status, failed);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_jam_salvage(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frame_status,
+                               int32_t *failed)
+{
+    JPK_TRY(jam_salvage_check(index, in, in_len, out, out_cap, out_len));
+    const int64_t raw_len = *out_len;
+    if (raw_len == 0) {                                       // nothing to decode: no device is looked for
+        for (size_t k = 0; frame_status && k < index->fr.size(); k++) frame_status[k] = JPK_OK;
+        if (failed) *failed = 0;
+        return JPK_OK;
+    }
+    jpk_ctx *ctx;
+    JPK_TRY(jpk_host_enter(&ctx, 0));
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)raw_len + 64));
+    try {
+        JPK_TRY(jam_salvage_run(ctx, index, nullptr, in, ctx->stage_res, frame_status, failed));
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return JPK_E_ALLOC;
+    }
+    JPK_HIP(hipMemcpyAsync(out, ctx->stage_res, (size_t)raw_len, hipMemcpyDeviceToHost, ctx->stream));
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    return JPK_OK;
 }
