@@ -16,7 +16,8 @@
 // walk (k_jam_walk, one launch + one read-back per JPK_JAM_PASS_FRAMES frames) and the decoded sizes (pass 1 of the batch decoder)
 // over the whole archive first -- that is what makes the capacity answer exact and leaves d_out untouched when it is too small --
 // then per pass jpk_dev_blocks_decompress with every frame decoded in place in d_out (its payload read in place in the archive),
-// one batched checksum of the outputs, and the comparison with the header crcs.  A pass holds at most JPK_JAM_PASS_FRAMES frames
+// one batched checksum of the outputs, and the comparison with the header crcs (jam_plain_group; the pass loop is jam_decode, which
+// the stock-CLI and the staged archives share: a plain archive is its pass without a chained frame).  A pass holds at most JPK_JAM_PASS_FRAMES frames
 // and JAM_PASS_RAW raw bytes, which bounds the scratch of both directions for archives of any length.
 // The stock-CLI writer (jpk_dev_jam_cli_compress) is the same pass with the stage chain in front of the batch compress: k_enc_wrap from
 // the raw slices into a slot A per frame, k_enc_lpx from A into a slot B, and the B slots are the batch's inputs; the crcs stay those
@@ -57,6 +58,17 @@ void jam_walk_host(const uint8_t *in, int64_t in_len, std::vector<JamFrame> &fr,
     }
 }
 
+// a header the walk kernel or the scan found, with the status and the bytes of its payload from jpk_ans_decoded_sizes: the frame as the
+// host walk gives it, or false -- the payload has bad chunk headers or declares too much (cli: measured against the slot of a chained frame)
+bool jam_frame_of(const JamWalkFrame &w, int32_t st, int64_t dec, bool cli, JamFrame *f)
+{
+    const bool staged = (w.block_size & JPK_JAM_STAGED) != 0;       // (only a walk or a scan with staged_ok lets such a field through)
+    const int32_t bs = w.block_size & ~JPK_JAM_STAGED;
+    if (st != JPK_OK || !jrs::decoded_ok(dec, bs, cli || staged)) return false;
+    *f = JamFrame{(int64_t)w.payload_off, w.psize, w.crc, bs, dec - JPK_TRAILER_BYTES, staged};
+    return true;
+}
+
 // the same walk of an archive in HBM: k_jam_walk per JPK_JAM_PASS_FRAMES frames, then their decoded sizes in one launch.  It starts at
 // offset `start`; *stop (nullable) = the offset of the frame it stopped at, in_len when it reached the end
 int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<JamFrame> &fr, int32_t *bad, int kind = JAM_PLAIN, int64_t start = 0,
@@ -81,14 +93,13 @@ int jam_walk_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, std::vector<
         for (int i = 0; i < n; i++) { ins[i] = d_in + h[i].payload_off; lens[i] = h[i].psize; }
         JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
         for (int i = 0; i < n; i++) {
-            const bool staged = (h[i].block_size & JPK_JAM_STAGED) != 0;       // (only a walk with staged_ok lets such a field through)
-            const int32_t bs = h[i].block_size & ~JPK_JAM_STAGED;
-            if (st[i] != JPK_OK || !jrs::decoded_ok(dec[i], bs, kind == JAM_CLI || staged)) {
+            JamFrame f;
+            if (!jam_frame_of(h[i], st[i], dec[i], kind == JAM_CLI, &f)) {
                 *bad = (int32_t)fr.size();
                 if (stop) *stop = (int64_t)h[i].payload_off - JPK_JAM_HEADER_BYTES;
                 return JPK_OK;
             }
-            fr.push_back(JamFrame{(int64_t)h[i].payload_off, h[i].psize, h[i].crc, bs, dec[i] - JPK_TRAILER_BYTES, staged});
+            fr.push_back(f);
         }
         o = ((uint64_t)m[3] << 32) | m[2];
         if (m[1]) { *bad = (int32_t)fr.size(); if (stop) *stop = (int64_t)o; return JPK_OK; }
@@ -285,49 +296,6 @@ extern "C" int jpk_dev_jam_staged_compress(jpk_ctx *ctx, const uint8_t *d_in, in
     return jam_compress_dev(ctx, d_in, in_len, block_size, d_out, out_cap, out_len, in_flight, JAM_STAGED, flags);
 }
 
-extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
-                                      int32_t *bad_frame)
-{
-    JPK_ENTER(ctx);
-    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    const JamResult res{out_len, frames, bad_frame};
-    jam_result_zero(res);
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
-    const int64_t need = jam_sum(fr, 0, fr.size(), false);
-    if (need > out_cap) { *out_len = need; return JPK_E_CAPACITY; }         // the size query (out_cap = 0) ends here
-    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, (size_t)JPK_JAM_PASS_FRAMES * 4));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k, false);
-        const int n = (int)(e - k);
-        std::vector<const uint8_t *> ins((size_t)n);
-        std::vector<uint8_t *> outs((size_t)n);
-        std::vector<int32_t> lens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
-        std::vector<uint32_t> crc((size_t)n);
-        int64_t o = pos;
-        for (int i = 0; i < n; i++) {
-            const JamFrame &f = fr[k + i];
-            ins[i] = d_in + f.payload_off; lens[i] = f.psize;
-            outs[i] = d_out + o; caps[i] = (int32_t)f.raw;
-            o += f.raw;
-        }
-        JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins.data(), lens.data(), outs.data(), caps.data(), outl.data(), st.data()));
-        int fail = n, rc = JPK_OK;
-        for (int i = 0; i < n && fail == n; i++) if (st[i] != JPK_OK || outl[i] != caps[i]) { fail = i; rc = st[i] != JPK_OK ? st[i] : JPK_E_CORRUPT; }
-        if (fail > 0) {
-            JPK_TRY(jam_crcs(ctx, fail, outs.data(), caps.data(), d_crc, crc.data()));
-            for (int i = 0; i < fail; i++) if (crc[i] != fr[k + i].crc) { fail = i; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
-        }
-        for (int i = 0; i < fail; i++) pos += caps[i];
-        if (fail < n) return jam_result_stop(res, pos, (int32_t)(k + fail), rc);
-        k = e;
-    }
-    return jam_result_done(res, pos, fr.size(), bad);
-}
-
 namespace {
 // jpk_jam_frames / jpk_jam_cli_frames: the host walk, *len = the raw bytes (cli: the sum of BlockSize) of the frames it found
 int jam_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *len, int32_t *bad_frame, int kind)
@@ -415,7 +383,7 @@ struct jpk_jam_index {
     std::vector<int64_t> raw_off;      // fr.size() + 1 entries: raw_off[k] = the raw bytes in front of frame k, the last one = raw_len
     int64_t archive_len = 0;
     int32_t bad = -1;
-    int32_t kind = JPK_JAM_INDEX_PLAIN;    // JPK_JAM_INDEX_CLI: frames of the stock CLI, fr[k].raw from a decode (jam_cli_decode)
+    int32_t kind = JPK_JAM_INDEX_PLAIN;    // JPK_JAM_INDEX_CLI: frames of the stock CLI, fr[k].raw from a decode (jam_decode)
                                            // JPK_JAM_INDEX_STAGED: plain and staged frames (fr[k].staged), a staged one's raw from its token walk or a decode
     // what a recovered index skipped (jpk_(dev_)jam_index_recover), in archive order: `frame` recovered frames lie in front of the gap; with
     // the frames' spans [payload_off - 15, payload_off + psize) the gaps tile [0, archive_len).  Empty for every other creator.
@@ -442,6 +410,14 @@ jpk_jam_index *jam_index_make(const std::vector<JamFrame> &fr, int64_t in_len, i
     ix->bad = bad;
     ix->kind = kind;
     return ix;
+}
+
+// the last step of every index creator: the index of fr, and the frame it stops in front of
+int jam_index_finish(const std::vector<JamFrame> &fr, int64_t in_len, int32_t bad, int32_t kind, jpk_jam_index **index, int32_t *bad_frame)
+{
+    if (!(*index = jam_index_make(fr, in_len, bad, kind))) return JPK_E_ALLOC;
+    if (bad_frame) *bad_frame = bad;
+    return JPK_OK;
 }
 }  // namespace
 
@@ -471,8 +447,7 @@ struct CliPass {
     uint8_t *const *a; uint8_t *const *b; const int32_t *caps;
     uint8_t *const *dst; const int32_t *dst_cap;
     const uint32_t *crc; uint32_t *d_crc;
-    bool prefix, exact;
-    bool staged = false, sizes = false;
+    bool prefix = false, exact = false, staged = false, sizes = false;
 };
 
 // st[i] = JPK_OK and raw[i] = the raw size of a frame that went through every stage and matches its crc -- it is at dst[i] --, else the
@@ -542,67 +517,187 @@ int jam_cli_pass(jpk_ctx *ctx, const CliPass &p, int32_t *raw, int32_t *st)
     return JPK_OK;
 }
 
-// jpk_dev_jam_cli_decompress(_ix) and, with deliver == false, jpk_dev_jam_cli_index_create: the same passes without an output buffer,
-// a capacity answer or a gather.  done (nullable) receives the frames that were verified, f.raw = their raw size, and *done_bad the first
-// bad frame (-1: none) -- what an index of the archive holds.
-int jam_cli_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, bool deliver,
-                   std::vector<JamFrame> *done, int32_t *done_bad)
+// Where the chained frames of one pass work, in ctx->jam_scratch: the pass's crc words, a gather table of `pieces` entries, slot A and
+// slot B of every frame, and `rest` bytes behind them that are the caller's.  A slot holds caps[q] bytes for the stages and is slot[q] long.
+struct ChainSlots {
+    uint32_t *d_crc = nullptr;
+    JamGatherPiece *d_pieces = nullptr;
+    uint8_t *rest = nullptr;
+    std::vector<uint8_t *> a, b;
+    std::vector<int32_t> caps;
+    std::vector<size_t> slot;
+    explicit ChainSlots(size_t n) : a(n), b(n), caps(n), slot(n) {}
+};
+int jam_chain_slots(jpk_ctx *ctx, const std::vector<int32_t> &block_size, size_t pieces, size_t rest, ChainSlots *s)
 {
+    const size_t n = block_size.size(), o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align(pieces * sizeof(JamGatherPiece));
+    size_t need = o_slots;
+    for (size_t q = 0; q < n; q++) {
+        s->caps[q] = jam_cli_cap(block_size[q]);
+        s->slot[q] = jpk_align((size_t)s->caps[q] + 64);         // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
+        need += 2 * s->slot[q];
+    }
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need + rest));
+    s->d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
+    s->d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
+    size_t off = o_slots;
+    for (size_t q = 0; q < n; q++) { s->a[q] = ctx->jam_scratch + off; s->b[q] = s->a[q] + s->slot[q]; off += 2 * s->slot[q]; }
+    s->rest = ctx->jam_scratch + off;
+    return JPK_OK;
+}
+
+// the CliPass of the frames that work in the slots s, every flag off: a caller sets the ones it means by name
+CliPass jam_chain_pass(const ChainSlots &s, const uint8_t *const *ins, const int32_t *lens, uint8_t *const *dst, const int32_t *dst_cap, const uint32_t *crc)
+{
+    CliPass p{};
+    p.n = (int)s.a.size();
+    p.ins = ins; p.lens = lens;
+    p.a = s.a.data(); p.b = s.b.data(); p.caps = s.caps.data();
+    p.dst = dst; p.dst_cap = dst_cap;
+    p.crc = crc; p.d_crc = s.d_crc;
+    return p;
+}
+
+// The plain frames of one pass: the batch decoder, ins[i] into the raws[i] bytes at outs[i] -- a frame that does not decode to exactly
+// that is JPK_E_CORRUPT --, then one batched checksum of the frames that decoded against crc[i] (d_crc: n words of device memory).
+// st[i] = JPK_OK for a verified frame, else its status.  prefix as in CliPass: only the frames in front of the first one that did not
+// decode are checked, and every frame behind the first failing one has its status; otherwise every frame has its own.
+int jam_plain_group(jpk_ctx *ctx, int n, const uint8_t *const *ins, const int32_t *lens, uint8_t *const *outs, const int32_t *raws, const uint32_t *crc,
+                    uint32_t *d_crc, bool prefix, int32_t *st)
+{
+    std::vector<int32_t> outl((size_t)n), clen;
+    std::vector<int> dec;
+    std::vector<const uint8_t *> cin;
+    JPK_TRY(jpk_dev_blocks_decompress(ctx, n, ins, lens, outs, raws, outl.data(), st));
+    for (int i = 0; i < n; i++) {
+        if (st[i] == JPK_OK && outl[i] != raws[i]) st[i] = JPK_E_CORRUPT;
+        if (st[i] != JPK_OK) {
+            if (prefix) break;
+            continue;
+        }
+        dec.push_back(i); cin.push_back(outs[i]); clen.push_back(raws[i]);
+    }
+    if (!dec.empty()) {
+        std::vector<uint32_t> got(dec.size());
+        JPK_TRY(jam_crcs(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc, got.data()));
+        for (size_t q = 0; q < dec.size(); q++)
+            if (got[q] != crc[dec[q]]) st[dec[q]] = JPK_E_CORRUPT;       // "Detected corrupt block!", jampack.cpp:59
+    }
+    if (prefix) {
+        int fail = 0;
+        while (fail < n && st[fail] == JPK_OK) fail++;
+        for (int i = fail + 1; i < n; i++) st[i] = st[fail];
+    }
+    return JPK_OK;
+}
+}  // namespace
+
+// ---- whole archives on the device: one pass loop for plain, stock-CLI and staged archives ("Staged frames") ------------------
+// Per pass: the chained frames first -- every frame of a stock-CLI archive with the full stage list, the staged frames of a JAM_STAGED
+// archive with the staged one, none of a plain archive -- through jam_cli_pass: every one ends verified in its slot A, and its raw size
+// is known; then the capacity answer for the pass; then the plain frames in front of the first bad chained one decode in their places
+// in d_out, which are known now, and meet their crcs; then one gather launch moves the chained frames to theirs.
+namespace {
+// jpk_dev_jam_decompress, jpk_dev_jam_cli_decompress(_ix), jpk_dev_jam_staged_decompress(_ix) and, with deliver == false,
+// jpk_dev_jam_cli_index_create: the same passes without an output buffer, a capacity answer or a gather.  done (nullable) receives the
+// frames that were verified, f.raw = their raw size, and *done_bad (nullable) the first bad frame (-1: none) -- what an index of the
+// archive holds.
+int jam_decode(jpk_ctx *ctx, int kind, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, bool deliver,
+               std::vector<JamFrame> *done, int32_t *done_bad)
+{
+    const bool cli = kind == JAM_CLI;
     jam_result_zero(res);
     if (done_bad) *done_bad = -1;
-    if (in_len == 0) return JPK_OK;                        // an empty archive: no frame, no device call
+    if (kind != JAM_PLAIN && in_len == 0) return JPK_OK;        // an empty archive: no frame, no device call
     std::vector<JamFrame> fr;
     int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, JAM_CLI));
-    const int64_t raw_bound = jam_sum(fr, 0, fr.size(), true);
-    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
+    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, kind));
+    // plain: the raw bytes, known from the walk -- the capacity answer is exact, comes first and nothing is touched; otherwise the raw
+    // bound (a chained frame at its BlockSize), and the answer comes per pass, behind the pass's chain
+    const int64_t raw_bound = jam_sum(fr, 0, fr.size(), cli);
+    if (kind == JAM_PLAIN && raw_bound > out_cap) { *res.out_len = raw_bound; return JPK_E_CAPACITY; }      // the size query (out_cap = 0) ends here
+    auto chained = [cli](const JamFrame &f) { return cli || f.staged; };
     int64_t pos = 0;
     for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k, true);
+        const size_t e = jam_pass_end(fr, k, cli);
         const int n = (int)(e - k);
-        std::vector<const uint8_t *> ins((size_t)n);
-        std::vector<uint8_t *> a((size_t)n), b((size_t)n);
-        std::vector<int32_t> lens((size_t)n), caps((size_t)n), bsz((size_t)n), raw((size_t)n), st((size_t)n);
-        std::vector<uint32_t> crc((size_t)n);
-        std::vector<size_t> slot((size_t)n);
-        size_t need = o_slots;
+        // the chained frames of the pass: at[q] = its place in the pass
+        std::vector<int> at;
+        std::vector<const uint8_t *> cin;
+        std::vector<int32_t> clens, bsz;
+        std::vector<uint32_t> ccrc;
         for (int i = 0; i < n; i++) {
             const JamFrame &f = fr[k + i];
-            ins[i] = d_in + f.payload_off; lens[i] = f.psize; bsz[i] = f.block_size; crc[i] = f.crc;
-            caps[i] = jam_cli_cap(f.block_size);
-            slot[i] = jpk_align((size_t)caps[i] + 64);           // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
-            need += 2 * slot[i];
+            if (!chained(f)) continue;
+            at.push_back(i);
+            cin.push_back(d_in + f.payload_off); clens.push_back(f.psize); bsz.push_back(f.block_size); ccrc.push_back(f.crc);
         }
-        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
-        size_t off = o_slots;
-        for (int i = 0; i < n; i++) { a[i] = ctx->jam_scratch + off; b[i] = a[i] + slot[i]; off += 2 * slot[i]; }
-        // every frame ends in its slot A; a frame that decodes to more than its BlockSize is a bad frame
-        JPK_TRY(jam_cli_pass(ctx, CliPass{n, ins.data(), lens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), crc.data(), d_crc, true, false},
-                             raw.data(), st.data()));
-        int m = 0, rc = JPK_OK;
-        while (m < n && st[m] == JPK_OK) m++;
-        if (m < n) rc = st[m];
+        const int nc = (int)at.size();
+        ChainSlots s(bsz.size());
+        JPK_TRY(jam_chain_slots(ctx, bsz, (size_t)JPK_JAM_PASS_FRAMES, 0, &s));
+        std::vector<int32_t> craw((size_t)nc), cst((size_t)nc);
+        if (nc) {
+            // every frame ends in its slot A; a frame that decodes to more than its BlockSize is a bad frame
+            CliPass p = jam_chain_pass(s, cin.data(), clens.data(), s.a.data(), bsz.data(), ccrc.data());
+            p.prefix = true;
+            p.staged = !cli;
+            JPK_TRY(jam_cli_pass(ctx, p, craw.data(), cst.data()));
+        }
+        // m = the frames in front of the first one that has failed so far, rc = its status; raw[i] of the frames in front of it
+        std::vector<int64_t> raw((size_t)n);
+        int m = n, rc = JPK_OK;
+        for (int i = 0; i < n; i++) raw[i] = fr[k + i].raw;
+        for (int q = 0; q < nc; q++) {
+            if (cst[q] != JPK_OK) { m = at[q]; rc = cst[q]; break; }
+            raw[at[q]] = craw[q];
+        }
         int64_t sum = 0;
         for (int i = 0; i < m; i++) sum += raw[i];
-        if (deliver) {
-            if (sum > out_cap - pos) {
-                *res.out_len = raw_bound;
-                if (res.frames) *res.frames = (int32_t)k;
-                return JPK_E_CAPACITY;
-            }
-            std::vector<JamGatherPiece> pieces;
-            uint64_t words = 0;
+        if (deliver && sum > out_cap - pos) {
+            *res.out_len = raw_bound;
+            if (res.frames) *res.frames = (int32_t)k;
+            return JPK_E_CAPACITY;
+        }
+        // the plain frames in front of frame m, in place
+        std::vector<int> pat;
+        std::vector<const uint8_t *> pin;
+        std::vector<uint8_t *> pout;
+        std::vector<int32_t> plens, praw;
+        std::vector<uint32_t> pcrc;
+        {
             int64_t o = pos;
             for (int i = 0; i < m; i++) {
-                if (raw[i] == 0) continue;
-                jam_piece_add(pieces, &words, a[i], d_out + o, (uint64_t)raw[i], a[i], a[i] + slot[i]);
+                const JamFrame &f = fr[k + i];
+                if (!chained(f)) {
+                    pat.push_back(i);
+                    pin.push_back(d_in + f.payload_off); plens.push_back(f.psize); pout.push_back(d_out + o); praw.push_back((int32_t)f.raw); pcrc.push_back(f.crc);
+                }
                 o += raw[i];
             }
-            JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, (uint64_t)sum));
-            if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
         }
+        if (!pat.empty()) {
+            const int np = (int)pat.size();
+            std::vector<int32_t> pst((size_t)np);
+            JPK_TRY(jam_plain_group(ctx, np, pin.data(), plens.data(), pout.data(), praw.data(), pcrc.data(), s.d_crc, true, pst.data()));
+            for (int q = 0; q < np; q++)
+                if (pst[q] != JPK_OK) { m = pat[q]; rc = pst[q]; break; }
+        }
+        // the chained frames in front of frame m, from their slots to their places
+        std::vector<JamGatherPiece> pieces;
+        uint64_t words = 0, gbytes = 0;
+        sum = 0;
+        for (int i = 0, q = 0; i < m; i++) {
+            if (chained(fr[k + i])) {
+                if (deliver && raw[i]) {
+                    jam_piece_add(pieces, &words, s.a[q], d_out + pos + sum, (uint64_t)raw[i], s.a[q], s.a[q] + s.slot[q]);
+                    gbytes += (uint64_t)raw[i];
+                }
+                q++;
+            }
+            sum += raw[i];
+        }
+        JPK_TRY(jam_gather(ctx, s.d_pieces, pieces, words, gbytes));
+        if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
         if (done)
             for (int i = 0; i < m; i++) {
                 done->push_back(fr[k + i]);
@@ -618,172 +713,67 @@ int jam_cli_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d
     if (done_bad) *done_bad = bad;
     return jam_result_done(res, pos, fr.size(), bad);
 }
-}  // namespace
 
-extern "C" int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
-                                             int32_t *frames, int32_t *bad_frame, jpk_jam_index **index)
+// the _ix entries: the decode, and the index of what was delivered -- the whole archive, or the frames in front of the bad one
+int jam_decode_ix(jpk_ctx *ctx, int kind, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, jpk_jam_index **index)
 {
     // (JPK_ENTER taken apart: the argument checks come before the first device call)
-    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    if (!ctx || !res.out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
     if (index) *index = nullptr;
     JPK_HIP(hipSetDevice(ctx->device));
     std::vector<JamFrame> done;
     int32_t done_bad = -1;
-    const int rc = jam_cli_decode(ctx, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, true, index ? &done : nullptr, &done_bad);
-    // the index of what was delivered: the whole archive, or the frames in front of the bad one
-    if (index && (rc == JPK_OK || rc == JPK_E_CORRUPT) && !(*index = jam_index_make(done, in_len, done_bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
+    const int rc = jam_decode(ctx, kind, d_in, in_len, d_out, out_cap, res, true, index ? &done : nullptr, &done_bad);
+    const int32_t ix_kind = kind == JAM_CLI ? JPK_JAM_INDEX_CLI : JPK_JAM_INDEX_STAGED;
+    if (index && (rc == JPK_OK || rc == JPK_E_CORRUPT) && !(*index = jam_index_make(done, in_len, done_bad, ix_kind))) return JPK_E_ALLOC;
     return rc;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames,
+                                      int32_t *bad_frame)
+{
+    JPK_ENTER(ctx);
+    if (!out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
+    return jam_decode(ctx, JAM_PLAIN, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, true, nullptr, nullptr);
+}
+
+extern "C" int jpk_dev_jam_cli_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
+                                             int32_t *frames, int32_t *bad_frame, jpk_jam_index **index)
+{
+    return jam_decode_ix(ctx, JAM_CLI, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, index);
 }
 
 extern "C" int jpk_dev_jam_cli_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
                                           int32_t *frames, int32_t *bad_frame)
 {
-    return jpk_dev_jam_cli_decompress_ix(ctx, d_in, in_len, d_out, out_cap, out_len, frames, bad_frame, nullptr);
+    return jam_decode_ix(ctx, JAM_CLI, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, nullptr);
 }
-
-
-// ---- archives of plain and staged frames ("Staged frames") ---------------------------------------------------------------
-// Per pass: the staged frames first, through jam_cli_pass with the staged stage list -- every one ends verified in its slot A, and its
-// raw size is known; then the capacity answer for the pass; then the plain frames in front of the first bad staged one decode in their
-// places in d_out, which are known now, and meet their crcs; then one gather launch moves the staged frames to theirs.
-namespace {
-// jpk_dev_jam_staged_decompress(_ix).  done (nullable) receives the frames that were delivered, f.raw = their raw size, and *done_bad the
-// first bad frame (-1: none) -- what an index of the archive holds.
-int jam_staged_decode(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, const JamResult &res, std::vector<JamFrame> *done,
-                      int32_t *done_bad)
-{
-    jam_result_zero(res);
-    *done_bad = -1;
-    if (in_len == 0) return JPK_OK;
-    std::vector<JamFrame> fr;
-    int32_t bad = -1;
-    JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad, JAM_STAGED));
-    const int64_t raw_bound = jam_sum(fr, 0, fr.size(), false);
-    const size_t o_pieces = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_pieces + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamGatherPiece));
-    int64_t pos = 0;
-    for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_pass_end(fr, k, false);
-        const int n = (int)(e - k);
-        // the staged frames of the pass: sidx[q] = its place in the pass
-        std::vector<int> sidx;
-        std::vector<const uint8_t *> sin;
-        std::vector<uint8_t *> a, b;
-        std::vector<int32_t> slens, caps, bsz;
-        std::vector<uint32_t> scrc;
-        std::vector<size_t> slot;
-        size_t need = o_slots;
-        for (int i = 0; i < n; i++) {
-            const JamFrame &f = fr[k + i];
-            if (!f.staged) continue;
-            sidx.push_back(i);
-            sin.push_back(d_in + f.payload_off); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
-            caps.push_back(jam_cli_cap(f.block_size));
-            slot.push_back(jpk_align((size_t)caps.back() + 64));      // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
-            need += 2 * slot.back();
-        }
-        const int ns = (int)sidx.size();
-        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-        JamGatherPiece *d_pieces = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_pieces);
-        size_t off = o_slots;
-        a.resize((size_t)ns); b.resize((size_t)ns);
-        for (int q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
-        std::vector<int32_t> sraw((size_t)ns), sst((size_t)ns);
-        if (ns)
-            JPK_TRY(jam_cli_pass(ctx, CliPass{ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, true, false, true},
-                                 sraw.data(), sst.data()));
-        // m = the frames in front of the first one that has failed so far, rc = its status; raw[i] of the frames in front of it
-        std::vector<int64_t> raw((size_t)n);
-        int m = n, rc = JPK_OK;
-        for (int i = 0; i < n; i++) raw[i] = fr[k + i].raw;
-        for (int q = 0; q < ns; q++) {
-            if (sst[q] != JPK_OK) { m = sidx[q]; rc = sst[q]; break; }
-            raw[sidx[q]] = sraw[q];
-        }
-        int64_t sum = 0;
-        for (int i = 0; i < m; i++) sum += raw[i];
-        if (sum > out_cap - pos) {
-            *res.out_len = raw_bound;
-            if (res.frames) *res.frames = (int32_t)k;
-            return JPK_E_CAPACITY;
-        }
-        // the plain frames in front of frame m, in place
-        std::vector<int> pidx;
-        std::vector<const uint8_t *> pin;
-        std::vector<uint8_t *> pout;
-        std::vector<int32_t> plens, pcaps;
-        {
-            int64_t o = pos;
-            for (int i = 0; i < m; i++) {
-                const JamFrame &f = fr[k + i];
-                if (!f.staged) { pidx.push_back(i); pin.push_back(d_in + f.payload_off); plens.push_back(f.psize); pout.push_back(d_out + o); pcaps.push_back((int32_t)f.raw); }
-                o += raw[i];
-            }
-        }
-        if (!pidx.empty()) {
-            const int np = (int)pidx.size();
-            std::vector<int32_t> outl((size_t)np), st((size_t)np);
-            std::vector<uint32_t> crc((size_t)np);
-            JPK_TRY(jpk_dev_blocks_decompress(ctx, np, pin.data(), plens.data(), pout.data(), pcaps.data(), outl.data(), st.data()));
-            int fail = np;
-            for (int q = 0; q < np && fail == np; q++) if (st[q] != JPK_OK || outl[q] != pcaps[q]) { fail = q; rc = st[q] != JPK_OK ? st[q] : JPK_E_CORRUPT; }
-            if (fail > 0) {
-                JPK_TRY(jam_crcs(ctx, fail, pout.data(), pcaps.data(), d_crc, crc.data()));
-                for (int q = 0; q < fail; q++) if (crc[q] != fr[k + pidx[q]].crc) { fail = q; rc = JPK_E_CORRUPT; break; }   // "Detected corrupt block!", jampack.cpp:59
-            }
-            if (fail < np) m = pidx[fail];
-        }
-        // the staged frames in front of frame m, from their slots to their places
-        std::vector<JamGatherPiece> pieces;
-        uint64_t words = 0, gbytes = 0;
-        sum = 0;
-        for (int i = 0, q = 0; i < m; i++) {
-            if (fr[k + i].staged) {
-                if (raw[i]) { jam_piece_add(pieces, &words, a[q], d_out + pos + sum, (uint64_t)raw[i], a[q], a[q] + slot[q]); gbytes += (uint64_t)raw[i]; }
-                q++;
-            }
-            sum += raw[i];
-        }
-        JPK_TRY(jam_gather(ctx, d_pieces, pieces, words, gbytes));
-        if (!pieces.empty() && ctx->prof_on) jpk_prof_resolve(ctx);
-        if (done)
-            for (int i = 0; i < m; i++) {
-                done->push_back(fr[k + i]);
-                done->back().raw = raw[i];
-            }
-        pos += sum;
-        if (m < n) {
-            *done_bad = (int32_t)k + m;
-            return jam_result_stop(res, pos, (int32_t)k + m, rc);
-        }
-        k = e;
-    }
-    *done_bad = bad;
-    return jam_result_done(res, pos, fr.size(), bad);
-}
-}  // namespace
 
 extern "C" int jpk_dev_jam_staged_decompress_ix(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
                                                 int32_t *frames, int32_t *bad_frame, jpk_jam_index **index)
 {
-    if (!ctx || !out_len || in_len < 0 || out_cap < 0 || (in_len > 0 && !d_in) || (out_cap > 0 && !d_out)) return JPK_E_ARG;
-    if (index) *index = nullptr;
-    JPK_HIP(hipSetDevice(ctx->device));
-    std::vector<JamFrame> done;
-    int32_t done_bad = -1;
-    const int rc = jam_staged_decode(ctx, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, index ? &done : nullptr, &done_bad);
-    // the index of what was delivered: the whole archive, or the frames in front of the bad one
-    if (index && (rc == JPK_OK || rc == JPK_E_CORRUPT) && !(*index = jam_index_make(done, in_len, done_bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
-    return rc;
+    return jam_decode_ix(ctx, JAM_STAGED, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, index);
 }
 
 extern "C" int jpk_dev_jam_staged_decompress(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, uint8_t *d_out, int64_t out_cap, int64_t *out_len,
                                              int32_t *frames, int32_t *bad_frame)
 {
-    return jpk_dev_jam_staged_decompress_ix(ctx, d_in, in_len, d_out, out_cap, out_len, frames, bad_frame, nullptr);
+    return jam_decode_ix(ctx, JAM_STAGED, d_in, in_len, d_out, out_cap, JamResult{out_len, frames, bad_frame}, nullptr);
 }
 
 namespace {
+// frames [k, e) of an archive in host memory as a device archive of their own: copied to ctx->stage_in in stream order, *len bytes long,
+// and *a0 = the archive offset of its first byte, which a payload_off found in it lacks
+int jam_stage_frames(jpk_ctx *ctx, const uint8_t *in, const std::vector<JamFrame> &fr, size_t k, size_t e, int64_t *len, int64_t *a0)
+{
+    *a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES;
+    *len = fr[e - 1].payload_off + fr[e - 1].psize - *a0;
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)*len + 64));
+    JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + *a0, (size_t)*len, hipMemcpyHostToDevice, ctx->stream));
+    return JPK_OK;
+}
+
 // jpk_jam_decompress / jpk_jam_cli_decompress / jpk_jam_staged_decompress: the archive staged one pass at a time -- the pass's frames are an archive of their own
 // for the device call
 int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frames, int32_t *bad_frame, int kind)
@@ -804,18 +794,14 @@ int jam_decompress_host(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t
     int64_t pos = 0;
     for (size_t k = 0; k < fr.size();) {
         const size_t e = jam_pass_end(fr, k, kind == JAM_CLI);
-        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
         // the pass decodes into its raw bytes; cli: into what is left of out_cap, at most the pass's BlockSize bytes
         int64_t room = jam_sum(fr, k, e, kind == JAM_CLI);
         if (cli) room = std::min(room, out_cap - pos);
-        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
         JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
-        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
-        int64_t n = 0;
+        int64_t len = 0, a0 = 0, n = 0;
+        JPK_TRY(jam_stage_frames(ctx, in, fr, k, e, &len, &a0));
         int32_t nf = 0, bf = -1;
-        const int rc = kind == JAM_STAGED ? jpk_dev_jam_staged_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
-                       : cli            ? jpk_dev_jam_cli_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf)
-                                        : jpk_dev_jam_decompress(ctx, ctx->stage_in, a1 - a0, ctx->stage_res, room, &n, &nf, &bf);
+        const int rc = jam_decode(ctx, kind, ctx->stage_in, len, ctx->stage_res, room, JamResult{&n, &nf, &bf}, true, nullptr, nullptr);
         if (cli && rc == JPK_E_CAPACITY) {
             JPK_HIP(hipStreamSynchronize(ctx->stream));
             *out_len = total;
@@ -918,38 +904,35 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
     // the frames that go through the stage chain (jam_cli_pass): all of a stock-CLI index, the staged ones of a JPK_JAM_INDEX_STAGED index
     // (no other index holds one); the other frames are plain ones for the batch decoder alone
     auto chained = [&](size_t f) { return cli || ix->fr[f].staged; };
-    // (>= 16 bytes behind every frame: k_jam_gather's aligned loads)
-    auto cli_slot = [&](size_t f) { return jpk_align((size_t)jam_cli_cap(ix->fr[f].block_size) + 64); };
-    const size_t o_tab = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
-    // the jobs of one decoder in a pass: at[q] = the frame's place in the pass; sa / sb / scap / crcs of the chain's frames only
+    // the jobs of one decoder in a pass: at[q] = the frame's place in the pass, crcs[q] the crc to meet
     struct Group {
         std::vector<int> at;
         std::vector<const uint8_t *> ins;
-        std::vector<uint8_t *> outs, sa, sb;
-        std::vector<int32_t> lens, caps, scap;
+        std::vector<uint8_t *> outs;
+        std::vector<int32_t> lens, caps;
         std::vector<uint32_t> crcs;
     };
     for (size_t k = 0; k < touched.size();) {
         const size_t e = jam_pass_end(touched.size(), k, [&](size_t i) { return jam_weight(ix->fr[touched[i]], cli); });
         const int m = (int)(e - k);
-        size_t npieces = 0, slot_bytes = 0, stage_bytes = 0;
+        size_t npieces = 0, plain_bytes = 0, stage_bytes = 0;
+        std::vector<int32_t> bsz;                                             // of the chain's frames: two slots each, whatever the frame's raw size
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             npieces += start[f + 1] - start[f];
-            if (chained(f)) slot_bytes += 2 * cli_slot(f);                          // the stages' slots A and B, whatever the frame's raw size
-            else if (!home[f]) slot_bytes += jpk_align((size_t)ix->fr[f].raw + 64);
+            if (chained(f)) bsz.push_back(ix->fr[f].block_size);
+            else if (!home[f]) plain_bytes += jpk_align((size_t)ix->fr[f].raw + 64);
             stage_bytes += jpk_align((size_t)ix->fr[f].psize + 64);
         }
-        const size_t o_slots = o_tab + jpk_align(npieces * sizeof(JamGatherPiece));
-        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, o_slots + slot_bytes));
+        ChainSlots s(bsz.size());
+        JPK_TRY(jam_chain_slots(ctx, bsz, npieces, plain_bytes, &s));
         if (!d_in) JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, stage_bytes));
-        uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-        JamGatherPiece *d_tab = reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch + o_tab);
         std::vector<const uint8_t *> hi((size_t)m);                           // hi[i]: the end of what is readable around the decoded frame
         std::vector<uint8_t *> outs((size_t)m);
         Group chain, plain;
-        chain.crcs.resize((size_t)m);                                         // (filled by copies in stream order: the words must stay where they are)
-        size_t slot = o_slots, stage = 0;
+        chain.crcs.resize(bsz.size());                                        // (filled by copies in stream order: the words must stay where they are)
+        uint8_t *slot = s.rest;
+        size_t stage = 0;
         for (int i = 0; i < m; i++) {
             const size_t f = touched[k + i];
             const JamFrame &fr = ix->fr[f];
@@ -962,18 +945,16 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
             }
             g.at.push_back(i); g.lens.push_back(fr.psize); g.caps.push_back((int32_t)fr.raw);
             if (chained(f)) {
-                uint8_t *sa = ctx->jam_scratch + slot;
-                slot += 2 * cli_slot(f);
-                g.sa.push_back(sa); g.sb.push_back(sa + cli_slot(f)); g.scap.push_back(jam_cli_cap(fr.block_size));
+                const size_t q = g.at.size() - 1;
                 // the crc to meet is the one in the header of the archive being read, which need not be the indexed one any more
-                uint32_t *crc = &g.crcs[g.at.size() - 1];
-                if (d_in) JPK_HIP(hipMemcpyAsync(crc, d_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
-                else memcpy(crc, h_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4);
-                outs[i] = home[f] ? home[f] : sa;
-                hi[i] = home[f] ? outs[i] + fr.raw : sa + cli_slot(f);
+                if (d_in) JPK_HIP(hipMemcpyAsync(&g.crcs[q], d_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4, hipMemcpyDeviceToHost, ctx->stream));
+                else memcpy(&g.crcs[q], h_in + fr.payload_off - JPK_JAM_HEADER_BYTES + 3, 4);
+                outs[i] = home[f] ? home[f] : s.a[q];
+                hi[i] = home[f] ? outs[i] + fr.raw : s.a[q] + s.slot[q];
             } else {
+                g.crcs.push_back(fr.crc);
                 if (home[f]) outs[i] = home[f];
-                else { outs[i] = ctx->jam_scratch + slot; slot += jpk_align((size_t)fr.raw + 64); }
+                else { outs[i] = slot; slot += jpk_align((size_t)fr.raw + 64); }
                 hi[i] = home[f] ? outs[i] + fr.raw : outs[i] + ((fr.raw + 15) & ~(int64_t)15) + 16;
             }
             g.outs.push_back(outs[i]);
@@ -982,29 +963,18 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
             // the stage chain on the touched frames alone, the last stage at the indexed raw size; the checksum is the pass's
             const int nc = (int)chain.at.size();
             std::vector<int32_t> outl((size_t)nc), st((size_t)nc);
-            JPK_TRY(jam_cli_pass(ctx, CliPass{nc, chain.ins.data(), chain.lens.data(), chain.sa.data(), chain.sb.data(), chain.scap.data(), chain.outs.data(),
-                                              chain.caps.data(), chain.crcs.data(), d_crc, false, true, !cli},
-                                 outl.data(), st.data()));
+            CliPass p = jam_chain_pass(s, chain.ins.data(), chain.lens.data(), chain.outs.data(), chain.caps.data(), chain.crcs.data());
+            p.exact = true;
+            p.staged = !cli;
+            JPK_TRY(jam_cli_pass(ctx, p, outl.data(), st.data()));
             for (int q = 0; q < nc; q++) fstat[touched[k + (size_t)chain.at[q]]] = st[q];
         }
         if (!plain.at.empty()) {
-            // the batch decoder, then one batched checksum of the frames that decoded, against their header crcs
+            // the batch decoder, then one batched checksum of the frames that decoded, against their indexed crcs
             const int np = (int)plain.at.size();
-            std::vector<int32_t> outl((size_t)np), st((size_t)np), clen;
-            std::vector<size_t> dec;
-            std::vector<const uint8_t *> cin;
-            JPK_TRY(jpk_dev_blocks_decompress(ctx, np, plain.ins.data(), plain.lens.data(), plain.outs.data(), plain.caps.data(), outl.data(), st.data()));
-            for (int q = 0; q < np; q++) {
-                const size_t f = touched[k + (size_t)plain.at[q]];
-                if (st[q] != JPK_OK || outl[q] != plain.caps[q]) { fstat[f] = st[q] != JPK_OK ? st[q] : JPK_E_CORRUPT; continue; }
-                dec.push_back(f); cin.push_back(plain.outs[q]); clen.push_back(plain.caps[q]);
-            }
-            if (!dec.empty()) {
-                std::vector<uint32_t> crc(dec.size());
-                JPK_TRY(jam_crcs(ctx, (int)dec.size(), cin.data(), clen.data(), d_crc, crc.data()));
-                for (size_t q = 0; q < dec.size(); q++)
-                    if (crc[q] != ix->fr[dec[q]].crc) fstat[dec[q]] = JPK_E_CORRUPT;   // "Detected corrupt block!", jampack.cpp:59
-            }
+            std::vector<int32_t> st((size_t)np);
+            JPK_TRY(jam_plain_group(ctx, np, plain.ins.data(), plain.lens.data(), plain.outs.data(), plain.caps.data(), plain.crcs.data(), s.d_crc, false, st.data()));
+            for (int q = 0; q < np; q++) fstat[touched[k + (size_t)plain.at[q]]] = st[q];
         }
         // the pieces of the verified frames (the one a frame was decoded into in place is already where it belongs)
         std::vector<JamGatherPiece> tab;
@@ -1023,7 +993,7 @@ int jam_read_pieces(jpk_ctx *ctx, const jpk_jam_index *ix, const uint8_t *d_in, 
                 bytes += (uint64_t)(b - a);
             }
         }
-        JPK_TRY(jam_gather(ctx, d_tab, tab, words, bytes));
+        JPK_TRY(jam_gather(ctx, s.d_pieces, tab, words, bytes));
         k = e;
     }
     int32_t bad = -1;
@@ -1073,9 +1043,7 @@ extern "C" int jpk_dev_jam_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64
     std::vector<JamFrame> fr;
     int32_t bad = -1;
     JPK_TRY(jam_walk_dev(ctx, d_in, in_len, fr, &bad));
-    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(fr, in_len, bad, JPK_JAM_INDEX_PLAIN, index, bad_frame);
 }
 
 extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
@@ -1085,9 +1053,7 @@ extern "C" int jpk_jam_index_create(const uint8_t *in, int64_t in_len, jpk_jam_i
     std::vector<JamFrame> fr;
     int32_t bad = -1;
     jam_walk_host(in, in_len, fr, &bad);
-    if (!(*index = jam_index_make(fr, in_len, bad))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(fr, in_len, bad, JPK_JAM_INDEX_PLAIN, index, bad_frame);
 }
 
 extern "C" int jpk_dev_jam_cli_index_create(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
@@ -1099,11 +1065,9 @@ extern "C" int jpk_dev_jam_cli_index_create(jpk_ctx *ctx, const uint8_t *d_in, i
     std::vector<JamFrame> done;
     int64_t raw_len = 0;
     int32_t bad = -1;
-    const int rc = jam_cli_decode(ctx, d_in, in_len, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &done, &bad);
+    const int rc = jam_decode(ctx, JAM_CLI, d_in, in_len, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &done, &bad);
     if (rc != JPK_OK && rc != JPK_E_CORRUPT) return rc;      // a bad frame ends the index, not the call
-    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(done, in_len, bad, JPK_JAM_INDEX_CLI, index, bad_frame);
 }
 
 extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_jam_index **index, int32_t *bad_frame)
@@ -1116,16 +1080,14 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
         jpk_ctx *ctx;
         JPK_TRY(jpk_host_enter(&ctx, 0));
         jam_walk_host(in, in_len, fr, &bad, JAM_CLI);
-        // staged one pass at a time, as jam_decompress_host: the pass's frames are an archive of their own for the device decode
+        // staged one pass at a time, jam_stage_frames: the pass is an archive of its own for the device decode
         for (size_t k = 0; k < fr.size();) {
             const size_t e = jam_pass_end(fr, k, true);
-            const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
-            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
-            JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+            int64_t len = 0, a0 = 0, raw_len = 0;
+            JPK_TRY(jam_stage_frames(ctx, in, fr, k, e, &len, &a0));
             std::vector<JamFrame> got;
-            int64_t raw_len = 0;
             int32_t pass_bad = -1;
-            const int rc = jam_cli_decode(ctx, ctx->stage_in, a1 - a0, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &got, &pass_bad);
+            const int rc = jam_decode(ctx, JAM_CLI, ctx->stage_in, len, nullptr, 0, JamResult{&raw_len, nullptr, nullptr}, false, &got, &pass_bad);
             JPK_HIP(hipStreamSynchronize(ctx->stream));
             if (rc != JPK_OK && rc != JPK_E_CORRUPT) return rc;
             for (JamFrame &f : got) { f.payload_off += a0; done.push_back(f); }
@@ -1133,9 +1095,7 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
             k = e;
         }
     }
-    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_CLI))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(done, in_len, bad, JPK_JAM_INDEX_CLI, index, bad_frame);
 }
 
 namespace {
@@ -1145,34 +1105,28 @@ namespace {
 // every staged frame behind the first failing one); a plain frame keeps the raw size of the walk, is not decoded and is JPK_OK.
 int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool verify, bool prefix, int32_t *st)
 {
-    const size_t o_slots = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4);
-    std::vector<size_t> sidx, slot;
+    std::vector<size_t> sidx;
     std::vector<const uint8_t *> sin;
-    std::vector<int32_t> slens, caps, bsz;
+    std::vector<int32_t> slens, bsz;
     std::vector<uint32_t> scrc;
-    size_t need = o_slots;
     for (size_t i = k; i < e; i++) {
         const JamFrame &f = fr[i];
         st[i - k] = JPK_OK;
         if (!f.staged) continue;
         sidx.push_back(i);
         sin.push_back(d_in + (f.payload_off - a0)); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
-        caps.push_back(jam_cli_cap(f.block_size));
-        slot.push_back(jpk_align((size_t)caps.back() + 64));
-        need += 2 * slot.back();
     }
     const size_t ns = sidx.size();
     if (!ns) return JPK_OK;
-    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
-    uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    std::vector<uint8_t *> a(ns), b(ns);
-    size_t off = o_slots;
-    for (size_t q = 0; q < ns; q++) { a[q] = ctx->jam_scratch + off; b[q] = a[q] + slot[q]; off += 2 * slot[q]; }
+    ChainSlots s(bsz.size());
+    JPK_TRY(jam_chain_slots(ctx, bsz, 0, 0, &s));
     std::vector<int32_t> sraw(ns), sst(ns);
     // a frame that declares more than its BlockSize is a bad frame, expanded or not
-    JPK_TRY(jam_cli_pass(ctx, CliPass{(int)ns, sin.data(), slens.data(), a.data(), b.data(), caps.data(), a.data(), bsz.data(), scrc.data(), d_crc, prefix, false,
-                                      true, !verify},
-                         sraw.data(), sst.data()));
+    CliPass p = jam_chain_pass(s, sin.data(), slens.data(), s.a.data(), bsz.data(), scrc.data());
+    p.prefix = prefix;
+    p.staged = true;
+    p.sizes = !verify;
+    JPK_TRY(jam_cli_pass(ctx, p, sraw.data(), sst.data()));
     for (size_t q = 0; q < ns; q++) {
         st[sidx[q] - k] = sst[q];
         if (sst[q] == JPK_OK) fr[sidx[q]].raw = sraw[q];
@@ -1214,9 +1168,7 @@ extern "C" int jpk_dev_jam_staged_index_create(jpk_ctx *ctx, const uint8_t *d_in
         JPK_HIP(hipSetDevice(ctx->device));
         JPK_TRY(jam_staged_sizes(ctx, d_in, in_len, verify != 0, done, &bad));
     }
-    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(done, in_len, bad, JPK_JAM_INDEX_STAGED, index, bad_frame);
 }
 
 extern "C" int jpk_jam_staged_index_create(const uint8_t *in, int64_t in_len, int32_t verify, jpk_jam_index **index, int32_t *bad_frame)
@@ -1233,22 +1185,19 @@ extern "C" int jpk_jam_staged_index_create(const uint8_t *in, int64_t in_len, in
     for (size_t k = 0; k < fr.size();) {
         const size_t e = jam_pass_end(fr, k, false);
         if (!staged_in(k, e)) { done.insert(done.end(), fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e); k = e; continue; }
-        // staged one pass at a time, as jpk_jam_cli_index_create: the pass's frames are an archive of their own for the device
-        const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
-        JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
-        JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+        // staged one pass at a time, jam_stage_frames: the pass is an archive of its own for the device
+        int64_t len = 0, a0 = 0;
+        JPK_TRY(jam_stage_frames(ctx, in, fr, k, e, &len, &a0));
         std::vector<JamFrame> got;
         int32_t pass_bad = -1;
-        const int rc = jam_staged_sizes(ctx, ctx->stage_in, a1 - a0, verify != 0, got, &pass_bad);
+        const int rc = jam_staged_sizes(ctx, ctx->stage_in, len, verify != 0, got, &pass_bad);
         JPK_HIP(hipStreamSynchronize(ctx->stream));
         JPK_TRY(rc);
         for (JamFrame &f : got) { f.payload_off += a0; done.push_back(f); }
         if (pass_bad >= 0) { bad = (int32_t)k + pass_bad; break; }
         k = e;
     }
-    if (!(*index = jam_index_make(done, in_len, bad, JPK_JAM_INDEX_STAGED))) return JPK_E_ALLOC;
-    if (bad_frame) *bad_frame = bad;
-    return JPK_OK;
+    return jam_index_finish(done, in_len, bad, JPK_JAM_INDEX_STAGED, index, bad_frame);
 }
 
 extern "C" int jpk_jam_index_kind(const jpk_jam_index *index) { return index ? index->kind : JPK_E_ARG; }
@@ -1396,14 +1345,8 @@ struct JamDevSrc {
         for (int32_t i = 0; i < n; i++) { ins[(size_t)i] = d_in + c[(size_t)i].payload_off; lens[(size_t)i] = c[(size_t)i].psize; }
         JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
         *hit = -1;
-        for (int32_t i = 0; i < n && *hit < 0; i++) {
-            const JamWalkFrame &w = c[(size_t)i];
-            const bool staged = (w.block_size & JPK_JAM_STAGED) != 0;            // (only a scan with staged_ok lets such a field through)
-            const int32_t bs = w.block_size & ~JPK_JAM_STAGED;
-            if (st[(size_t)i] != JPK_OK || !jrs::decoded_ok(dec[(size_t)i], bs, staged)) continue;
-            *f = JamFrame{(int64_t)w.payload_off, w.psize, w.crc, bs, dec[(size_t)i] - JPK_TRAILER_BYTES, staged};
-            *hit = i;
-        }
+        for (int32_t i = 0; i < n && *hit < 0; i++)
+            if (jam_frame_of(c[(size_t)i], st[(size_t)i], dec[(size_t)i], false, f)) *hit = i;
         return JPK_OK;
     }
 };
@@ -1488,10 +1431,9 @@ int jam_recover_host(const uint8_t *in, int64_t in_len, int32_t kind, int32_t ve
     for (size_t k = 0; k < fr.size();) {
         const size_t e = jam_recover_pass_end(fr, k);
         if (std::any_of(fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e, [](const JamFrame &f) { return f.staged; })) {
-            // staged one pass at a time, as jpk_jam_staged_index_create: the pass's frames lie back to back
-            const int64_t a0 = fr[k].payload_off - JPK_JAM_HEADER_BYTES, a1 = fr[e - 1].payload_off + fr[e - 1].psize;
-            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)(a1 - a0) + 64));
-            JPK_HIP(hipMemcpyAsync(ctx->stage_in, in + a0, (size_t)(a1 - a0), hipMemcpyHostToDevice, ctx->stream));
+            // staged one pass at a time, jam_stage_frames: the frames of the pass lie back to back
+            int64_t len = 0, a0 = 0;
+            JPK_TRY(jam_stage_frames(ctx, in, fr, k, e, &len, &a0));
             const int rc = jam_staged_size_pass(ctx, ctx->stage_in, a0, fr, k, e, verify != 0, false, st.data() + k);
             JPK_HIP(hipStreamSynchronize(ctx->stream));
             JPK_TRY(rc);

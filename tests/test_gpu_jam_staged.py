@@ -2,7 +2,7 @@
 reference's stage decoders, the read.  Archives of staged frames on the device: jpk_dev_jam_staged_compress against the concatenation of
 jpk_jam_staged_block_write, the host form against the device form, the round trip through jpk_dev_jam_staged_decompress and through the reference's stage decoders,
 archives that mix plain and staged frames, their capacity and corruption answers, the sort rounds the dedupe saves, and the pass
-edge.  -m gpu"""
+edge: a long archive, and what the plain, the staged and the stock-CLI entries answer when the capacity runs out behind it.  -m gpu"""
 import ctypes as C
 import struct
 
@@ -215,6 +215,127 @@ def test_a_bad_frame_1_stops_the_call_behind_frame_0(gpu, mixed):
         img, res = _decode(gpu, arch, 400_000 + MiB + 300_000, check=False)
         assert res == (400_000, 1, 1, E_CORRUPT), (name, res)
         assert np.array_equal(img[:400_000], parts[0]), name
+
+
+def _bad_frame_2(frames, how):
+    f2 = frames[2].copy()
+    if how == "crc":
+        f2[4] ^= 1
+    else:
+        f2[15 + len(f2) // 2] ^= 0x10
+    return np.concatenate([frames[0], frames[1], f2])
+
+
+@pytest.mark.parametrize("how", ("crc", "payload"))
+def test_a_bad_plain_frame_2_stops_the_call_behind_the_staged_frame_1(gpu, mixed, how):
+    """a plain frame fails behind a staged one of the same pass: the staged frame is delivered"""
+    frames, parts = mixed
+    img, res = _decode(gpu, _bad_frame_2(frames, how), 400_000 + MiB + 300_000, check=False)
+    assert res == (400_000 + 700_001, 2, 2, E_CORRUPT), res
+    assert np.array_equal(img[: 400_000 + 700_001], np.concatenate(parts[:2]))
+
+
+def test_the_earlier_plain_failure_wins_over_the_staged_one(gpu, mixed):
+    frames, _ = mixed
+    f0, f1 = frames[0].copy(), frames[1].copy()
+    f0[4] ^= 1
+    f1[15 + len(f1) // 2] ^= 0x10
+    _, res = _decode(gpu, np.concatenate([f0, f1, frames[2]]), 400_000 + MiB + 300_000, check=False)
+    assert res == (0, 0, 0, E_CORRUPT), res
+
+
+# ---- capacity behind the pass edge: 130 frames of 1 MiB BlockSize, 4096 raw bytes each --------------------------------------------
+EDGE_FRAMES, EDGE_RAW, PASS_FRAMES = 130, 4096, 128
+
+
+@pytest.fixture(scope="module")
+def edge(gpu):
+    """name -> archive of 130 frames (all plain, plain and staged in turn, all stock-CLI), and the raw bytes they share"""
+    _, jam, _ = gpu
+    text = jam.corpus.make("text", EDGE_FRAMES * EDGE_RAW, 1000)              # (one call: the generator's start-up is the slow part)
+    texts = [text[k * EDGE_RAW: (k + 1) * EDGE_RAW] for k in range(EDGE_FRAMES)]
+    assert len({t.tobytes() for t in texts}) == EDGE_FRAMES
+    plain = [jam.jam_block_write(t, MiB) for t in texts]
+    archives = {"plain": np.concatenate(plain),
+                "mixed": np.concatenate([jam.jam_staged_block_write(texts[k], MiB, flags=0) if k & 1 else plain[k] for k in range(EDGE_FRAMES)]),
+                "cli": np.concatenate([jam.jam_cli_block_write(t, MiB) for t in texts])}
+    return archives, np.concatenate(texts)
+
+
+def _edge_entry(gpu, entry):
+    _, jam, ctx = gpu
+    return {"plain": (ctx.jam_decompress, jam.lib().jpk_jam_decompress), "staged": (ctx.jam_staged_decompress, jam.lib().jpk_jam_staged_decompress),
+            "cli": (ctx.jam_cli_decompress, jam.lib().jpk_jam_cli_decompress)}[entry]
+
+
+def _edge_bound(gpu, entry, arch):
+    """what the entry's host walk reports for the archive: the raw bytes, or the raw bound of the chained kinds"""
+    _, jam, _ = gpu
+    k, bound, bad = {"plain": jam.jam_frames, "staged": jam.jam_staged_frames, "cli": jam.jam_cli_frames}[entry](arch)
+    assert (k, bad) == (EDGE_FRAMES, -1)
+    return bound
+
+
+def _edge_decode(gpu, entry, arch, cap):
+    torch, _, _ = gpu
+    d_out = torch.full((EDGE_FRAMES * EDGE_RAW + 64,), SENT, dtype=torch.uint8, device="cuda")
+    res = _edge_entry(gpu, entry)[0](_dev(torch, arch), len(arch), d_out, cap, check=False)
+    return d_out.cpu().numpy(), res
+
+
+def _edge_decode_host(gpu, entry, arch, cap):
+    """(rc, out_len, frames) of the host entry, called by ctypes"""
+    out = np.full(EDGE_FRAMES * EDGE_RAW + 64, SENT, dtype=np.uint8)
+    n, nf, bf = C.c_int64(0), C.c_int32(0), C.c_int32(-1)
+    rc = _edge_entry(gpu, entry)[1](arch.ctypes.data, len(arch), out.ctypes.data, cap, C.byref(n), C.byref(nf), C.byref(bf))
+    return out, (int(rc), n.value, nf.value)
+
+
+def test_plain_entry_answers_capacity_before_it_touches_anything(gpu, edge):
+    archives, raw = edge
+    img, res = _edge_decode(gpu, "plain", archives["plain"], len(raw) - 1)
+    assert res == (EDGE_FRAMES * EDGE_RAW, 0, -1, E_CAPACITY), res
+    assert (img == SENT).all()
+    _, res = _edge_decode_host(gpu, "plain", archives["plain"], len(raw) - 1)
+    assert res == (E_CAPACITY, EDGE_FRAMES * EDGE_RAW, 0), res
+
+
+@pytest.mark.parametrize("entry,name", (("staged", "mixed"), ("cli", "cli"), ("staged", "plain")))
+def test_chained_entries_answer_capacity_per_pass(gpu, edge, entry, name):
+    """one byte short: the first pass of 128 frames stays delivered, the second one is refused and nothing of it is written"""
+    archives, raw = edge
+    arch, done = archives[name], PASS_FRAMES * EDGE_RAW
+    bound = _edge_bound(gpu, entry, arch)
+    assert bound == {"mixed": 65 * EDGE_RAW + 65 * MiB, "cli": EDGE_FRAMES * MiB, "plain": EDGE_FRAMES * EDGE_RAW}[name]
+    img, res = _edge_decode(gpu, entry, arch, len(raw) - 1)
+    assert res == (bound, PASS_FRAMES, -1, E_CAPACITY), res
+    assert np.array_equal(img[:done], raw[:done]) and (img[done:] == SENT).all()
+    _, res = _edge_decode_host(gpu, entry, arch, len(raw) - 1)
+    assert res == (E_CAPACITY, bound, PASS_FRAMES), res
+
+
+@pytest.mark.parametrize("entry,name", (("plain", "plain"), ("staged", "mixed"), ("cli", "cli"), ("staged", "plain")))
+def test_exact_capacity_decodes_across_the_pass_edge(gpu, edge, entry, name):
+    archives, raw = edge
+    img, res = _edge_decode(gpu, entry, archives[name], len(raw))
+    assert res == (len(raw), EDGE_FRAMES, -1, OK), res
+    assert np.array_equal(img[: len(raw)], raw) and (img[len(raw):] == SENT).all()
+    out, res = _edge_decode_host(gpu, entry, archives[name], len(raw))
+    assert res == (OK, len(raw), EDGE_FRAMES) and np.array_equal(out[: len(raw)], raw) and (out[len(raw):] == SENT).all()
+
+
+@pytest.mark.parametrize("entry,name", (("staged", "mixed"), ("cli", "cli")))
+def test_exact_capacity_index_across_the_pass_edge(gpu, edge, entry, name):
+    torch, _, ctx = gpu
+    archives, raw = edge
+    arch = archives[name]
+    d_out = torch.full((len(raw) + 64,), SENT, dtype=torch.uint8, device="cuda")
+    fn = ctx.jam_staged_decompress_ix if entry == "staged" else ctx.jam_cli_decompress_ix
+    n, nf, bf, ix = fn(_dev(torch, arch), len(arch), d_out, len(raw))
+    assert (n, nf, bf) == (len(raw), EDGE_FRAMES, -1) and np.array_equal(d_out.cpu().numpy()[: len(raw)], raw)
+    assert (ix.frames, ix.bad_frame, ix.raw_len, ix.archive_len) == (EDGE_FRAMES, -1, len(raw), len(arch))
+    assert [ix.frame(k)[:2] for k in range(EDGE_FRAMES)] == [(k * EDGE_RAW, EDGE_RAW) for k in range(EDGE_FRAMES)]
+    ix.close()
 
 
 def test_fewer_sort_rounds(gpu):
