@@ -445,7 +445,7 @@ JPK_API int jpk_jam_staged_compress(const uint8_t *in, int64_t in_len, int32_t b
 JPK_API int jpk_jam_staged_frames(const uint8_t *in, int64_t in_len, int32_t *frames, int64_t *raw_bound, int32_t *bad_frame);
 /* Jampack::Decompress (jampack.cpp:262-336) of such an archive, in passes of at most 128 frames and 4 GiB.  A plain frame decodes in its
  * place in d_out as in jpk_dev_jam_decompress.  A staged frame goes jpk_dev_blocks_decompress -> slot A, k_pre_filters -> slot B,
- * jpk_dev_blocks_lz77_decompress -> slot A (at most BlockSize bytes), one batched checksum against the header crcs, and one gather launch
+ * jpk_dev_blocks_lz77_expand_deep -> slot A (at most BlockSize bytes), one batched checksum against the header crcs, and one gather launch
  * into its place. Bad frames, capacity and success are reported as by jpk_dev_jam_cli_decompress: a stage that runs out of its slot (1.05 x
  * BlockSize + 4096) is JPK_E_CORRUPT; when the frames of a pass do not fit the rest of out_cap the call is JPK_E_CAPACITY with *out_len =
  * *raw_bound of jpk_jam_staged_frames and nothing of that pass written.  Arguments are checked before a device is looked for. */
@@ -458,11 +458,25 @@ JPK_API int jpk_jam_staged_decompress(const uint8_t *in, int64_t in_len, uint8_t
  * of a match finding its literal in at most 8 hops.  A block that fails a check, needs more records or a longer chase goes through
  * k_pre_lz77 in one more launch.  The arguments are checked before a device is looked for.  No entry of the library calls it: it is far
  * faster than the serial kernel on stored and shallow streams and slower on the deep streams the dedupe writes of large blocks of real
- * sources ("Tried"), so the archive decoders stay with jpk_dev_blocks_lz77_decompress. */
+ * sources ("Tried"); the staged reader runs jpk_dev_blocks_lz77_expand_deep, below, whose caps are made for those streams. */
 JPK_API int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
                                        const int32_t *out_cap, int32_t *out_len, int32_t *status);
 /* how many blocks of ctx's last jpk_dev_blocks_lz77_expand call took the two parallel launches and how many the serial kernel */
 JPK_API int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial);
+/* The same stage and the same contract -- bytes, lengths and statuses of jpk_dev_blocks_lz77_decompress for every input, valid or not,
+ * d_out[b] at any alignment, the arguments checked before a device is looked for -- with the deep rule (lz_expand.hpp; DESIGN 4.6, "The
+ * deep expander"): k_lzd_plan gives a block up behind the first token that leaves it with more than op / 128 + 4 records for op bytes
+ * of output (a stream of the dedupe has at most op / 128 + 2; the record array is out_cap / 128 + 8 per block in ctx's arena), and
+ * k_lzd_copy follows a byte through up to H hops and leaves a block as soon as one of its two serial words is set.  Two launches for the
+ * batch, one host read of lengths and flags, one k_pre_lz77 launch for the blocks left to it and only then.  The last stage of the staged
+ * reader (jpk_dev_jam_staged_decompress and what runs its pass: the _ix and host forms, the verify = 1 index, reads and salvage). */
+JPK_API int jpk_dev_blocks_lz77_expand_deep(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                            const int32_t *out_cap, int32_t *out_len, int32_t *status);
+/* how many blocks of the last deep call on ctx -- jpk_dev_blocks_lz77_expand_deep, or the last staged pass -- took the two parallel
+ * launches and how many the serial kernel */
+JPK_API int jpk_debug_lz77_deep_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial);
+/* the constants of the deep rule: the hop cap H, the output bytes that pay for one record (128) and the records of slack (4) */
+JPK_API int jpk_debug_lz77_deep_limits(int32_t *hops, int32_t *bytes_per_record, int32_t *slack);
 /* The raw size of an Lz77 stream without its bytes: the token walk of Lz77::Decompress (lz77.cpp:678-714) with the checks of
  * jpk_lz77_decompress in their order and no copy.  Returns the status jpk_lz77_decompress gives the same stream at the same out_cap, for
  * every stream, valid or not (a token that does not parse, a negative offset, literals beyond the input or an offset beyond the output

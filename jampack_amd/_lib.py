@@ -143,6 +143,9 @@ _SIGS = {
     "jpk_jam_staged_decompress": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_dev_blocks_lz77_expand": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
     "jpk_debug_lz77_expand_last": (C.c_int, [_vp, _i32p, _i32p]),
+    "jpk_dev_blocks_lz77_expand_deep": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, C.POINTER(_vp), _i32p, _i32p, _i32p]),
+    "jpk_debug_lz77_deep_last": (C.c_int, [_vp, _i32p, _i32p]),
+    "jpk_debug_lz77_deep_limits": (C.c_int, [_i32p, _i32p, _i32p]),
     "jpk_lz77_size": (C.c_int, [_vp, C.c_int32, C.c_int32, _i32p]),
     "jpk_dev_blocks_lz77_sizes": (C.c_int, [_vp, C.c_int32, C.POINTER(_vp), _i32p, _i32p, _i32p, _i32p]),
     "jpk_dev_jam_staged_index_create": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(_vp), _i32p]),

@@ -326,6 +326,13 @@ def lz77_size(stream, cap: int) -> int:
     return n.value
 
 
+def lz77_deep_limits():
+    """jpk_debug_lz77_deep_limits -> (hop cap H, output bytes per record, records of slack) of the deep expander's rule (host code)"""
+    h, b, k = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _chk(lib().jpk_debug_lz77_deep_limits(C.byref(h), C.byref(b), C.byref(k)), "jpk_debug_lz77_deep_limits")
+    return h.value, b.value, k.value
+
+
 def _ranges(ranges):
     n = len(ranges)
     L = C.c_int64 * max(n, 1)
@@ -728,6 +735,18 @@ class Context:
         """jpk_debug_lz77_expand_last -> (blocks of the last blocks_lz77_expand call on the parallel path, on the serial path)"""
         p, q = C.c_int32(0), C.c_int32(0)
         _chk(lib().jpk_debug_lz77_expand_last(self._h, C.byref(p), C.byref(q)), "jpk_debug_lz77_expand_last")
+        return p.value, q.value
+
+    def blocks_lz77_expand_deep(self, d_ins, in_lens, d_outs, out_caps):
+        """jpk_dev_blocks_lz77_expand_deep: the same stage through the deep expander (record budget in output bytes, lz77_deep_limits()
+        hops; the serial kernel for the blocks left to it) -> (out_len list, status list); lz77_deep_last() says which way they went"""
+        return self._batch(lib().jpk_dev_blocks_lz77_expand_deep, "jpk_dev_blocks_lz77_expand_deep", d_ins, in_lens, d_outs, out_caps)
+
+    def lz77_deep_last(self):
+        """jpk_debug_lz77_deep_last -> (blocks of the last deep call on this context -- blocks_lz77_expand_deep or a staged pass -- on
+        the parallel path, on the serial path)"""
+        p, q = C.c_int32(0), C.c_int32(0)
+        _chk(lib().jpk_debug_lz77_deep_last(self._h, C.byref(p), C.byref(q)), "jpk_debug_lz77_deep_last")
         return p.value, q.value
 
     def blocks_lpx_decode(self, d_ins, lens, d_outs):

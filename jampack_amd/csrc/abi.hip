@@ -187,7 +187,7 @@ static const char *const PROF_NAMES[PROF_COUNT] = {
     "k_enc_hist/k_enc_prep", "k_enc_mtf", "k_rle_*", "k_cls_*/k_quasi_build", "k_adaptive", "k_pairs", "k_rans_lanes", "k_emit_*/k_put_*",
     "k_dec_headers", "k_dec_rans", "k_dec_rle", "k_dec_rank", "k_chk_*", "k_lg_hist", "k_lg_scatter", "k_sym_present/k_pack_keys", "k_jam_walk/k_jam_pack", "k_jam_scan_*",
     "k_enc_wrap", "k_enc_lpx", "k_dd_anchor", "k_dd_cand", "k_dd_extend", "k_dd_select", "k_dd_emit", "k_enc_filters",
-    "k_lzx_plan", "k_lz77_sizes", "k_lzx_copy", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
+    "k_lzx_plan", "k_lz77_sizes", "k_lzx_copy", "k_lzd_plan", "k_lzd_copy", "k_pre_lz77", "k_pre_lpx", "k_pre_filters"};
 
 extern "C" int jpk_ctx_profile(jpk_ctx *ctx, int enable)
 {

@@ -37,7 +37,7 @@ enum JpkProfId {
     PROF_ENC_HIST, PROF_ENC_MTF, PROF_ENC_RLE, PROF_ENC_CLASS, PROF_ENC_ADAPTIVE, PROF_ENC_PAIRS, PROF_ENC_RANS, PROF_ENC_EMIT,
     PROF_DEC_HEADERS, PROF_DEC_RANS, PROF_DEC_RLE, PROF_DEC_RANK, PROF_CHECKSUM, PROF_LG_HIST, PROF_LG_SCATTER, PROF_SA_PACK, PROF_JAM, PROF_JAM_SCAN,
     PROF_ENC_WRAP, PROF_ENC_LPX, PROF_DD_ANCHOR, PROF_DD_CAND, PROF_DD_EXTEND, PROF_DD_SELECT, PROF_DD_EMIT, PROF_ENC_FILTERS,
-    PROF_LZX_PLAN, PROF_LZ77_SIZES, PROF_LZX_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
+    PROF_LZX_PLAN, PROF_LZ77_SIZES, PROF_LZX_COPY, PROF_LZD_PLAN, PROF_LZD_COPY, PROF_PRE_LZ77, PROF_PRE_LPX, PROF_PRE_FILTERS, PROF_COUNT
 };
 struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 
@@ -109,6 +109,8 @@ struct jpk_ctx {
     jpk_stats stats;
     // jpk_dev_blocks_lz77_expand: the blocks of the last call that took the parallel path and the serial one (jpk_debug_lz77_expand_last)
     int32_t lzx_parallel = 0, lzx_serial = 0;
+    // the same for the deep expander (jpk_dev_blocks_lz77_expand_deep and the staged pass that runs it; jpk_debug_lz77_deep_last)
+    int32_t lzd_parallel = 0, lzd_serial = 0;
     // profiler
     bool prof_on = false;
     std::vector<JpkProfPending> prof_pending;
@@ -330,5 +332,9 @@ int jpk_cli_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const
 // d_tmp[b] (jpk_cli_stages_bound bytes) is where the dedupe leaves S1'
 int jpk_staged_stages_device(jpk_ctx *ctx, int n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_mid, uint8_t *const *d_tmp,
                              uint32_t flags, int32_t *s2_len);
+// Lz77::Decompress of n blocks through the deep expander (prestage_dev.hip: k_lzd_plan + k_lzd_copy, k_pre_lz77 for the blocks they leave to
+// it): jpk_dev_blocks_lz77_expand_deep behind its argument checks.  Synchronises the stream.
+int jpk_lz77_expand_deep_device(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out, const int32_t *out_cap,
+                                int32_t *out_len, int32_t *status);
 // S2 of the n bytes at in on the host (prestage.cpp): the stage chain of jpk_cli_stages_encode_ex in front of Lpx::Encode
 int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);

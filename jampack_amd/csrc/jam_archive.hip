@@ -433,12 +433,13 @@ int jam_index_finish(const std::vector<JamFrame> &fr, int64_t in_len, int32_t ba
 namespace {
 // The frames of one pass and where their stages work.  Stage 0 decodes ins[i] into a[i], the stages go A -> B -> A -> B, and the last
 // one, the second Lz77::Decompress, writes at most dst_cap[i] bytes to dst[i] (slot A again, or any address of a caller's buffer:
-// k_pre_lz77 writes by bytes).  The slots hold caps[i] bytes each.  crc[i] is the header's, d_crc n words of device memory.
+// k_pre_lz77 writes by bytes, k_lzd_copy by bytes at the two ends).  The slots hold caps[i] bytes each.  crc[i] is the header's, d_crc n words of device memory.
 //   prefix  every stage runs on the frames in front of the first one that has failed so far (a whole archive stops there); otherwise
 //           on all surviving frames, compacted after every stage -- a frame that failed a stage has no lengths for the next one
 //   exact   a frame whose raw size is not dst_cap[i] is JPK_E_CORRUPT (the reader: dst_cap is the indexed raw size)
 //   staged  staged frames: the list without the first Lz77 and the Lpx stage -- stage 0 into A, Filters A -> B, and
-//           Lz77 B -> dst with the serial kernel (the parallel expander missed its condition: DESIGN 4.6, "Tried")
+//           Lz77 B -> dst through the deep expander (k_lzd_plan + k_lzd_copy at any address of dst; k_pre_lz77 only for the frames they
+//           leave to it: a bad stream, one denser than the dedupe writes, or a byte more than lzx::DEEP_CHASE hops from its literal)
 //   sizes   the last stage is k_lz77_sizes: raw[i] is what that Lz77::Decompress would give within dst_cap[i], nothing is expanded and
 //           nothing is checked against a crc (dst, crc and d_crc are not looked at) -- the index of staged frames that does not verify
 struct CliPass {
@@ -499,6 +500,7 @@ int jam_cli_pass(jpk_ctx *ctx, const CliPass &p, int32_t *raw, int32_t *st)
     if ((m = aim(p.b, p.dst, p.dst_cap))) {
         // Lz->Decompress; a frame that decodes to more than dst_cap (its BlockSize, or its indexed raw size) is a bad frame
         if (p.sizes) JPK_TRY(jpk_dev_blocks_lz77_sizes(ctx, m, src.data(), len.data(), cap.data(), got.data(), s.data()));
+        else if (p.staged) JPK_TRY(jpk_lz77_expand_deep_device(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));
         else JPK_TRY(jpk_dev_blocks_lz77_decompress(ctx, m, src.data(), len.data(), out.data(), cap.data(), got.data(), s.data()));
         if (p.exact) for (int32_t q = 0; q < m; q++) if (s[(size_t)q] == JPK_OK && got[(size_t)q] != cap[(size_t)q]) s[(size_t)q] = JPK_E_CORRUPT;
         settle();

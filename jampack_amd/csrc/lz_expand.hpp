@@ -1,5 +1,6 @@
-// lz_expand.hpp -- the rule of the parallel LZ77 expander (jpk_dev_blocks_lz77_expand; DESIGN 4.6, "Staged frames"), shared by its host
-// form (the stand-alone rule test) and the k_lzx_* kernels (prestage_dev.hip): the plan, which turns the token stream into one segment
+// lz_expand.hpp -- the rule of the parallel LZ77 expanders (jpk_dev_blocks_lz77_expand and, with the deep rule at the end of this file,
+// jpk_dev_blocks_lz77_expand_deep; DESIGN 4.6, "Staged frames"), shared by its host form (the stand-alone rule tests) and the k_lzx_* and
+// k_lzd_* kernels (prestage_dev.hip): the plan, which turns the token stream into one segment
 // record per literal run and per match with the checks of Lz77::Decompress in their order, and the chase, which finds the input byte
 // behind any output position from the records alone.  Pure functions of the stream, so the result depends on no launch order.
 #pragma once
@@ -98,16 +99,40 @@ JPK_HD uint32_t find(const Seg *s, uint32_t n, uint32_t pos)
 JPK_HD uint32_t back(const Seg &sg, uint32_t pos) { return sg.out - sg.src + (pos - sg.out) % sg.src; }
 
 // The input byte behind output position pos, which lies in record idx = sg: *in_off.  Every hop lands in an earlier record (a match is
-// never record 0: its offset would exceed the output so far), so the chase ends; false: it needs more than MAX_CHASE hops.
-JPK_HD bool source(const Seg *s, uint32_t idx, Seg sg, uint32_t pos, uint32_t *in_off)
+// never record 0: its offset would exceed the output so far), so the chase ends; false: it needs more than `hops` hops.
+JPK_HD bool source(const Seg *s, uint32_t idx, Seg sg, uint32_t pos, uint32_t hops, uint32_t *in_off)
 {
     for (uint32_t k = 0;; k++) {
         if (!sg.match) { *in_off = sg.src + (pos - sg.out); return true; }
-        if (k == MAX_CHASE) return false;
+        if (k == hops) return false;
         pos = back(sg, pos);
         idx = find(s, idx, pos);
         sg = s[idx];
     }
+}
+
+// the expander's chase: MAX_CHASE hops
+JPK_HD bool source(const Seg *s, uint32_t idx, Seg sg, uint32_t pos, uint32_t *in_off) { return source(s, idx, sg, pos, MAX_CHASE, in_off); }
+
+// ---- the deep rule: the same plan and chase with a record budget in output terms and a larger hop cap (jpk_dev_blocks_lz77_expand_deep,
+// k_lzd_plan / k_lzd_copy; DESIGN 4.6, "The deep expander") ----------------------------------------------------------------------------
+// The dedupe writes matches of at least dd::MIN_MATCH = 256 bytes and at most two records per token, so behind every token of a stream
+// it wrote records <= op / 128 + 2.  The deep plan gives a block up as soon as records > op / DEEP_BYTES + DEEP_SLACK behind a token: a
+// dense stream is left within its first tokens, and a stream inside the budget has at most out_cap / 128 + 4 records behind a token and
+// two more inside one -- deep_seg_cap, which the host knows without reading the stream.
+constexpr uint32_t DEEP_CHASE = 32;         // hops: twice the deepest dedupe stream measured (15 at 64 MiB of real sources), as a power of two
+constexpr uint32_t DEEP_BYTES = 128;        // output bytes that pay for one record
+constexpr uint32_t DEEP_SLACK = 4;          // records a stream may be ahead of its output
+
+JPK_HD uint32_t deep_seg_cap(int64_t out_cap) { return (uint32_t)(out_cap / DEEP_BYTES + DEEP_SLACK + 4); }
+
+JPK_HD bool deep_over(const Plan &p) { return (int64_t)p.nseg > p.op / (int64_t)DEEP_BYTES + (int64_t)DEEP_SLACK; }
+
+// One token of the deep plan: lzx::step with the array's size as its cap (never reached inside the budget), then the budget
+template <class Put> JPK_HD void deep_step(Plan &p, bool parsed, const pre::Token &t, int64_t in_len, int64_t out_cap, uint32_t cap, Put put)
+{
+    step(p, parsed, t, in_len, out_cap, cap, put);
+    if (!p.serial && deep_over(p)) { p.serial = true; p.done = true; }
 }
 
 }  // namespace lzx

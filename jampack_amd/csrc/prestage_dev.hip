@@ -4,6 +4,8 @@
 //   k_lz77_sizes   the raw size of that stage's output alone (jpk_dev_blocks_lz77_sizes): one wave per block walks the tokens, no copies
 //   k_lzx_plan     the same stage as two launches (jpk_dev_blocks_lz77_expand; the rule is lz_expand.hpp): one wave per block turns the
 //   k_lzx_copy     tokens into segment records, then every thread fills aligned 16-byte words of the output from the records
+//   k_lzd_plan     the same two launches with the deep rule (jpk_dev_blocks_lz77_expand_deep, the staged reader's last stage): a record
+//   k_lzd_copy     budget in output bytes, lzx::DEEP_CHASE hops, and a copy that leaves a block as soon as it is marked serial
 //   k_lpx<false>   Lpx::Decode      (lpx.cpp:101-169)    one workgroup per part: one lane runs the adaptive model in LDS, the others move tiles
 //                  (k_pre_lpx in the profiler's table and in DESIGN 4.7)
 //   k_pre_filters  Filters::Decode  (filters.cpp:442-490) one workgroup per 64 KiB filter block, scans in LDS
@@ -146,8 +148,9 @@ struct LzxJob { const uint8_t *in; uint8_t *out; lzx::Seg *segs; int32_t in_len;
 constexpr uint32_t LZX_WORDS = 4;                                     // 16-byte words per thread, as k_enc_wrap
 constexpr uint32_t LZX_INFO = 4;                                      // info words per block: serial (plan), out_len, records, serial (copy)
 
-// One wave per block: the token walk of k_pre_lz77 without its copies; lane 0 stores the records.
-__global__ __launch_bounds__(64) void k_lzx_plan(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+// One wave per block: the token walk of k_pre_lz77 without its copies; lane 0 stores the records.  DEEP: the budget of lzx::deep_step
+// behind every token in the place of the record cap alone.
+template <bool DEEP> __device__ __forceinline__ void lzx_plan_block(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
 {
     const LzxJob jb = jobs[blockIdx.x];
     const uint32_t tid = threadIdx.x;
@@ -159,7 +162,9 @@ __global__ __launch_bounds__(64) void k_lzx_plan(const LzxJob *__restrict__ jobs
         const uint32_t w = wi < in_len ? jb.in[wi] : 0u;
         pre::Token t;
         const bool parsed = pre::parse_token([w](int j) { return win_byte(w, j); }, in_len - p.pos, &t);
-        lzx::step(p, parsed, t, in_len, (int64_t)jb.out_cap, jb.cap, [segs, tid](uint32_t i, const lzx::Seg &sg) { if (tid == 0) segs[i] = sg; });
+        auto put = [segs, tid](uint32_t i, const lzx::Seg &sg) { if (tid == 0) segs[i] = sg; };
+        if (DEEP) lzx::deep_step(p, parsed, t, in_len, (int64_t)jb.out_cap, jb.cap, put);
+        else lzx::step(p, parsed, t, in_len, (int64_t)jb.out_cap, jb.cap, put);
     }
     if (tid == 0) {
         uint32_t *r = info + LZX_INFO * (size_t)blockIdx.x;
@@ -169,17 +174,29 @@ __global__ __launch_bounds__(64) void k_lzx_plan(const LzxJob *__restrict__ jobs
     }
 }
 
+__global__ __launch_bounds__(64) void k_lzx_plan(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info) { lzx_plan_block<false>(jobs, info); }
+
+// The plan of the deep expander (jpk_dev_blocks_lz77_expand_deep): the same walk; a block is given up behind the first token that leaves
+// it with more than op / 128 + 4 records, so the walk of a dense stream ends within its first tokens and that of any stream after at
+// most out_cap / 128 + 4 records' worth of tokens.  Every iteration moves pos by the token's bytes or ends the walk.
+__global__ __launch_bounds__(64) void k_lzd_plan(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info) { lzx_plan_block<true>(jobs, info); }
+
 // Organised by destination as k_dd_emit: grid (workgroups of the largest out_cap, blocks), a workgroup owns LZX_WORDS * PRE_TB aligned
 // 16-byte words of its block's output.  A word that lies inside one record follows the matches as a whole -- lzx::back of its first byte,
 // while its 16 bytes stay inside one record and inside one period -- down to a literal run, which it reads through two aligned loads when
 // both lie inside the input; every other word resolves its bytes one by one (lzx::source).  Whole words are stored once, the partial words
 // at the two ends with byte stores: nothing outside [out, out + out_len) is written, and every read is of an input byte a record covers.
-__global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+// HOPS is the cap of the chase.  WATCH: the thread reads the block's two serial words -- the plan's and the one a thread of this launch
+// sets on finding a byte too deep -- in front of every word it resolves and returns when either is set, so a block on its way to the
+// serial kernel costs what was in flight and not a whole copy.  The read for a word is issued one word early (for the first word, on
+// entry) and is in flight while the word in front of it resolves: it costs no round trip of its own.
+template <uint32_t HOPS, bool WATCH> __device__ __forceinline__ void lzx_copy_block(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
 {
     const LzxJob jb = jobs[blockIdx.y];
     uint32_t *inf = info + LZX_INFO * (size_t)blockIdx.y;
     const uint32_t total = inf[1], nseg = inf[2];
     if (inf[0] || total == 0u) return;
+    uint32_t stop = WATCH ? __hip_atomic_load(&inf[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     const lzx::Seg *__restrict__ segs = jb.segs;
     const uintptr_t base = (uintptr_t)jb.out & ~(uintptr_t)15, r_lo = (uintptr_t)jb.in, r_hi = r_lo + (uint32_t)jb.in_len;
     const uint32_t lead = (uint32_t)((uintptr_t)jb.out - base);
@@ -189,6 +206,10 @@ __global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ 
     for (uint32_t t = 0; t < LZX_WORDS; t++) {
         const uint64_t w = w0 + (uint64_t)t * PRE_TB;
         if (w >= words) break;
+        if (WATCH) {
+            if (stop) return;
+            stop = __hip_atomic_load(&inf[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | __hip_atomic_load(&inf[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         const int64_t p0 = (int64_t)(w * 16u) - (int64_t)lead;
         uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
         const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
@@ -202,7 +223,7 @@ __global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ 
             for (uint32_t k = 0;; k++) {
                 if ((uint64_t)p + 16u > (uint64_t)s.out + s.len) { word = false; break; }       // the word crosses into the next record
                 if (!s.match) break;
-                if (k == lzx::MAX_CHASE) { deep = true; break; }
+                if (k == HOPS) { deep = true; break; }
                 const uint32_t r = (p - s.out) % s.src;
                 if ((uint64_t)r + 16u > s.src) { word = false; break; }                         // the word crosses the period's end
                 p = s.out - s.src + r;
@@ -237,7 +258,7 @@ __global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ 
             if (p < 0 || (uint64_t)p >= total) continue;
             while (idx + 1 < nseg && (uint64_t)p >= (uint64_t)sg.out + sg.len) sg = segs[++idx];
             uint32_t io = 0;
-            if (!lzx::source(segs, idx, sg, (uint32_t)p, &io)) { deep = true; break; }
+            if (!lzx::source(segs, idx, sg, (uint32_t)p, HOPS, &io)) { deep = true; break; }
             const uint32_t byte = jb.in[io];
             if (!whole) dst[j] = (uint8_t)byte;
             const uint32_t sh = byte << (8u * (j & 3u)), q = j >> 2;
@@ -246,6 +267,19 @@ __global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ 
         if (deep) { inf[3] = 1u; continue; }
         if (whole) *reinterpret_cast<uint4 *>(dst) = make_uint4(v[0], v[1], v[2], v[3]);
     }
+}
+
+__global__ __launch_bounds__(PRE_TB) void k_lzx_copy(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+{
+    lzx_copy_block<lzx::MAX_CHASE, false>(jobs, info);
+}
+
+// The copy of the deep expander: lzx::DEEP_CHASE hops, and the block's serial words in front of every word.  Every loop is bounded by the
+// hop cap, the record count (the binary search, the walk to the next record) or the 16 bytes of a word: on a hostile stream the launch
+// does O(records + DEEP_CHASE * log records * bytes) work and waits for nothing.
+__global__ __launch_bounds__(PRE_TB) void k_lzd_copy(const LzxJob *__restrict__ jobs, uint32_t *__restrict__ info)
+{
+    lzx_copy_block<lzx::DEEP_CHASE, true>(jobs, info);
 }
 
 // ---- LPX -----------------------------------------------------------------------------------------------------------------------
@@ -921,21 +955,21 @@ extern "C" int jpk_dev_blocks_lz77_sizes(jpk_ctx *ctx, int32_t n, const uint8_t 
     return finish_statuses(n, status, stp);
 }
 
-// The same stage through k_lzx_plan + k_lzx_copy, and k_pre_lz77 for the blocks they leave to it: one host read of the plan's lengths and
-// both kernels' flags, a second one only when a block went the serial way.  The records (lzx::seg_cap per block) live in ctx's arena.
-extern "C" int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
-                                          const int32_t *out_cap, int32_t *out_len, int32_t *status)
+namespace {
+// The same stage through a plan and a copy launch, and k_pre_lz77 for the blocks they leave to it: one host read of the plan's lengths and
+// both kernels' flags, a second one only when a block went the serial way.  The records live in ctx's arena: lzx::seg_cap(in_len) per
+// block, or lzx::deep_seg_cap(out_cap) with `deep` (k_lzd_plan + k_lzd_copy).  The arguments have been checked.  *par / *ser: the blocks
+// that took either way.
+int lz77_expand_run(jpk_ctx *ctx, bool deep, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out, const int32_t *out_cap,
+                    int32_t *out_len, int32_t *status, int32_t *par, int32_t *ser_n)
 {
-    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
-    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
-    JPK_TRY(pre_enter(ctx));
-    ctx->lzx_parallel = 0; ctx->lzx_serial = 0;
+    *par = 0; *ser_n = 0;
     if (n == 0) return JPK_OK;
     std::vector<LzxJob> jobs((size_t)n);
     size_t seg_recs = 0;
     uint64_t bytes = 0, max_words = 0;
     for (int b = 0; b < n; b++) {
-        const uint32_t cap = lzx::seg_cap(in_len[b]);
+        const uint32_t cap = deep ? lzx::deep_seg_cap(out_cap[b]) : lzx::seg_cap(in_len[b]);
         jobs[(size_t)b] = LzxJob{d_in[b], d_out[b], nullptr, in_len[b], out_cap[b], cap, 0u};
         seg_recs += cap;
         bytes += (uint32_t)in_len[b];
@@ -954,11 +988,14 @@ extern "C" int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t
     for (int b = 0; b < n; b++) { jobs[(size_t)b].segs = segs + so; so += jobs[(size_t)b].cap; }
     JPK_HIP(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(LzxJob), hipMemcpyHostToDevice, ctx->stream));
     JPK_HIP(hipMemsetAsync(d_info, 0, LZX_INFO * (size_t)n * 4, ctx->stream));
-    JPK_LAUNCH(ctx, PROF_LZX_PLAN, bytes, k_lzx_plan, dim3((unsigned)n), dim3(64), d_jobs, d_info);
+    if (deep) JPK_LAUNCH(ctx, PROF_LZD_PLAN, bytes, k_lzd_plan, dim3((unsigned)n), dim3(64), d_jobs, d_info);
+    else JPK_LAUNCH(ctx, PROF_LZX_PLAN, bytes, k_lzx_plan, dim3((unsigned)n), dim3(64), d_jobs, d_info);
     if (max_words)
-        for (int b0 = 0; b0 < n; b0 += DD_GRID_Y)
-            JPK_LAUNCH(ctx, PROF_LZX_COPY, bytes, k_lzx_copy, dim3(jpk_grid(max_words, LZX_WORDS * PRE_TB), (unsigned)std::min(DD_GRID_Y, n - b0)), dim3(PRE_TB),
-                       d_jobs + b0, d_info + LZX_INFO * (size_t)b0);
+        for (int b0 = 0; b0 < n; b0 += DD_GRID_Y) {
+            const dim3 grid(jpk_grid(max_words, LZX_WORDS * PRE_TB), (unsigned)std::min(DD_GRID_Y, n - b0));
+            if (deep) JPK_LAUNCH(ctx, PROF_LZD_COPY, bytes, k_lzd_copy, grid, dim3(PRE_TB), d_jobs + b0, d_info + LZX_INFO * (size_t)b0);
+            else JPK_LAUNCH(ctx, PROF_LZX_COPY, bytes, k_lzx_copy, grid, dim3(PRE_TB), d_jobs + b0, d_info + LZX_INFO * (size_t)b0);
+        }
     std::vector<uint32_t> info(LZX_INFO * (size_t)n);
     JPK_TRY(pre_finish(ctx, d_info, info));
     std::vector<int32_t> st_local((size_t)n);
@@ -979,9 +1016,20 @@ extern "C" int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t
         JPK_TRY(lz77_serial(ctx, (int32_t)m, sin.data(), slen.data(), sout.data(), scap.data(), sgot.data(), sst.data()));
         for (size_t q = 0; q < m; q++) { stp[ser[q]] = sst[q]; out_len[ser[q]] = sgot[q]; }
     }
-    ctx->lzx_serial = (int32_t)ser.size();
-    ctx->lzx_parallel = n - ctx->lzx_serial;
+    *ser_n = (int32_t)ser.size();
+    *par = n - *ser_n;
     return finish_statuses(n, status, stp);
+}
+}  // namespace
+
+extern "C" int jpk_dev_blocks_lz77_expand(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                          const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    JPK_TRY(pre_enter(ctx));
+    ctx->lzx_parallel = 0; ctx->lzx_serial = 0;
+    return lz77_expand_run(ctx, false, n, d_in, in_len, d_out, out_cap, out_len, status, &ctx->lzx_parallel, &ctx->lzx_serial);
 }
 
 extern "C" int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial)
@@ -989,6 +1037,40 @@ extern "C" int jpk_debug_lz77_expand_last(jpk_ctx *ctx, int32_t *parallel, int32
     if (!ctx || !parallel || !serial) return JPK_E_ARG;
     *parallel = ctx->lzx_parallel;
     *serial = ctx->lzx_serial;
+    return JPK_OK;
+}
+
+// The deep expander behind its argument checks (the staged pass of jam_archive.hip calls it with job arrays of its own making)
+int jpk_lz77_expand_deep_device(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out, const int32_t *out_cap,
+                                int32_t *out_len, int32_t *status)
+{
+    JPK_TRY(pre_enter(ctx));
+    ctx->lzd_parallel = 0; ctx->lzd_serial = 0;
+    return lz77_expand_run(ctx, true, n, d_in, in_len, d_out, out_cap, out_len, status, &ctx->lzd_parallel, &ctx->lzd_serial);
+}
+
+extern "C" int jpk_dev_blocks_lz77_expand_deep(jpk_ctx *ctx, int32_t n, const uint8_t *const *d_in, const int32_t *in_len, uint8_t *const *d_out,
+                                               const int32_t *out_cap, int32_t *out_len, int32_t *status)
+{
+    if (!ctx || n < 0 || (n > 0 && (!d_in || !in_len || !d_out || !out_cap || !out_len))) return JPK_E_ARG;
+    if (!blocks_args_ok(n, d_in, in_len, d_out, out_cap)) return JPK_E_ARG;
+    return jpk_lz77_expand_deep_device(ctx, n, d_in, in_len, d_out, out_cap, out_len, status);
+}
+
+extern "C" int jpk_debug_lz77_deep_last(jpk_ctx *ctx, int32_t *parallel, int32_t *serial)
+{
+    if (!ctx || !parallel || !serial) return JPK_E_ARG;
+    *parallel = ctx->lzd_parallel;
+    *serial = ctx->lzd_serial;
+    return JPK_OK;
+}
+
+extern "C" int jpk_debug_lz77_deep_limits(int32_t *hops, int32_t *bytes_per_record, int32_t *slack)
+{
+    if (!hops || !bytes_per_record || !slack) return JPK_E_ARG;
+    *hops = (int32_t)lzx::DEEP_CHASE;
+    *bytes_per_record = (int32_t)lzx::DEEP_BYTES;
+    *slack = (int32_t)lzx::DEEP_SLACK;
     return JPK_OK;
 }
 

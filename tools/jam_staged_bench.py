@@ -3,9 +3,12 @@
   (a) writer    Context.jam_staged_compress with flags 0, 1 (dedupe) and 5 (dedupe + filters) against Context.jam_compress (plain frames)
                 and Context.jam_cli_compress with the same flags (stock-CLI frames): GB/s, archive bytes, sa_rounds of the first block
   (b) reader    Context.jam_staged_decompress of those archives against Context.jam_decompress of the plain one
-  (c) expander  Context.blocks_lz77_expand against Context.blocks_lz77_decompress on the same S1 streams -- stored (04 80 | R) and deduped
-                (Context.blocks_lz77_dedupe) -- of 1, 8 and 64 MiB blocks, one block and 16 blocks per call, with the blocks each path took
-                and, from a token walk on the host, every stream's records and its deepest byte
+  (c) expander  Context.blocks_lz77_expand and Context.blocks_lz77_expand_deep (the staged reader's last stage) against
+                Context.blocks_lz77_decompress on the same S1 streams -- stored (04 80 | R) and deduped (Context.blocks_lz77_dedupe) -- of
+                1, 8 and 64 MiB blocks, one block and 16 blocks per call, with the blocks each path took and, from a token walk on the
+                host, every stream's records and its deepest byte
+  (w) worst     one 64 MiB block of matches at distance 3 stacked H deep (H = lz77_deep_limits()[0]), inside the record budget: every byte
+                takes the per-byte chase through H records.  The deep entry against the serial one, once (--only w)
 
 Inputs: corpus text (64 generations of 1 MiB; the 256 MiB input is that in four block orders) and corpus.system_sources, as 64 frames of
 1 MiB and as 4 frames of 64 MiB.  Every workload runs in a process of its own under `timeout -k 10` (--limit seconds); the first that fails
@@ -185,6 +188,7 @@ def measure_expander(tmp, key, reps):
     ctx = jam.Context(0, torch.cuda.current_stream().cuda_stream)
     sync = torch.cuda.synchronize
     lines = [f"device: {torch.cuda.get_device_name(0)}"]
+    hops, per, slack = jam.lz77_deep_limits()
     for mib in (1, 8, 64):
         n = mib * MiB
         raw = load(tmp, key, n)
@@ -196,7 +200,8 @@ def measure_expander(tmp, key, reps):
         s1_len = {"stored": n + 2, "deduped": m}
         shape = {form: stream_shape(d_s1[form][: s1_len[form]].cpu().numpy(), n) for form in s1_len}
         for form, (nrec, deepest) in shape.items():
-            lines.append(f"{mib:3d} MiB  {form:<8s} |S1| {s1_len[form]:>9d}  records {nrec} (cap {s1_len[form] // 64 + 4})  deepest byte {deepest} hops (cap 8)")
+            lines.append(f"{mib:3d} MiB  {form:<8s} |S1| {s1_len[form]:>9d}  records {nrec} (cap {s1_len[form] // 64 + 4}; deep: {n // per + slack + 4})  "
+                         f"deepest byte {deepest} hops (cap 8; deep: {hops})")
         for nblk in (1, 16):
             d_out = [torch.empty(n + 64, dtype=torch.uint8, device="cuda") for _ in range(nblk)]
             for form in ("stored", "deduped"):
@@ -206,24 +211,72 @@ def measure_expander(tmp, key, reps):
                     ol, st = ctx.blocks_lz77_expand(ins, lens, d_out, caps)
                     assert st == [0] * nblk and ol == [n] * nblk
 
+                def deep():
+                    ol, st = ctx.blocks_lz77_expand_deep(ins, lens, d_out, caps)
+                    assert st == [0] * nblk and ol == [n] * nblk
+
                 def serial():
                     ol, st = ctx.blocks_lz77_decompress(ins, lens, d_out, caps)
                     assert st == [0] * nblk and ol == [n] * nblk
 
-                for f in (serial, expand):                      # both give the raw block back
+                for f in (serial, expand, deep):                # all give the raw block back
                     d_out[-1].zero_()
                     f()
                     assert torch.equal(d_out[-1][:n], d_raw), (form, f.__name__)
-                path = ctx.lz77_expand_last()
-                t = medians({"serial": serial, "expand": expand}, reps, sync)
+                path, dpath = ctx.lz77_expand_last(), ctx.lz77_deep_last()
+                t = medians({"serial": serial, "expand": expand, "deep": deep}, reps, sync)
                 tot = n * nblk
                 lines.append(f"{mib:3d} MiB x {nblk:2d}  {form:<8s} |S1| {s1_len[form]:>9d}  serial {t['serial'][0]:9.3f} ms {tot / t['serial'][0] / 1e6:8.2f} GB/s   "
                              f"expand {t['expand'][0]:9.3f} ms {tot / t['expand'][0] / 1e6:8.2f} GB/s   serial / expand {t['serial'][0] / t['expand'][0]:7.2f}   "
-                             f"blocks parallel {path[0]} serial {path[1]}   rounds: serial " + " ".join(f"{x:.3f}" for x in t["serial"][1])
-                             + "; expand " + " ".join(f"{x:.3f}" for x in t["expand"][1]))
+                             f"blocks parallel {path[0]} serial {path[1]}   "
+                             f"deep {t['deep'][0]:9.3f} ms {tot / t['deep'][0] / 1e6:8.2f} GB/s   serial / deep {t['serial'][0] / t['deep'][0]:7.2f}   "
+                             f"blocks parallel {dpath[0]} serial {dpath[1]}   rounds: serial " + " ".join(f"{x:.3f}" for x in t["serial"][1])
+                             + "; expand " + " ".join(f"{x:.3f}" for x in t["expand"][1]) + "; deep " + " ".join(f"{x:.3f}" for x in t["deep"][1]))
             del d_out
     ctx.close()
     return lines
+
+
+def leb(v):
+    """Utils::EncodeLeb128 as pre::leb_write has it"""
+    if v < LEB_OFF[0]:
+        return bytes([v | 0x80])
+    for d in range(1, 5):
+        if d == 4 or v < LEB_OFF[d]:
+            x = v - LEB_OFF[d - 1]
+            return bytes([(x >> (7 * (d - k))) & 0x7F for k in range(d)] + [0x80 | (x & 0x7F)])
+
+
+def measure_worst():
+    """one run of each entry after a warm-up of each: the block is made to be slow"""
+    import torch
+    import jampack_amd as jam
+    ctx = jam.Context(0, torch.cuda.current_stream().cuda_stream)
+    sync = torch.cuda.synchronize
+    hops = jam.lz77_deep_limits()[0]
+    n, lit = 64 * MiB, 4096
+    ln = (n - lit) // hops                                      # hops matches of ln bytes at distance 3 behind 4 KiB of literals
+    rest = n - lit - hops * ln
+    s = bytes([(31 << 3) | 7]) + leb(3) + leb(ln - 35) + leb(lit - 7) + np.random.default_rng(3).integers(0, 256, lit, dtype=np.uint8).tobytes()
+    s += (bytes([31 << 3]) + leb(3) + leb(ln - 35)) * (hops - 1) + bytes([4, 0x80]) + bytes(rest)
+    nrec, deepest = stream_shape(s, n)
+    d_s1 = torch.from_numpy(np.frombuffer(s, dtype=np.uint8).copy()).to("cuda")
+    d_out = [torch.empty(n + 64, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    ms = {}
+    for k, (name, fn) in enumerate((("serial", ctx.blocks_lz77_decompress), ("deep", ctx.blocks_lz77_expand_deep))):
+        for _ in range(2):                                      # warm-up, then the run that counts
+            d_out[k].zero_()
+            sync()
+            t0 = time.perf_counter()
+            ol, st = fn([d_s1], [len(s)], [d_out[k]], [n])
+            sync()
+            ms[name] = (time.perf_counter() - t0) * 1e3
+            assert st == [0] and ol == [n], name
+    assert torch.equal(d_out[0][:n], d_out[1][:n]) and ctx.lz77_deep_last() == (1, 0)
+    ctx.close()
+    return [f"device: {torch.cuda.get_device_name(0)}",
+            f"64 MiB, {hops} matches of {ln} bytes at distance 3 behind {lit} literals: |S1| {len(s)}, records {nrec}, deepest byte {deepest} hops",
+            f"serial {ms['serial']:9.3f} ms   deep {ms['deep']:9.3f} ms (parallel path)   serial / deep {ms['serial'] / ms['deep']:.2f}"]
 
 
 def main():
@@ -237,15 +290,21 @@ def main():
     a = ap.parse_args()
     if a.step:
         part, key, *shape = a.step.split(":")
-        print(json.dumps(measure_archive(a.data, key, shape[0], a.reps) if part == "a" else measure_expander(a.data, key, a.reps)))
+        if part == "w":
+            print(json.dumps(measure_worst()))
+        else:
+            print(json.dumps(measure_archive(a.data, key, shape[0], a.reps) if part == "a" else measure_expander(a.data, key, a.reps)))
         return
     lines = [f"python tools/jam_staged_bench.py --reps {a.reps}" + (f" --only {a.only}" if a.only else ""),
              f"median of {a.reps} alternating rounds after one warm-up, wall clock with a device synchronise"]
     steps = [(f"a:{key}:{shape}", f"(a, b) writer and reader, {frames} frames of {bs // MiB} MiB of {name}") for key, name in INPUTS for shape, bs, frames in SHAPES]
-    steps += [(f"c:{key}", f"(c) expander against the serial kernel, S1 of {name}") for key, name in INPUTS]
+    steps += [(f"c:{key}", f"(c) expanders against the serial kernel, S1 of {name}") for key, name in INPUTS]
+    if a.only and "w:" in a.only.split(","):                   # only on request: it is one slow block, timed once
+        steps.append(("w:", "(w) the per-byte chase at its worst: distance 3, H deep, 64 MiB"))
     failed = None
     with tempfile.TemporaryDirectory() as tmp:
-        make_inputs(tmp)
+        if not a.only or any(k[0] != "w" for k in a.only.split(",")):
+            make_inputs(tmp)
         for step, title in steps:
             if a.only and step not in a.only.split(","):
                 continue
