@@ -373,7 +373,7 @@ void jpk_compress_inflight_leave(int device)
 {
     if (device >= 0 && device < 64) g_compress_inflight[device].fetch_sub(1, std::memory_order_relaxed);
 }
-// launch groups of the entropy encoder for a block of `nch` chunks that is one of `inflight` blocks on its device (ans_enc.hip):
+// launch groups of the entropy encoder for a block of `nch` chunks that is one of `inflight` blocks on its device (ans_enc.hip, enc_launch_groups):
 // graded groups shorten ONE block and cost throughput when other blocks fill the machine anyway
 int jpk_enc_groups_for(int inflight, uint32_t nch)
 {

@@ -1,4 +1,4 @@
-"""Plain-Python restatement of how the encoder's adaptive-model kernels (k_adapt_* in jampack_amd/csrc/ans_enc.hip) cut the nine
+"""Plain-Python restatement of how the encoder's adaptive-model kernels (k_adapt_* in jampack_amd/csrc/ans_enc_model.hip) cut the nine
 recurrences of a chunk into 4096-item segments and what becomes of every segment.  No GPU, no library: the crafted streams of
 test_adapt_segment_model.py and test_gpu_adapt_merge.py are built here, and this model says which routes of the kernels they reach.
 

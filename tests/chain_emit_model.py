@@ -1,4 +1,4 @@
-"""The back half of ans_enc.hip restated in plain Python: what k_pairs pads, what k_rans_lanes leaves behind, and how k_emit_count ->
+"""The back half of ans_enc_chain.hip restated in plain Python: what k_pairs pads, what k_rans_lanes leaves behind, and how k_emit_count ->
 k_emit_prefix -> k_put_payload turn that into the payload bytes -- and the crafted inputs that reach its index edges.  No GPU code is
 imported; the functions that need the oracle take it as an argument.
 
@@ -253,7 +253,7 @@ def payload(pairs, mut=None, em=None):
 
 # ---- rans_record ---------------------------------------------------------------------------------------------------------------------
 def record(lo, fr):
-    """rans_record of ans_enc.hip on numpy uint32 arrays: -> (xmax, rcp, bias, w = (65536 - fr) | shift << 24); 32-bit arithmetic only"""
+    """rans_record of ans_enc_chain.hip on numpy uint32 arrays: -> (xmax, rcp, bias, w = (65536 - fr) | shift << 24); 32-bit arithmetic only"""
     lo = np.asarray(lo, dtype=np.uint32)
     fr = np.asarray(fr, dtype=np.uint32)
     big = fr >= 2

@@ -1,4 +1,4 @@
-"""Code-generation guard for the rANS encoder chain (k_rans_lanes, ans_enc.hip).
+"""Code-generation guard for the rANS encoder chain (k_rans_lanes, ans_enc_chain.hip).
 
 Round 4 made the chain's record prefetch correct by construction: the sixteen batches of records in flight land in an LDS ring
 (global_load_lds_dwordx4 issued from asm volatile) and become register values only through an ordinary ds_read behind an asm
@@ -21,8 +21,8 @@ VMEM = re.compile(r"^\s*(global_|buffer_|scratch_|flat_)\w+")
 
 
 def kernel_body(tmp_dir):
-    src = os.path.join(ROOT, "jampack_amd", "csrc", "ans_enc.hip")
-    out = os.path.join(str(tmp_dir), "ans_enc.s")
+    src = os.path.join(ROOT, "jampack_amd", "csrc", "ans_enc_chain.hip")
+    out = os.path.join(str(tmp_dir), "ans_enc_chain.s")
     subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-DJPK_BUILD", "--cuda-device-only", "-S", src, "-o", out],
                           stderr=subprocess.DEVNULL)
     text = open(out).read()

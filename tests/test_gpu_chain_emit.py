@@ -1,4 +1,4 @@
-"""The rANS encoder's back half (ans_enc.hip: k_pairs' record and padding writes, k_rans_lanes, k_emit_count, k_emit_prefix,
+"""The rANS encoder's back half (ans_enc_chain.hip: k_pairs' record and padding writes, k_rans_lanes, k_emit_count, k_emit_prefix,
 k_put_payload) on the crafted inputs of chain_emit_model, bit-exact against the oracle (which test_oracle_vs_ref.py pins to the reference
 build).  -m gpu
 

@@ -1,4 +1,4 @@
-"""The rANS encode chain on a stream of the device's chain pool (chain_pool.hpp; ans_enc.hip encode_core, one group).
+"""The rANS encode chain on a stream of the device's chain pool (chain_pool.hpp; ans_enc.hip encode_core, enc_single_group).
 
 k_rans_lanes runs on a high-priority stream that the library owns and shares among contexts; the model pass in front of it and the
 emit kernels behind it stay on the context's stream, and the host orders the two.  A chain that starts before its model pass has

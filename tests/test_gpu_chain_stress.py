@@ -1,4 +1,4 @@
-"""Stress test of the rANS encoder chain (k_rans_lanes, ans_enc.hip; ans.cpp:189-208).
+"""Stress test of the rANS encoder chain (k_rans_lanes, ans_enc_chain.hip; ans.cpp:189-208).
 
 The chain keeps sixteen batches of step records in flight while other blocks' suffix sorts saturate the memory system; round 3
 produced timing-dependent wrong bytes there (about one per 10^6 steps) when records in flight lived in registers.  They live in an
