@@ -712,6 +712,10 @@ JPK_API int jpk_debug_multi_lock_probe(uint64_t device_mask, int32_t hold_ms);
 /* host-logic probe: the work list jpk_dev_blocks_compress forms for these block lengths (groups of small blocks, large blocks alone):
  * task t covers blocks [first[t], first[t] + count[t]); returns the number of tasks.  No device call. */
 JPK_API int jpk_debug_group_plan(int32_t nblocks, const int32_t *in_len, int32_t *first, int32_t *count);
+/* host-logic probe: the groups the batched inverse BWT of jpk_dev_blocks_decompress cuts nblocks consecutive blocks of these output
+ * capacities into: as many blocks per group as fit budget_bytes of scratch (0 = the production 8 GiB) and 65 535 jobs, a block beyond the
+ * budget alone; group g ends in front of block group_end[g] (nblocks entries of room).  Returns the number of groups.  No device call. */
+JPK_API int jpk_debug_inv_batch_plan(int32_t nblocks, const int32_t *out_cap, int64_t budget_bytes, int32_t *group_end);
 /* host-logic probe: which rounds of a suffix sort the host makes PAIR rounds (bwt_fwd.hip PairSchedule: behind a doubling round that left >= 90 % of
  * its list, two doubling rounds apart, twice as far behind a pair round that left most of its list; JPK_PAIR_* override), given what the host
  * knows -- list[r] = the unresolved suffixes round r started with (list[0] = n; 0 = the sort had ended).  is_pair[r] = 1 for pair rounds; returns

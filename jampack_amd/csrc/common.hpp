@@ -63,7 +63,7 @@ struct JpkMail {
     uint32_t spare0[120 - 32 - (int)(sizeof(SaStats) / 4)];
     uint32_t sa_vmode;                       // word 120, host: the code round 0 of the suffix sort chose
     uint32_t spare1[7];
-    uint8_t jam_header[4 * (WORDS - 128)];   // words 128-255, host: one frame header on its way to or from the device (abi.hip)
+    uint8_t jam_header[4 * (WORDS - 128)];   // words 128-255, host: one frame header on its way to or from the device (abi.hip, jpk_dev_jam_block_write / _read)
 };
 static_assert(sizeof(JpkMail) == 4 * JpkMail::WORDS, "the page is 256 words");
 static_assert(offsetof(JpkMail, dec.status) == 4 * 8 && offsetof(JpkMail, sa_counts) == 4 * 16 && sizeof(JpkMail::SaCounts) == 4 * 8 &&
@@ -230,7 +230,7 @@ int jpk_radix_sort_slot_keys(jpk_ctx *ctx, uint32_t n, uint64_t *keysA, uint32_t
                              uint32_t *scratch, uint64_t **keys_out, uint32_t **vals_out, bool group, const uint8_t *slot_tag = nullptr, int tag_shift = 26,
                              uint32_t slot_n = 0);
 // compress-side calls (forward BWT, rANS encode) of the contexts of ONE DEVICE that are running right now: the encoder cuts its
-// chains into fewer launch groups when other blocks are in flight on the same GPU (abi.hip)
+// chains into fewer launch groups when other blocks are in flight on the same GPU (abi.hip, the in-flight accounting)
 int jpk_compress_inflight_enter(int device);        // returns the count on that device including the caller
 void jpk_compress_inflight_leave(int device);
 int jpk_enc_groups_for(int inflight, uint32_t nch);
@@ -244,7 +244,7 @@ struct JpkCompressInflight {
 // moves the per-round statistics of the last suffix sort from the pinned mailbox into ctx->stats (call after a stream sync)
 void jpk_sa_stats_sync(jpk_ctx *ctx);
 
-// ---- what the archive layer (jam_archive.hip) shares with abi.hip, which defines each of them once -------
+// ---- what the archive layer (jam_archive.hip) shares with the ABI units (abi.hip, abi_pool.hip, abi_multi.hip), each defined once -------
 #define JPK_ENTER(ctx)                         \
     if (!(ctx)) return JPK_E_ARG;              \
     JPK_HIP(hipSetDevice((ctx)->device))

@@ -1,7 +1,7 @@
 // jam_archive.hip -- whole .jam archives of the C ABI (include/jampack_abi.h): the frame walks, the batched compress and decompress
 // calls of plain and stock-CLI archives with their host-buffer forms, the index + range reads, and the index and the salvage of damaged
 // archives (the rule they share with the kernels: jam_resync.hpp).  Host drivers only: the kernels
-// are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines and the context pool in abi.hip.
+// are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines in abi_blocks.hip and the context pool in abi_pool.hip.
 #include <algorithm>
 #include <atomic>
 #include <new>

@@ -330,7 +330,7 @@ extern "C" int jpk_cli_stages_encode_ex(const uint8_t *in, int32_t n, uint8_t *o
 }
 
 // The same chain stopped at S2, which is what a staged frame hands to the BWT ("Staged frames"); |S2| = jpk_cli_stages_bound - 2
-// at most.  Declared in common.hpp for abi.hip.
+// at most.  Declared in common.hpp for abi_host.hip.
 int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags);
 int jpk_staged_s2_host(const uint8_t *in, int32_t n, uint8_t *out, int32_t out_cap, int32_t *out_len, uint32_t flags)
 {

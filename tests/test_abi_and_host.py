@@ -331,6 +331,44 @@ def test_group_plan_covers_every_block_once_and_in_order():
     assert lib().jpk_debug_group_plan(2, (ctypes.c_int32 * 2)(5, -1), (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 2)()) == -1
 
 
+def test_inv_batch_plan_cuts_greedily_at_the_budget_and_the_job_cap():
+    """jpk_dev_blocks_decompress' cut of a batched call into groups (host logic): consecutive blocks, as many as fit the scratch budget
+    (8 GiB in production) and 65 535 jobs -- the GPU suite only ever reaches one group"""
+    from jampack_amd import lib
+    MiB = 1 << 20
+
+    def plan(caps, budget):
+        n = len(caps)
+        A = (ctypes.c_int32 * max(n, 1))(*caps)
+        E = (ctypes.c_int32 * max(n, 1))()
+        g = lib().jpk_debug_inv_batch_plan(n, A, budget, E)
+        assert g >= 0
+        ends = [E[i] for i in range(g)]
+        assert ends == sorted(set(ends)) and all(e >= 1 for e in ends) and (ends[-1] if ends else 0) == n     # consecutive, every block once
+        return ends
+
+    assert plan([], 0) == []
+    assert plan([MiB] * 256, 0) == [256]                                             # the production budget: one group
+    assert plan([120] * 70000, 1 << 50) == [65535, 70000]                            # the job cap, whatever the budget
+    # a small budget over mixed sizes, one block (4 MiB: ~10 bytes of scratch per byte) larger than the budget
+    caps = ([64 << 10, MiB, 300 << 10, 120, 0, 512 << 10, 7, MiB - 1] * 6)[:45]
+    caps[20] = 4 * MiB
+    budget = 16 * MiB
+    ends = plan(caps, budget)
+    assert len(ends) >= 4
+    first = 0
+    for e in ends:
+        assert plan(caps[first:e], budget) == [e - first]                            # the group alone is one group ...
+        if e < len(caps):
+            assert plan(caps[first:e + 1], budget) == [e - first, e - first + 1]     # ... and takes no block more: the cut is maximal
+        first = e
+    assert plan([4 * MiB], budget) == [1] and 21 in ends and 20 in ends              # beyond the budget: a group of its own
+    bad = lib().jpk_debug_inv_batch_plan
+    assert bad(-1, None, 0, None) == -1 and bad(1, None, 0, (ctypes.c_int32 * 1)()) == -1 and bad(1, (ctypes.c_int32 * 1)(5), 0, None) == -1
+    assert bad(1, (ctypes.c_int32 * 1)(-1), 0, (ctypes.c_int32 * 1)()) == -1 and bad(1, (ctypes.c_int32 * 1)(5), -1, (ctypes.c_int32 * 1)()) == -1
+    assert bad(1, (ctypes.c_int32 * 1)(0x7fffffff), 0, (ctypes.c_int32 * 1)()) == -1  # the image (+ trailer) passes 2^31 - 1, as in the call itself
+
+
 def test_stats_struct_layout_matches_the_header(tmp_path):
     """jpk_stats as the C compiler lays it out from include/jampack_abi.h against the ctypes mirror (jampack_amd/_lib.py): size and the
     offset of every field -- the bench reads the rounds, the key depth of round 0 and the arena size through it"""

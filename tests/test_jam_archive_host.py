@@ -21,7 +21,7 @@ def jam():
 
 
 def _slot_cap(n):
-    """the payload slot of a frame of n input bytes (abi.hip jpk_multi_comp_cap, which jam_archive.hip sizes the frames with)"""
+    """the payload slot of a frame of n input bytes (abi_multi.hip jpk_multi_comp_cap, which jam_archive.hip sizes the frames with)"""
     m = n + 480
     return m * 5 // 4 + 4096 + 1400 * (m // MiB + 1)
 
