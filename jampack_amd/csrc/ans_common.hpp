@@ -58,4 +58,7 @@ __device__ __forceinline__ int32_t adapt_step(int32_t x, int i, int sym, int A)
     return x + ((mix - x) >> 5);
 }
 
+// the 64-bit value a kernel posted as mail words lo, lo + 1 (host side of both coders' mail word names: ans_enc.hpp, ans_dec.hpp)
+inline uint64_t mail_u64(const uint32_t *mail, int lo) { return ((uint64_t)mail[lo + 1] << 32) | mail[lo]; }
+
 }  // namespace jpk

@@ -90,8 +90,6 @@ static_assert(MAIL_SYM_TOTAL < MAIL_LAYOUT_WORDS && MAIL_LANE_TOTAL < MAIL_LAYOU
 static_assert(MAIL_SYM_TOTAL >= MAIL_OFFSETS_WORDS && MAIL_LANE_TOTAL >= MAIL_OFFSETS_WORDS && MAIL_SYM_TOTAL != MAIL_LANE_TOTAL, "k_sym_layout's words are none of k_out_offsets' nine");
 static_assert(MAIL_TOTAL + 2 == MAIL_RLE_SYMBOLS && MAIL_RLE_SYMBOLS + 2 == MAIL_CHAIN_CYCLES && MAIL_CHAIN_CYCLES + 2 == MAIL_CHAIN_TICKS &&
               MAIL_CHAIN_TICKS + 2 == MAIL_CHAIN_RLEN, "four lo / hi pairs and one word, back to back");
-// the 64-bit value posted as words lo, lo + 1
-inline uint64_t mail_u64(const uint32_t *mail, int lo) { return ((uint64_t)mail[lo + 1] << 32) | mail[lo]; }
 
 // ---- the host steps, each in the unit that owns its kernels; all enqueue on ctx->stream ----------------------------------------
 // ans_enc_front.hip -- rank coding (k_enc_hist, k_enc_prep, k_enc_mtf) and RLE0 (k_rle_lz, k_rle_ext, k_rle_tiles, k_tile_prefix)

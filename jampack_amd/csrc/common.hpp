@@ -47,7 +47,7 @@ struct JpkProfPending { hipEvent_t a, b; int id; uint64_t units; };
 // the entropy decoder's status word.
 struct JpkMail {
     static constexpr int WORDS = 256, READ_WORDS = 16, SA_COUNT_WORDS = 5;
-    struct Dec { uint32_t posted[8]; uint32_t status; };              // device: k_dec_rank's status behind jpk_dev_rank_decode (ans_dec.hip)
+    struct Dec { uint32_t posted[8]; uint32_t status; };              // device: k_dec_rank's status behind jpk_dev_rank_decode (ans_dec_rank.hip; the entry is in ans_dec.hip)
     struct SaCounts { uint32_t m[2], npieces, lc, nrun, pad[3]; };    // the head of the suffix sort's SaState as a round leaves it: five words, stride 8
     struct SaStats { uint32_t round_m[JPK_SA_MAX_ROUNDS], round_lc[JPK_SA_MAX_ROUNDS], bits, depth, vmode; };   // SaState from round_m on
     union {                                  // words 0-15

@@ -1,5 +1,5 @@
-"""ans_dec.hip's front restated in plain Python: the scheme of k_dec_headers, k_dec_rans (with its ByteQueue) and k_dec_rle, and of the
-batch plumbing around them (cbase, rle_off / out_off, the cleared rank arrays, k_dec_order) -- window by window, symbol by symbol and
+"""The rANS decoder's front restated in plain Python: the scheme of k_dec_headers (ans_dec.hip), k_dec_rans (with its ByteQueue,
+ans_dec_rans.hip) and k_dec_rle (ans_dec_rank.hip), and of the batch plumbing around them in ans_dec.hip (cbase, rle_off / out_off, the cleared rank arrays, k_dec_order) -- window by window, symbol by symbol and
 pass by pass with the kernels' own intermediate values -- and the crafted inputs that reach their edges.  No GPU code is imported; what
 needs the oracle takes it as an argument.
 

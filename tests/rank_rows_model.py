@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the sorted-rank codec (rank.cpp:45-151) and of the row scheme by which k_dec_rank (jampack_amd/csrc/ans_dec.hip)
+"""Plain-Python restatement of the sorted-rank codec (rank.cpp:45-151) and of the row scheme by which k_dec_rank (jampack_amd/csrc/ans_dec_rank.hip)
 decodes it.  No GPU, no library: the crafted texts of test_rank_rows_model.py and test_gpu_rank_rows.py are built here, and walk() says which
 arms of the kernel a rank array reaches.
 

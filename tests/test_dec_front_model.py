@@ -1,4 +1,4 @@
-"""dec_front_model on the CPU: the restated scheme of ans_dec.hip's front (k_dec_headers, ByteQueue and k_dec_rans, k_dec_rle, the batch
+"""dec_front_model on the CPU: the restated scheme of the rANS decoder's front (ans_dec*.hip: k_dec_headers, ByteQueue and k_dec_rans, k_dec_rle, the batch
 plumbing with k_dec_order) gives the oracle's chunk table, RLE0 symbols, rank arrays and bytes on every crafted stream, every named arm is
 reached by the input made for it (REACH, pinned by name and lead), and every one-token change of the scheme changes the output of the input
 named in DETECTS or is shown to change none (dec_front_model.EQUIVALENT).  test_oracle_vs_ref.py pins the oracle to the reference build.

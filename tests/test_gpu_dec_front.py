@@ -1,4 +1,5 @@
-"""The rANS decoder's front (ans_dec.hip: k_dec_headers, k_dec_rans with its ByteQueue, k_dec_rle, and the batch plumbing around them:
+"""The rANS decoder's front (k_dec_headers in ans_dec.hip, k_dec_rans with its ByteQueue in ans_dec_rans.hip, k_dec_rle in ans_dec_rank.hip, and
+the batch plumbing around them in ans_dec.hip:
 cbase, rle_off / out_off, the cleared rank arrays, k_dec_order) on the crafted streams of dec_front_model, bit-exact against the oracle
 (which test_oracle_vs_ref.py pins to the reference build).  -m gpu
 

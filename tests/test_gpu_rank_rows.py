@@ -1,4 +1,4 @@
-"""k_dec_rank (ans_dec.hip) on the crafted texts of rank_rows_model: row top-ups, bucket ends, ranks at and above 64.  -m gpu
+"""k_dec_rank (ans_dec_rank.hip) on the crafted texts of rank_rows_model: row top-ups, bucket ends, ranks at and above 64.  -m gpu
 
 test_rank_rows_model.py shows, from the inputs alone, which arms of the kernel's row scheme every text reaches (fast iterations with and
 without zeros, the exit for a rank >= 64, inserts and front drops below and above 64, runs past the known entries, top-ups full, cut and
