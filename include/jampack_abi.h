@@ -603,22 +603,32 @@ JPK_API int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64_t 
  * a gap; the frame at o is taken and g moves behind its payload.  Frames and gaps tile [0, in_len) in order and without overlap; on an
  * undamaged archive the result is the frame table of the creators above, no gap, and for an archive in HBM no launch beyond theirs.
  * The index is a pure function of the archive bytes, kind and verify.  A header-shaped decoy inside a lost payload is taken only if
- * its chunk headers walk too; one that does is a frame of the index, and a read of it fails its crc (or, rarely, its decode).
+ * its chunk headers walk too; one that does is a frame of the index, and a read of it fails its crc (or, rarely, its decode) -- kinds
+ * 0 and 2; with kind 1 such a decoy is decoded like every candidate, fails, and is a JPK_JAM_GAP_STAGE gap, never a frame.
  * A gap is {archive_off, archive_len, frame = the number of recovered frames in front of it, why}:
  *   JPK_JAM_GAP_NOFRAME  no structurally valid frame starts in these archive bytes
- *   JPK_JAM_GAP_STAGE    (kind JPK_JAM_INDEX_STAGED) a structurally valid staged frame whose stages -- or, verify = 1, crc -- refuse it:
- *                        its raw size is unknown, so it cannot be a frame of the index; the gap is its span, header + payload
+ *   JPK_JAM_GAP_STAGE    (kind JPK_JAM_INDEX_STAGED) a structurally valid staged frame whose stages -- or, verify = 1, crc -- refuse it;
+ *                        (kind JPK_JAM_INDEX_CLI) a structurally valid frame that a stage refuses, that decodes to more than its
+ *                        BlockSize or that fails its crc: its raw size is unknown, so it cannot be a frame of the index; the gap is
+ *                        its span, header + payload
  * kind JPK_JAM_INDEX_PLAIN: verify must be 0; frames are unverified as in a plain index; the host form makes no device call.
  * kind JPK_JAM_INDEX_STAGED: staged frames are sized pass by pass as by jpk_dev_jam_staged_index_create (verify as there); a pass holds
  * frames that lie back to back; the host form looks for a device only when the walk found a staged frame.
- * kind JPK_JAM_INDEX_CLI: JPK_E_ARG -- a stock-CLI index comes from a decode that stops at a bad frame; continuing it is future work.
+ * kind JPK_JAM_INDEX_CLI: verify must be 1 (verify = 0: JPK_E_ARG) -- every frame of a stock-CLI index has been decoded and has met its
+ * crc, as with jpk_dev_jam_cli_index_create.  Structurally valid means what the stock-CLI frame walk means: no staged bit, and a
+ * declared entropy-decoded size of at most 1.05 x BlockSize + 4096.  Every structurally valid frame then goes through the whole
+ * stock-CLI stage chain and the crc, pass by pass, each with a status of its own; a pass holds frames that lie back to back, at most
+ * JPK_JAM_PASS_FRAMES of them and 4 GiB of BlockSize; there is no output buffer.  f.raw comes from that decode.  The walk goes on behind
+ * a frame that fails.  The host form walks on the host, looks for a device only when the walk found a frame, and stages pass by pass.
+ * The price is one full stage chain per structurally valid candidate, decoys included.
  * The index has the requested kind, no bad frame (jpk_jam_index_info and the readers see a plain table), raw offsets that count the
  * recovered frames only -- a gap holds no raw bytes --, and jpk_jam_index_info / _frame / _kind / _frame_kind / _destroy,
  * jpk_dev_jam_read and jpk_jam_read take it unchanged.  *gaps (may be NULL) = the number of gaps.  Arguments are checked before a
  * device is looked for; in_len == 0 gives an empty index.  Cost on hostile input: every archive byte is scanned once per search that
  * reaches it, every plausible header costs one chunk-header walk of its payload (DESIGN 4.6 has the bound). */
 #define JPK_JAM_GAP_NOFRAME 0   /* no structurally valid frame starts in these archive bytes */
-#define JPK_JAM_GAP_STAGE   1   /* a structurally valid staged frame whose stages (or, verify = 1, crc) refuse it: its raw size is unknown */
+#define JPK_JAM_GAP_STAGE   1   /* a structurally valid staged frame (kind 2) whose stages (or, verify = 1, crc) refuse it, or frame of the
+                                 * stock CLI (kind 1) that fails its stage chain or its crc: its raw size is unknown */
 JPK_API int jpk_dev_jam_index_recover(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps);
 JPK_API int jpk_jam_index_recover(const uint8_t *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *gaps);
 JPK_API int jpk_jam_index_gaps(const jpk_jam_index *index);   /* count; 0 for an index of the existing creators; JPK_E_ARG for NULL */
@@ -636,6 +646,19 @@ JPK_API int jpk_dev_jam_salvage(jpk_ctx *ctx, const jpk_jam_index *index, const 
 /* host-buffer form through the calling thread's pooled context (the arguments and the capacity are checked before a device is looked for) */
 JPK_API int jpk_jam_salvage(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, uint8_t *out, int64_t out_cap, int64_t *out_len, int32_t *frame_status,
                             int32_t *failed);
+/* The archive that holds exactly the kept frames of an index, back to back: for every frame k of the index with frame_status == NULL or
+ * frame_status[k] == JPK_OK, in order, its 15 header bytes (at payload_off - 15 of the archive) and its payload, copied unchanged.  *out_len
+ * = the bytes written, *frames (may be NULL) = the frames kept.  in_len must be the index's archive length (JPK_E_ARG).  out_cap too
+ * small: JPK_E_CAPACITY, *out_len = the size needed, nothing written.  Nothing outside [d_in, d_in + in_len) is read and nothing outside
+ * [d_out, d_out + *out_len) is written; d_in and d_out at any alignment; the buffers must not overlap.  No frame is decoded: pass the
+ * frame_status of a salvage to drop frames that fail their decode or crc.  Takes any index, recovered or not, of any kind; the result
+ * of a recovered one is an archive that the stock decoder and every whole-archive decoder here read to its end.  One k_jam_gather
+ * launch, a piece per kept frame; an index without a kept frame gives *out_len = 0 and no launch.  Arguments and capacity are checked
+ * before a device is looked for. */
+JPK_API int jpk_dev_jam_repair(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, const int32_t *frame_status,
+                               uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames);
+JPK_API int jpk_jam_repair(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, const int32_t *frame_status, uint8_t *out,
+                           int64_t out_cap, int64_t *out_len, int32_t *frames);   /* host memory: memcpy, no device call */
 /* probe: the offsets of the first max_cands (1..65536) plausible frame headers that start in [start, start + window) of d_in[0..in_len),
  * ascending, from one run of k_jam_scan_count / the prefix scan / k_jam_scan_emit; window <= 2^30; stateless, reads only.  offsets holds
  * max_cands entries */

@@ -290,13 +290,20 @@ def jam_staged_index(stream, verify: bool = False) -> JamIndex:
     return JamIndex(h, bad.value)
 
 
-def jam_recover_index(stream, kind: int = JAM_INDEX_PLAIN, verify: bool = False) -> JamIndex:
+def _recover_verify(kind: int, verify) -> int:
+    """verify=None is the kind's own value: 1 for a stock-CLI index, whose every frame is decoded, 0 otherwise"""
+    return int(kind == JAM_INDEX_CLI) if verify is None else int(verify)
+
+
+def jam_recover_index(stream, kind: int = JAM_INDEX_PLAIN, verify: bool | None = None) -> JamIndex:
     """jpk_jam_index_recover: the index of a damaged archive in host memory -- the walk goes on behind a bad frame at the next offset
     where a structurally valid frame starts, and what it skipped is in `gaps`.  kind 0: plain frames, no device call; kind 2: plain and
-    staged frames, a staged frame sized (verify=True: decoded and checked) on the device, one its stages refuse becomes a gap."""
+    staged frames, a staged frame sized (verify=True: decoded and checked) on the device, one its stages refuse becomes a gap; kind 1:
+    frames of the stock CLI, every structurally valid one decoded and checked on the device (verify must be True), one that fails
+    becomes a gap.  verify=None is the kind's own value: True for kind 1, False otherwise."""
     c = _np_u8(stream)
     h, g = C.c_void_p(), C.c_int32(0)
-    _chk(lib().jpk_jam_index_recover(_ptr(c), len(c), int(kind), int(verify), C.byref(h), C.byref(g)), "jpk_jam_index_recover")
+    _chk(lib().jpk_jam_index_recover(_ptr(c), len(c), int(kind), _recover_verify(kind, verify), C.byref(h), C.byref(g)), "jpk_jam_index_recover")
     return JamIndex(h, -1)
 
 
@@ -315,6 +322,27 @@ def jam_salvage(stream, index: JamIndex | None = None, kind: int = JAM_INDEX_PLA
     finally:
         if index is None:
             ix.close()
+
+
+def _frame_status(index: JamIndex, frame_status):
+    """the frame_status argument of the repair entries: NULL, or one int32 per frame of the index"""
+    if frame_status is None:
+        return None
+    if len(frame_status) != index.frames:
+        raise ValueError("frame_status needs one entry per frame of the index")
+    return (C.c_int32 * max(index.frames, 1))(*[int(s) for s in frame_status])
+
+
+def jam_repair(stream, index: JamIndex, frame_status=None) -> np.ndarray:
+    """jpk_jam_repair: the archive that holds exactly the kept frames of the index -- every frame, or with frame_status (a salvage's) the
+    ones whose status is 0 --, headers and payloads copied unchanged, back to back.  Host code; no frame is decoded.  The result of a
+    recovered index is an archive every whole-archive decoder reads to its end."""
+    c = _np_u8(stream)
+    st = _frame_status(index, frame_status)
+    out = np.empty(max(len(c), 1), dtype=np.uint8)
+    n, k = C.c_int64(0), C.c_int32(0)
+    _chk(lib().jpk_jam_repair(index._h, _ptr(c), len(c), st, out.ctypes.data, len(c), C.byref(n), C.byref(k)), "jpk_jam_repair")
+    return out[: n.value].copy()
 
 
 def lz77_size(stream, cap: int) -> int:
@@ -904,12 +932,23 @@ class Context:
         _chk(lib().jpk_dev_jam_staged_index_create(self._h, _dptr(d_in), in_len, int(verify), C.byref(h), C.byref(bad)), "jpk_dev_jam_staged_index_create")
         return JamIndex(h, bad.value)
 
-    def jam_recover_index(self, d_in, in_len, kind: int = JAM_INDEX_PLAIN, verify: bool = False) -> JamIndex:
+    def jam_recover_index(self, d_in, in_len, kind: int = JAM_INDEX_PLAIN, verify: bool | None = None) -> JamIndex:
         """jpk_dev_jam_index_recover: the index of a damaged archive in HBM, past its damage (see jam_recover_index); where the frame walk
-        stops, k_jam_scan_* look for the next frame"""
+        stops, k_jam_scan_* look for the next frame.  kind 1 (frames of the stock CLI): every structurally valid frame goes through the
+        stage chain and its crc, and one that fails is a gap.  verify=None is the kind's own value: True for kind 1, False otherwise."""
         h, g = C.c_void_p(), C.c_int32(0)
-        _chk(lib().jpk_dev_jam_index_recover(self._h, _dptr(d_in), in_len, int(kind), int(verify), C.byref(h), C.byref(g)), "jpk_dev_jam_index_recover")
+        _chk(lib().jpk_dev_jam_index_recover(self._h, _dptr(d_in), in_len, int(kind), _recover_verify(kind, verify), C.byref(h), C.byref(g)),
+             "jpk_dev_jam_index_recover")
         return JamIndex(h, -1)
+
+    def jam_repair(self, index: JamIndex, d_in, in_len, d_out, out_cap, frame_status=None):
+        """jpk_dev_jam_repair: the kept frames of the index (every one, or with frame_status the ones whose status is 0), headers and
+        payloads unchanged, back to back in d_out -> (out_len, frames).  One gather launch, no decode.  Raises JampackError(-2) when
+        out_cap is too small (nothing is written)."""
+        n, k = C.c_int64(0), C.c_int32(0)
+        _chk(lib().jpk_dev_jam_repair(self._h, index._h, _dptr(d_in), in_len, _frame_status(index, frame_status), _dptr(d_out), out_cap, C.byref(n), C.byref(k)),
+             "jpk_dev_jam_repair")
+        return n.value, k.value
 
     def jam_salvage(self, index: JamIndex, d_in, in_len, d_out, out_cap):
         """jpk_dev_jam_salvage: every frame of the index into d_out at its raw offset -> (raw_len, frame_status); a failed frame has

@@ -1,5 +1,5 @@
 // jam_archive.hip -- whole .jam archives of the C ABI (include/jampack_abi.h): the frame walks, the batched compress and decompress
-// calls of plain and stock-CLI archives with their host-buffer forms, the index + range reads, and the index and the salvage of damaged
+// calls of plain and stock-CLI archives with their host-buffer forms, the index + range reads, and the index, the salvage and the repair of damaged
 // archives (the rule they share with the kernels: jam_resync.hpp).  Host drivers only: the kernels
 // are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines in abi_blocks.hip and the context pool in abi_pool.hip.
 #include <algorithm>
@@ -1101,11 +1101,12 @@ extern "C" int jpk_jam_cli_index_create(const uint8_t *in, int64_t in_len, jpk_j
 }
 
 namespace {
-// The staged frames among fr[k, e) (one pass: the limits of jpk_dev_jam_staged_decompress) through jam_cli_pass without an output -- verify:
-// the whole staged stage list and the header crcs; otherwise its sizes form, which stops in front of the expansion.  The payload of a frame
-// is at d_in + (payload_off - a0).  st[i - k] = JPK_OK and fr[i].raw = its raw size, or the status of the stage it failed (prefix: also of
-// every staged frame behind the first failing one); a plain frame keeps the raw size of the walk, is not decoded and is JPK_OK.
-int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool verify, bool prefix, int32_t *st)
+// The chained frames among fr[k, e) (one pass: the limits of the whole-archive decode of their kind) through jam_cli_pass without an output
+// -- cli: every frame, with the stock-CLI stage list; otherwise the staged ones, with the staged list.  verify: the whole stage list and the
+// header crcs; otherwise (staged frames only) its sizes form, which stops in front of the expansion.  The payload of a frame is at d_in +
+// (payload_off - a0).  st[i - k] = JPK_OK and fr[i].raw = its raw size, or the status of the stage it failed (prefix: also of every chained
+// frame behind the first failing one); a plain frame keeps the raw size of the walk, is not decoded and is JPK_OK.
+int jam_chain_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool cli, bool verify, bool prefix, int32_t *st)
 {
     std::vector<size_t> sidx;
     std::vector<const uint8_t *> sin;
@@ -1114,7 +1115,7 @@ int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vec
     for (size_t i = k; i < e; i++) {
         const JamFrame &f = fr[i];
         st[i - k] = JPK_OK;
-        if (!f.staged) continue;
+        if (!cli && !f.staged) continue;
         sidx.push_back(i);
         sin.push_back(d_in + (f.payload_off - a0)); slens.push_back(f.psize); bsz.push_back(f.block_size); scrc.push_back(f.crc);
     }
@@ -1126,7 +1127,7 @@ int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vec
     // a frame that declares more than its BlockSize is a bad frame, expanded or not
     CliPass p = jam_chain_pass(s, sin.data(), slens.data(), s.a.data(), bsz.data(), scrc.data());
     p.prefix = prefix;
-    p.staged = true;
+    p.staged = !cli;
     p.sizes = !verify;
     JPK_TRY(jam_cli_pass(ctx, p, sraw.data(), sst.data()));
     for (size_t q = 0; q < ns; q++) {
@@ -1134,6 +1135,15 @@ int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vec
         if (sst[q] == JPK_OK) fr[sidx[q]].raw = sraw[q];
     }
     return JPK_OK;
+}
+int jam_staged_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool verify, bool prefix, int32_t *st)
+{
+    return jam_chain_size_pass(ctx, d_in, a0, fr, k, e, false, verify, prefix, st);
+}
+// every frame of a stock-CLI pass decoded into its slot A and checked against its crc (the passes of jpk_dev_jam_cli_index_create)
+int jam_cli_size_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t a0, std::vector<JamFrame> &fr, size_t k, size_t e, bool prefix, int32_t *st)
+{
+    return jam_chain_size_pass(ctx, d_in, a0, fr, k, e, true, true, prefix, st);
 }
 
 // The frames of an index of kind JPK_JAM_INDEX_STAGED for an archive in HBM: the walk, then jam_staged_size_pass per pass.
@@ -1285,7 +1295,10 @@ extern "C" int jpk_jam_read(const jpk_jam_index *index, const uint8_t *in, int64
 // jpk_(dev_)jam_index_recover run the resync walk of jam_resync.hpp -- one loop for both forms, over JamDevSrc or jrs::HostSrc: where
 // the frame walk stops, the first structurally valid frame behind it is searched (in HBM: k_jam_scan_* for the plausible headers of a
 // window, jpk_ans_decoded_sizes for a batch of them), and what lies between becomes a gap of the index.  An undamaged archive is one run
-// of the frame walk and launches no scan.  jpk_(dev_)jam_salvage is one range per frame through the reader above.
+// of the frame walk and launches no scan.  The frames of a stock-CLI archive (kind 1) then go through their stage chain and meet their
+// crcs, pass by pass (jam_cli_size_pass, every frame with a status of its own): that is where their raw sizes come from, and a frame that
+// fails is a gap over its own span.  jpk_(dev_)jam_salvage is one range per frame through the reader above; jpk_(dev_)jam_repair copies the
+// spans of the kept frames back to back and decodes nothing.
 namespace {
 std::atomic<int64_t> g_recover_window{jrs::DEFAULT_WINDOW};
 std::atomic<int32_t> g_recover_cands{jrs::DEFAULT_CANDS};
@@ -1322,7 +1335,7 @@ struct JamDevSrc {
     jpk_ctx *ctx;
     const uint8_t *d_in;
     int64_t in_len;
-    int kind;                                         // JAM_PLAIN or JAM_STAGED
+    int kind;                                         // JAM_PLAIN, JAM_CLI or JAM_STAGED
     std::vector<JamWalkFrame> c;                      // the candidates of the last cands()
     template <class OnFrame> int run(int64_t g, OnFrame on_frame, int64_t *stop)
     {
@@ -1348,7 +1361,7 @@ struct JamDevSrc {
         JPK_TRY(jpk_ans_decoded_sizes(ctx, n, ins.data(), lens.data(), dec.data(), st.data()));
         *hit = -1;
         for (int32_t i = 0; i < n && *hit < 0; i++)
-            if (jam_frame_of(c[(size_t)i], st[(size_t)i], dec[(size_t)i], false, f)) *hit = i;
+            if (jam_frame_of(c[(size_t)i], st[(size_t)i], dec[(size_t)i], kind == JAM_CLI, f)) *hit = i;
         return JPK_OK;
     }
 };
@@ -1362,11 +1375,11 @@ template <class Src> int jam_recover_walk(Src &src, int64_t in_len, std::vector<
                      [&](int64_t o, int64_t n) { gaps.push_back(JamGap{o, n, (int32_t)fr.size(), JPK_JAM_GAP_NOFRAME}); });
 }
 
-// frames [k, e) form the sizing pass that starts at frame k: the limits of jam_pass_end, and frames that lie back to back in the
-// archive -- a pass never spans a gap, so the host form can stage it as one piece
-size_t jam_recover_pass_end(const std::vector<JamFrame> &fr, size_t k)
+// frames [k, e) form the sizing pass that starts at frame k: the limits of jam_pass_end (cli: a frame weighs its BlockSize), and frames
+// that lie back to back in the archive -- a pass never spans a gap, so the host form can stage it as one piece
+size_t jam_recover_pass_end(const std::vector<JamFrame> &fr, size_t k, bool cli)
 {
-    const size_t lim = jam_pass_end(fr, k, false);
+    const size_t lim = jam_pass_end(fr, k, cli);
     size_t e = k + 1;
     while (e < lim && fr[e].payload_off - JPK_JAM_HEADER_BYTES == fr[e - 1].payload_off + fr[e - 1].psize) e++;
     return e;
@@ -1392,24 +1405,29 @@ jpk_jam_index *jam_recover_make(const std::vector<JamFrame> &fr, const std::vect
 
 bool jam_recover_args_ok(const void *in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index)
 {
-    // (an index of a stock-CLI archive comes from a decode that stops at a bad frame: not recovered here)
-    return index && in_len >= 0 && (in_len == 0 || in) && (kind == JPK_JAM_INDEX_PLAIN || kind == JPK_JAM_INDEX_STAGED) && jam_verify_ok(verify) &&
-           !(kind == JPK_JAM_INDEX_PLAIN && verify);
+    // (a plain index verifies nothing; every frame of a stock-CLI index has been decoded: its raw size is known only behind its last stage)
+    return index && in_len >= 0 && (in_len == 0 || in) && (kind == JPK_JAM_INDEX_PLAIN || kind == JPK_JAM_INDEX_CLI || kind == JPK_JAM_INDEX_STAGED) &&
+           jam_verify_ok(verify) && !(kind == JPK_JAM_INDEX_PLAIN && verify) && !(kind == JPK_JAM_INDEX_CLI && !verify);
 }
+
+// what the walks call the archive of an index kind
+int jam_recover_walk_kind(int32_t kind) { return kind == JPK_JAM_INDEX_STAGED ? JAM_STAGED : kind == JPK_JAM_INDEX_CLI ? JAM_CLI : JAM_PLAIN; }
 
 int jam_recover_dev(jpk_ctx *ctx, const uint8_t *d_in, int64_t in_len, int32_t kind, int32_t verify, jpk_jam_index **index, int32_t *ngaps)
 {
     std::vector<JamFrame> fr;
     std::vector<JamGap> gaps;
     std::vector<int32_t> st;
+    const bool cli = kind == JPK_JAM_INDEX_CLI;
     if (in_len > 0) {
         JPK_HIP(hipSetDevice(ctx->device));
-        JamDevSrc src{ctx, d_in, in_len, kind == JPK_JAM_INDEX_STAGED ? JAM_STAGED : JAM_PLAIN, {}};
+        JamDevSrc src{ctx, d_in, in_len, jam_recover_walk_kind(kind), {}};
         JPK_TRY(jam_recover_walk(src, in_len, fr, gaps));
         st.assign(fr.size(), JPK_OK);
         for (size_t k = 0; k < fr.size();) {
-            const size_t e = jam_recover_pass_end(fr, k);
-            JPK_TRY(jam_staged_size_pass(ctx, d_in, 0, fr, k, e, verify != 0, false, st.data() + k));
+            const size_t e = jam_recover_pass_end(fr, k, cli);
+            if (cli) JPK_TRY(jam_cli_size_pass(ctx, d_in, 0, fr, k, e, false, st.data() + k));
+            else JPK_TRY(jam_staged_size_pass(ctx, d_in, 0, fr, k, e, verify != 0, false, st.data() + k));
             k = e;
         }
     }
@@ -1424,19 +1442,22 @@ int jam_recover_host(const uint8_t *in, int64_t in_len, int32_t kind, int32_t ve
     std::vector<JamGap> gaps;
     const int32_t K = g_recover_cands.load();
     std::vector<int64_t> offs((size_t)(K < 1 ? jrs::DEFAULT_CANDS : K));
-    jrs::HostSrc src{in, in_len, kind == JPK_JAM_INDEX_STAGED, offs.data()};
+    const bool cli = kind == JPK_JAM_INDEX_CLI;
+    jrs::HostSrc src{in, in_len, kind == JPK_JAM_INDEX_STAGED, offs.data(), cli};
     JPK_TRY(jam_recover_walk(src, in_len, fr, gaps));
     std::vector<int32_t> st(fr.size(), JPK_OK);
-    // an archive without a staged frame is indexed by the walk alone: no device is looked for
+    // an archive without a chained frame (of a stock-CLI archive, every frame is one) is indexed by the walk alone: no device is looked for
+    auto chained = [cli](const JamFrame &f) { return cli || f.staged; };
     jpk_ctx *ctx = nullptr;
-    if (std::any_of(fr.begin(), fr.end(), [](const JamFrame &f) { return f.staged; })) JPK_TRY(jpk_host_enter(&ctx, 0));
+    if (std::any_of(fr.begin(), fr.end(), chained)) JPK_TRY(jpk_host_enter(&ctx, 0));
     for (size_t k = 0; k < fr.size();) {
-        const size_t e = jam_recover_pass_end(fr, k);
-        if (std::any_of(fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e, [](const JamFrame &f) { return f.staged; })) {
+        const size_t e = jam_recover_pass_end(fr, k, cli);
+        if (std::any_of(fr.begin() + (ptrdiff_t)k, fr.begin() + (ptrdiff_t)e, chained)) {
             // staged one pass at a time, jam_stage_frames: the frames of the pass lie back to back
             int64_t len = 0, a0 = 0;
             JPK_TRY(jam_stage_frames(ctx, in, fr, k, e, &len, &a0));
-            const int rc = jam_staged_size_pass(ctx, ctx->stage_in, a0, fr, k, e, verify != 0, false, st.data() + k);
+            const int rc = cli ? jam_cli_size_pass(ctx, ctx->stage_in, a0, fr, k, e, false, st.data() + k)
+                               : jam_staged_size_pass(ctx, ctx->stage_in, a0, fr, k, e, verify != 0, false, st.data() + k);
             JPK_HIP(hipStreamSynchronize(ctx->stream));
             JPK_TRY(rc);
         }
@@ -1590,4 +1611,68 @@ extern "C" int jpk_jam_salvage(const jpk_jam_index *index, const uint8_t *in, in
     JPK_HIP(hipMemcpyAsync(out, ctx->stage_res, (size_t)raw_len, hipMemcpyDeviceToHost, ctx->stream));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
     return JPK_OK;
+}
+
+// ---- repair: the kept frames of an index, their headers and payloads unchanged, back to back -- an archive every whole-archive decoder reads to its end
+namespace {
+struct JamSpan { int64_t off, len; };       // a frame in the archive: its header and its payload
+
+// the checks of both repair entries, the spans of the frames that stay and the capacity answer: nothing is touched before they pass
+int jam_repair_plan(const jpk_jam_index *ix, const void *in, int64_t in_len, const int32_t *frame_status, const void *out, int64_t out_cap, int64_t *out_len,
+                    int32_t *frames, std::vector<JamSpan> &keep)
+{
+    if (!ix || !out_len || in_len != ix->archive_len || out_cap < 0 || (in_len > 0 && !in) || (out_cap > 0 && !out)) return JPK_E_ARG;
+    int64_t total = 0;
+    for (size_t k = 0; k < ix->fr.size(); k++) {
+        if (frame_status && frame_status[k] != JPK_OK) continue;
+        const JamFrame &f = ix->fr[k];
+        keep.push_back(JamSpan{f.payload_off - JPK_JAM_HEADER_BYTES, (int64_t)JPK_JAM_HEADER_BYTES + f.psize});
+        total += keep.back().len;
+    }
+    *out_len = total;
+    if (frames) *frames = (int32_t)keep.size();
+    return total > out_cap ? JPK_E_CAPACITY : JPK_OK;
+}
+}  // namespace
+
+extern "C" int jpk_dev_jam_repair(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, const int32_t *frame_status, uint8_t *d_out,
+                                  int64_t out_cap, int64_t *out_len, int32_t *frames)
+{
+    // (the argument checks and the capacity answer come before the first device call, and an index without a kept frame makes none)
+    if (!ctx) return JPK_E_ARG;
+    try {
+        std::vector<JamSpan> keep;
+        JPK_TRY(jam_repair_plan(index, d_in, in_len, frame_status, d_out, out_cap, out_len, frames, keep));
+        if (keep.empty()) return JPK_OK;
+        JPK_HIP(hipSetDevice(ctx->device));
+        // one piece per kept frame; the table is as long as the index, not as a pass
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, keep.size() * sizeof(JamGatherPiece)));
+        std::vector<JamGatherPiece> tab;
+        tab.reserve(keep.size());
+        uint64_t words = 0, pos = 0;
+        for (const JamSpan &s : keep) {
+            jam_piece_add(tab, &words, d_in + s.off, d_out + pos, (uint64_t)s.len, d_in, d_in + in_len);
+            pos += (uint64_t)s.len;
+        }
+        JPK_TRY(jam_gather(ctx, reinterpret_cast<JamGatherPiece *>(ctx->jam_scratch), tab, words, pos));
+        if (ctx->prof_on) jpk_prof_resolve(ctx);
+        return JPK_OK;
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_jam_repair(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, const int32_t *frame_status, uint8_t *out, int64_t out_cap,
+                              int64_t *out_len, int32_t *frames)
+{
+    try {
+        std::vector<JamSpan> keep;
+        JPK_TRY(jam_repair_plan(index, in, in_len, frame_status, out, out_cap, out_len, frames, keep));
+        int64_t pos = 0;
+        for (const JamSpan &s : keep) { memcpy(out + pos, in + s.off, (size_t)s.len); pos += s.len; }
+        return JPK_OK;
+    } catch (const std::bad_alloc &) {
+        return JPK_E_ALLOC;
+    }
 }

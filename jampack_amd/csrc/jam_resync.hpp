@@ -1,12 +1,13 @@
 // jam_resync.hpp -- the rule by which a damaged .jam archive is walked past its damage ("Damaged archives"), written once for
-// the host drivers (jam_archive.hip), the kernels (jam.hip: the header test of k_jam_walk and k_jam_scan_*) and a stand-alone program
-// (tests/jam_resync_rule_host.cpp) that runs it under a sanitizer:
+// the host drivers (jam_archive.hip), the kernels (jam.hip: the header test of k_jam_walk and k_jam_scan_*) and two stand-alone programs
+// (tests/jam_resync_rule_host.cpp, and tests/jam_resync_cli_rule_host.cpp for stock-CLI archives) that run it under a sanitizer:
 //   fields_ok / magic_ok   a plausible frame header at an offset -- exactly what k_jam_walk and jpk_jam_header_parse accept
 //   ans_decoded_size       the chunk-header walk of a payload (jpk_ans_decoded_size is this function)
 //   decoded_ok             what a payload may declare against its BlockSize
 //   frame_at               a structurally valid frame in host memory: the three together, no more and no fewer than the walks apply
 //   walk                   the resync walk, a template over where candidates come from and how a batch of them is validated; HostSrc is
-//                          that pair for an archive in host memory
+//                          that pair for an archive in host memory -- of plain frames, of plain and staged ones, or (cli) of the stock CLI,
+//                          whose frames may declare what a chained frame may (decoded_ok)
 // Pure functions, no HIP header: magic_ok and fields_ok compile for the device too, the rest is host code.
 #pragma once
 #include <stdint.h>
@@ -143,16 +144,19 @@ template <class Src, class OnFrame, class OnGap> int walk(Src &src, int64_t in_l
     return JPK_OK;
 }
 
-// Src for an archive in host memory (plain frames, with staged_ok staged ones too; stock-CLI archives are not recovered)
+// Src for an archive in host memory: plain frames, with staged_ok staged ones too, or with cli (and staged_ok false: a stock-CLI header
+// has no staged bit) the frames of the stock CLI, every one measured against the slot of a chained frame.  cli stays the last member:
+// HostSrc{in, in_len, staged_ok, offs} is the source of kinds 0 and 2
 struct HostSrc {
     const uint8_t *in;
     int64_t in_len;
     bool staged_ok;
     int64_t *offs;           // room for K offsets
+    bool cli = false;
     template <class OnFrame> int run(int64_t g, OnFrame on_frame, int64_t *stop)
     {
         JamFrame f;
-        while (g < in_len && frame_at(in, in_len, g, staged_ok, false, &f)) { on_frame(f); g = f.payload_off + f.psize; }
+        while (g < in_len && frame_at(in, in_len, g, staged_ok, cli, &f)) { on_frame(f); g = f.payload_off + f.psize; }
         *stop = g;
         return JPK_OK;
     }
@@ -175,7 +179,7 @@ struct HostSrc {
     int first_valid(int32_t n, int32_t *hit, JamFrame *f)
     {
         *hit = -1;
-        for (int32_t i = 0; i < n && *hit < 0; i++) if (frame_at(in, in_len, offs[i], staged_ok, false, f)) *hit = i;
+        for (int32_t i = 0; i < n && *hit < 0; i++) if (frame_at(in, in_len, offs[i], staged_ok, cli, f)) *hit = i;
         return JPK_OK;
     }
 };

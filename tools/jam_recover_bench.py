@@ -10,12 +10,18 @@
        measured once more over 1 GiB of random bytes, which do not
   (c)  Context.jam_salvage through a plain index against Context.jam_decompress (which this change leaves as it was) on the same
        undamaged archives
+  (d)  stock-CLI archives (kind 1), 64 frames of 1 MiB: Context.jam_recover_index(kind 1) against Context.jam_cli_index on the undamaged
+       archive -- the same passes, no scan launch --, the recover of that archive with 1 and with 8 lost headers (one pass fewer frames,
+       one search per lost header), and Context.jam_repair of the index with 1 lost header against a device-to-device copy of the bytes
+       it writes
 
 Workloads: corpus text as 64 frames of 1 MiB and as 4 frames of 64 MiB.  After one warm-up of each, the variants are timed in turn (every round starts one
 variant further on), --reps rounds, and the medians reported; every call ends in a device synchronise.  It is one GPU step: run it under a time limit of
 its own,
 
-  timeout -k 10 900 python tools/jam_recover_bench.py [--reps 5] [--out profiles/jam_recover.txt]
+  timeout -k 10 900 python tools/jam_recover_bench.py [--reps 5] [--parts plain,cli] [--out profiles/jam_recover.txt]
+
+--parts cli measures (d) alone; its lines are appended to the profile behind those of the other parts.
 """
 import argparse
 import os
@@ -52,16 +58,101 @@ def timed(order, run, reps, sync):
     return {k: float(np.median(v)) * 1e3 for k, v in times.items()}, times
 
 
+def cli_part(torch, jam, ctx, reps, sync):
+    """(d): the lines of the stock-CLI measurements"""
+    frames, bs = 64, MiB
+    n = frames * bs
+    d_raw = workload(torch, jam, frames, bs)
+    bound = jam.jam_cli_compress_bound(n, bs)
+    d_arch = torch.empty(bound + 64, dtype=torch.uint8, device="cuda")
+    alen = ctx.jam_cli_compress(d_raw, n, bs, d_arch, bound)
+    ref = ctx.jam_cli_index(d_arch, alen)
+    assert (ref.frames, ref.raw_len, ref.bad_frame) == (frames, n, -1)
+    starts = [ref.frame(k)[2] - 15 for k in range(frames)]
+    lost = {1: [31], 8: list(range(3, 64, 8))}
+    d_lost = {}
+    for m, ks in lost.items():
+        d_lost[m] = d_arch[:alen].clone()
+        for k in ks:
+            d_lost[m][starts[k]] ^= 1
+    ix1 = ctx.jam_recover_index(d_lost[1], alen, jam.JAM_INDEX_CLI)
+    assert ix1.frames == frames - 1 and len(ix1.gaps) == 1
+    keep = alen - ix1.gaps[0][1]
+    d_fix, d_copy = torch.empty(alen + 64, dtype=torch.uint8, device="cuda"), torch.empty(alen + 64, dtype=torch.uint8, device="cuda")
+
+    def run(k):
+        if k == "cli_index":
+            jx = ctx.jam_cli_index(d_arch, alen)
+            assert (jx.frames, jx.raw_len, jx.bad_frame) == (frames, n, -1)
+            jx.close()
+        elif k == "recover":
+            jx = ctx.jam_recover_index(d_arch, alen, jam.JAM_INDEX_CLI)
+            assert (jx.frames, jx.raw_len, jx.gaps) == (frames, n, [])
+            jx.close()
+        elif k in ("lost1", "lost8"):
+            m = int(k[4:])
+            jx = ctx.jam_recover_index(d_lost[m], alen, jam.JAM_INDEX_CLI)
+            assert (jx.frames, len(jx.gaps)) == (frames - m, m)
+            jx.close()
+        elif k == "repair":
+            assert ctx.jam_repair(ix1, d_lost[1], alen, d_fix, alen) == (keep, frames - 1)
+        else:
+            d_copy[:keep].copy_(d_lost[1][:keep])
+
+    ctx.profile_enable(2)
+    for k in ("cli_index", "recover"):                      # warm-up: arenas, scratch, code objects
+        run(k)
+    sync()
+    scans = [r for r in ctx.profile_table() if r["name"] == "k_jam_scan_*"]
+    ctx.profile_enable(0)
+    assert not scans, scans                                 # an undamaged archive launches no scan
+    for k in ("lost1", "lost8", "repair", "copy"):
+        run(k)
+    sync()
+    gap = ix1.gaps[0]
+    want = torch.cat([d_lost[1][: gap[0]], d_lost[1][gap[0] + gap[1]: alen]])
+    assert torch.equal(d_fix[:keep], want)
+    med, times = timed(("cli_index", "recover"), run, reps, sync)
+    for order in (("lost1", "lost8"), ("repair", "copy")):
+        m2, t2 = timed(order, run, reps, sync)
+        med.update(m2)
+        times.update(t2)
+    ratio = med["recover"] / med["cli_index"]
+    return [
+        f"-- (d) stock-CLI archive, {frames} frames of {bs // MiB} MiB: archive {alen} bytes, raw {n} bytes; median of {reps} alternating rounds after one warm-up",
+        f"(d) jam_cli_index                                {med['cli_index']:9.2f} ms",
+        f"(d) jam_recover_index, kind 1 (no gap, no scan)  {med['recover']:9.2f} ms   recover / cli_index = {ratio:.3f}",
+        f"(d) jam_recover_index, kind 1, 1 lost header     {med['lost1']:9.2f} ms",
+        f"(d) jam_recover_index, kind 1, 8 lost headers    {med['lost8']:9.2f} ms",
+        f"(d) jam_repair, 63 kept frames, {keep} bytes  {med['repair']:9.3f} ms   ({keep / med['repair'] / 1e6:.1f} GB/s)",
+        f"(d) device-to-device copy of {keep} bytes     {med['copy']:9.3f} ms   ({keep / med['copy'] / 1e6:.1f} GB/s)   repair / copy = {med['repair'] / med['copy']:.2f}",
+        "all rounds (ms): " + "; ".join(f"{k} " + " ".join(f"{t * 1e3:.3f}" for t in times[k]) for k in times),
+        f"kind-1 recover of an undamaged archive within 3 % of the index creator: {'yes' if abs(ratio - 1) <= 0.03 else 'NO'} (recover / cli_index = {ratio:.3f})",
+    ]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--parts", default="plain,cli", help="plain: (a)-(c) on plain archives; cli: (d) on a stock-CLI archive")
     a = ap.parse_args()
+    parts = a.parts.split(",")
 
     import torch                                            # first: torch brings its own HIP runtime, and the library must share it
     import jampack_amd as jam
     sync = torch.cuda.synchronize
     ctx = jam.Context(0, torch.cuda.current_stream().cuda_stream)
+    if "plain" not in parts:
+        lines = cli_part(torch, jam, ctx, a.reps, sync)
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write(text)
+        ctx.close()
+        return
     lines = ["tools/jam_recover_bench.py: plain archives of corpus text in HBM",
              f"device: {torch.cuda.get_device_name(0)}; median of {a.reps} alternating rounds after one warm-up, wall clock with a device synchronise"]
     answers = []
@@ -186,6 +277,8 @@ def main():
             frames, bs, ri, sd = x
             lines.append(f"{frames} x {bs // MiB} MiB: salvage within 3 % of the whole-archive call: {'yes' if abs(sd - 1) <= 0.03 else 'NO'} (salvage / decompress = {sd:.3f}); "
                          f"recover / index on an undamaged archive = {ri:.3f}")
+    if "cli" in parts:
+        lines += cli_part(torch, jam, ctx, a.reps, sync)
     text = "\n".join(lines) + "\n"
     print(text, end="")
     if a.out:
