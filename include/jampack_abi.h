@@ -659,6 +659,50 @@ JPK_API int jpk_dev_jam_repair(jpk_ctx *ctx, const jpk_jam_index *index, const u
                                uint8_t *d_out, int64_t out_cap, int64_t *out_len, int32_t *frames);
 JPK_API int jpk_jam_repair(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, const int32_t *frame_status, uint8_t *out,
                            int64_t out_cap, int64_t *out_len, int32_t *frames);   /* host memory: memcpy, no device call */
+/* ---- updating an archive: byte ranges replaced, only the touched frames encoded again ("Updating an archive") ----
+ * The input is an index of any kind, recovered or not, and its archive (in_len must be the index's archive length).  The n writes
+ * (off[r], len[r], src[r]) are in raw coordinates; a tail of tail_len bytes (may be 0) is appended.  The result is the archive whose decode
+ * is the old raw bytes with every [off[r], off[r] + len[r]) replaced by the len[r] bytes at src[r], followed by the tail.
+ *   writes      every one inside [0, raw_len]; those with len > 0 pairwise disjoint (end to end is allowed), in any order; len == 0 is
+ *               legal anywhere and touches nothing.  An overlap, a write outside the range, a wrong in_len, a NULL pointer that is
+ *               needed, flags other than 0, 1, 4, 5 (checked always), tail_len < 0 or a tail_block_size outside [JPK_MIN_BLOCKSIZE,
+ *               JPK_MAX_BLOCKSIZE] with a tail: JPK_E_ARG before any device is looked for, and nothing is written, the results included
+ *   untouched   a frame no write touches is copied unchanged, header and payload, neither decoded nor verified (as jpk_dev_jam_repair);
+ *               the gaps of a recovered index are dropped as repair drops them; a frame of 0 raw bytes is always kept
+ *   rewritten   a touched frame keeps its raw size, its BlockSize field and its kind: a plain frame stays plain (also under an index of
+ *               kind 2) and is what jpk_jam_block_write gives for its new raw bytes and its BlockSize; a staged frame what
+ *               jpk_jam_staged_block_write gives with `flags`; a frame of an index of kind 1 what jpk_jam_cli_block_write_ex gives with
+ *               `flags` -- byte for byte.  A frame whose every byte the union of the writes covers is not decoded: its old content does
+ *               not matter, so a frame that fails its crc can be replaced this way.  A partly covered frame is decoded and verified
+ *               through the passes of jpk_dev_jam_read; if one fails its decode or its crc the call returns JPK_E_CORRUPT, *bad_frame
+ *               (may be NULL) = the lowest such frame of the index, *new_index = NULL, and what the output buffer holds is unspecified
+ *   tail        new frames behind the last one: tail_block_size slices, the last one short, of the index's kind (kind 2: staged frames
+ *               with `flags`) -- the bytes of the matching jpk_dev_jam_*compress call over the tail.  tail_len == 0 ignores
+ *               tail_block_size.  An empty index with a tail makes the call a writer that returns its index
+ *   new index   *new_index (the caller destroys it) has the index's kind, no gap and no bad frame, and equals field by field what the
+ *               matching creator makes of the output.  It is built from what the call knows -- offsets, payload sizes, crcs, BlockSize
+ *               fields, raw sizes, staged bits --: the output is not walked, and a rewritten frame is WRITTEN by this call, not decoded
+ *               back, so its entry vouches for the writer, not for a read-back.  *rewritten (may be NULL) = the rewritten frames
+ *   capacity    jpk_jam_update_bound = the spans of the kept frames + the frame bound of every rewritten frame (15 + the payload slot of
+ *               its raw size, of its pre-stage bound for a chained frame) + the kind's compress bound of the tail; it always suffices,
+ *               and is JPK_E_ARG for arguments the entries refuse.  A smaller out_cap that turns out too small: JPK_E_CAPACITY, *out_len
+ *               = the bound (earlier stretches of the output may have been written; one that cannot even hold the kept frames and
+ *               the new headers is refused before anything is written)
+ * The archive, the sources, the tail and the output must not overlap; each at any alignment.  Nothing outside [d_in, d_in + in_len) and
+ * [d_src[r], d_src[r] + len[r]) is read of them and nothing outside [d_out, d_out + *out_len) is written.  Per pass of at most 128
+ * rewritten frames (and 4 GiB of their weight, a chained frame its BlockSize): the reader for the partly covered ones, one k_jam_gather
+ * launch for the sources, the compress pass, one k_jam_splice launch for the stretch of the output the pass ends. */
+JPK_API int64_t jpk_jam_update_bound(const jpk_jam_index *index, int32_t n, const int64_t *off, const int64_t *len, int64_t tail_len, int32_t tail_block_size);
+JPK_API int jpk_dev_jam_update(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                               const uint8_t *const *d_src, const uint8_t *d_tail, int64_t tail_len, int32_t tail_block_size, uint32_t flags, int32_t in_flight,
+                               uint8_t *d_out, int64_t out_cap, int64_t *out_len, jpk_jam_index **new_index, int32_t *rewritten, int32_t *bad_frame);
+/* host-buffer form through the calling thread's pooled context: only the payloads of the partly covered frames, the pieces of the sources
+ * and the tail travel to the device, only the new payloads travel back, and the kept frames are copied with memcpy.  Arguments are
+ * checked before a device is looked for; a call with no rewritten frame and no tail makes no device call, and its output is
+ * jpk_jam_repair's */
+JPK_API int jpk_jam_update(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                           const uint8_t *const *src, const uint8_t *tail, int64_t tail_len, int32_t tail_block_size, uint32_t flags, int32_t in_flight, uint8_t *out,
+                           int64_t out_cap, int64_t *out_len, jpk_jam_index **new_index, int32_t *rewritten, int32_t *bad_frame);
 /* probe: the offsets of the first max_cands (1..65536) plausible frame headers that start in [start, start + window) of d_in[0..in_len),
  * ascending, from one run of k_jam_scan_count / the prefix scan / k_jam_scan_emit; window <= 2^30; stateless, reads only.  offsets holds
  * max_cands entries */

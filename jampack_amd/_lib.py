@@ -160,6 +160,11 @@ _SIGS = {
     "jpk_jam_salvage": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p, _i32p]),
     "jpk_dev_jam_repair": (C.c_int, [_vp, _vp, _vp, C.c_int64, _i32p, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p]),
     "jpk_jam_repair": (C.c_int, [_vp, _vp, C.c_int64, _i32p, _vp, C.c_int64, C.POINTER(C.c_int64), _i32p]),
+    "jpk_jam_update_bound": (C.c_int64, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.c_int32]),
+    "jpk_dev_jam_update": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_vp), _vp, C.c_int64, C.c_int32,
+                                     C.c_uint32, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_vp), _i32p, _i32p]),
+    "jpk_jam_update": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(_vp), _vp, C.c_int64, C.c_int32,
+                                 C.c_uint32, C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(_vp), _i32p, _i32p]),
     "jpk_debug_jam_scan": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _i32p]),
     "jpk_debug_jam_recover_limits": (C.c_int, [C.c_int64, C.c_int32]),
     "jpk_dev_suffix_array": (C.c_int, [_vp, _vp, C.c_int32, _vp]),

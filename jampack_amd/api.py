@@ -345,6 +345,54 @@ def jam_repair(stream, index: JamIndex, frame_status=None) -> np.ndarray:
     return out[: n.value].copy()
 
 
+def _writes(writes):
+    """the (off, len, src) arrays of the update entries from [(raw offset, bytes), ...]; the numpy sources are returned to keep them alive"""
+    srcs = [_np_u8(s) for _, s in writes]
+    n = len(srcs)
+    L, P = C.c_int64 * max(n, 1), C.c_void_p * max(n, 1)
+    return n, L(*[int(o) for o, _ in writes]), L(*[len(s) for s in srcs]), P(*[_ptr(s) for s in srcs]), srcs
+
+
+def jam_update_bound(index: JamIndex, writes, tail_len: int = 0, block_size: int = 8 << 20) -> int:
+    """jpk_jam_update_bound: an output capacity that always suffices for jam_update(…, writes [(raw offset, length or bytes), ...], a tail
+    of tail_len bytes); raises JampackError(-1) for writes the update would refuse"""
+    n = len(writes)
+    L = C.c_int64 * max(n, 1)
+    lens = [int(s) if isinstance(s, (int, np.integer)) else len(_np_u8(s)) for _, s in writes]
+    b = lib().jpk_jam_update_bound(index._h, n, L(*[int(o) for o, _ in writes]), L(*lens), tail_len, block_size)
+    if b < 0:
+        raise JampackError(int(b), "jpk_jam_update_bound")
+    return int(b)
+
+
+def jam_update(stream, writes, index: JamIndex | None = None, tail=None, block_size: int = 8 << 20, dedupe: bool = False, filters: bool = False,
+               flags: int | None = None):
+    """jpk_jam_update: the archive in host memory with the writes [(raw offset, bytes), ...] applied and `tail` appended as new frames of
+    block_size -> (archive, JamIndex of it).  Only the frames a write touches are encoded again -- each keeps its raw size, its BlockSize
+    and its kind; dedupe / filters (or flags) are those of the stock-CLI and the staged writers --, every other frame is copied as it is.
+    Writes must be disjoint and inside the archive's raw bytes.  Without an index the archive is taken for a plain one; a stock-CLI
+    archive is updated through the index of jam_cli_index, one with staged frames through that of jam_staged_index.  A partly covered
+    frame that fails its decode or its crc raises JampackError(-3)."""
+    c = _np_u8(stream)
+    ix = index if index is not None else jam_index(c)
+    try:
+        n, off, ln, ptrs, keep = _writes(writes)
+        t = _np_u8(tail) if tail is not None else np.zeros(0, dtype=np.uint8)
+        fl = _cli_flags(dedupe, filters) if flags is None else flags
+        cap = lib().jpk_jam_update_bound(ix._h, n, off, ln, len(t), block_size)
+        _chk(min(int(cap), 0), "jpk_jam_update_bound")
+        out = np.empty(max(int(cap), 1), dtype=np.uint8)
+        m, h, rw, bad = C.c_int64(0), C.c_void_p(), C.c_int32(0), C.c_int32(-1)
+        rc = lib().jpk_jam_update(ix._h, _ptr(c), len(c), n, off, ln, ptrs, _ptr(t), len(t), block_size, fl, 0, out.ctypes.data, int(cap), C.byref(m), C.byref(h),
+                                  C.byref(rw), C.byref(bad))
+        _chk(rc, f"jpk_jam_update: frame {bad.value}" if bad.value >= 0 else "jpk_jam_update")
+        del keep
+        return out[: m.value].copy(), JamIndex(h, -1)
+    finally:
+        if index is None:
+            ix.close()
+
+
 def lz77_size(stream, cap: int) -> int:
     """jpk_lz77_size: what Lz77().Decompress(stream, cap) would be long, from the tokens alone (host code, no output buffer); raises
     JampackError with the status Decompress would raise"""
@@ -949,6 +997,24 @@ class Context:
         _chk(lib().jpk_dev_jam_repair(self._h, index._h, _dptr(d_in), in_len, _frame_status(index, frame_status), _dptr(d_out), out_cap, C.byref(n), C.byref(k)),
              "jpk_dev_jam_repair")
         return n.value, k.value
+
+    def jam_update(self, index: JamIndex, d_in, in_len, writes, d_out, out_cap, d_tail=None, tail_len: int = 0, block_size: int = 8 << 20, dedupe: bool = False,
+                   filters: bool = False, flags: int | None = None, in_flight: int = 0, check: bool = True):
+        """jpk_dev_jam_update: the archive d_in[0..in_len) with the writes [(raw offset, length, device source), ...] applied and the tail
+        appended, into d_out -> (out_len, JamIndex of the output, rewritten frames); check=False: (out_len, JamIndex or None, rewritten,
+        bad frame, status), no exception (out_len is jpk_jam_update_bound's answer on JPK_E_CAPACITY)"""
+        n = len(writes)
+        L, P = C.c_int64 * max(n, 1), C.c_void_p * max(n, 1)
+        off, ln, src = L(*[int(w[0]) for w in writes]), L(*[int(w[1]) for w in writes]), P(*[_dptr(w[2]) for w in writes])
+        fl = _cli_flags(dedupe, filters) if flags is None else flags
+        m, h, rw, bad = C.c_int64(0), C.c_void_p(), C.c_int32(0), C.c_int32(-1)
+        rc = lib().jpk_dev_jam_update(self._h, index._h, _dptr(d_in), in_len, n, off, ln, src, _dptr(d_tail), tail_len, block_size, fl, in_flight, _dptr(d_out), out_cap,
+                                      C.byref(m), C.byref(h), C.byref(rw), C.byref(bad))
+        ix = JamIndex(h, -1) if h else None
+        if not check:
+            return m.value, ix, rw.value, bad.value, int(rc)
+        _chk(rc, f"jpk_dev_jam_update: frame {bad.value}" if bad.value >= 0 else "jpk_dev_jam_update")
+        return m.value, ix, rw.value
 
     def jam_salvage(self, index: JamIndex, d_in, in_len, d_out, out_cap):
         """jpk_dev_jam_salvage: every frame of the index into d_out at its raw offset -> (raw_len, frame_status); a failed frame has

@@ -269,6 +269,7 @@ extern "C" void jpk_ctx_destroy(jpk_ctx *c)
     if (c->stage_out) (void)hipFree(c->stage_out);
     if (c->stage_res) (void)hipFree(c->stage_res);
     if (c->jam_scratch) (void)hipFree(c->jam_scratch);
+    if (c->jam_update) (void)hipFree(c->jam_update);
     if (c->d_mail) (void)hipFree(c->d_mail);
     if (c->h_mail) (void)hipHostFree(c->h_mail);
     if (c->h_map) (void)hipHostFree(c->h_map);

@@ -12,8 +12,6 @@
 bool jpk_arch_ok(const hipDeviceProp_t &prop);
 // the test hooks that CHANGE live state work only in a process that sets JPK_DEBUG_HOOKS=1
 bool jpk_debug_hooks_on();
-// the 15 bytes of a frame header at h (jpk_jam_header_parse reads them back)
-void jpk_jam_header_write(uint8_t *h, uint32_t crc, int32_t psize, int32_t block_size_field);
 
 // per-block statuses of a batch call: the caller's array, or `local` when the caller passed none -- the call then returns the first
 // status that is not JPK_OK

@@ -106,6 +106,10 @@ struct jpk_ctx {
     // the archive calls (jpk_dev_jam_compress / _decompress): crcs, frame tables and payload slots of one pass
     uint8_t *jam_scratch = nullptr;
     size_t jam_scratch_cap = 0;
+    // jpk_dev_jam_update: the new raw frames of one pass, its gather and splice tables -- apart from jam_scratch, which the reader and
+    // the compress pass of the same update use
+    uint8_t *jam_update = nullptr;
+    size_t jam_update_cap = 0;
     jpk_stats stats;
     // jpk_dev_blocks_lz77_expand: the blocks of the last call that took the parallel path and the serial one (jpk_debug_lz77_expand_last)
     int32_t lzx_parallel = 0, lzx_serial = 0;
@@ -259,6 +263,8 @@ size_t jpk_multi_comp_cap(int32_t len);
 bool jpk_jam_block_size_ok(int32_t bs);
 // the 15-byte frame header at h, `avail` bytes from h to the end of the input: the fields, and whether they pass DecompReadBlock's checks
 bool jpk_jam_header_parse(const uint8_t *h, int64_t avail, uint32_t *crc, int32_t *psize, int32_t *block_size);
+// the 15 bytes of a frame header at h (jpk_jam_header_parse reads them back)
+void jpk_jam_header_write(uint8_t *h, uint32_t crc, int32_t psize, int32_t block_size_field);
 
 // ---- stage drivers (device buffers) -----------------------------------------------------------------
 int jpk_fwd_bwt_device(jpk_ctx *ctx, const uint8_t *d_in, int32_t len, uint8_t *d_out);
@@ -321,6 +327,14 @@ int jpk_jam_pack_enqueue(jpk_ctx *ctx, const JamPackFrame *d_frames, int n, cons
 struct JamGatherPiece { const uint8_t *src; uint8_t *dst; uint64_t len; uint64_t word0; const uint8_t *src_lo; const uint8_t *src_hi; };
 // delivers d_pieces[0..n) (len > 0 each, `words` destination words and `bytes` bytes in all) with one launch.  Enqueued.
 int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_t n, uint64_t words, uint64_t bytes);
+// One frame of a splice (jpk_dev_jam_update): the frame starts `off` bytes into the stretch that one launch writes.  kept != 0: a frame
+// copied from the archive, its header and payload the 15 + psize contiguous bytes at src (crc and field are not looked at); otherwise a new
+// frame: src is its payload slot (at least 16 readable bytes behind the payload), the header is made of crc, psize and field (the
+// BlockSize field as it is written, JPK_JAM_STAGED included)
+struct JamSpliceFrame { uint64_t off; const uint8_t *src; int32_t psize; uint32_t crc; int32_t field; int32_t kept; };
+// writes the frames d_frames[0..n) (any n >= 1: the table is read through L2), ascending in off from 0 and back to back, into
+// d_out[0..total); a kept frame is read only inside [in_lo, in_hi), the archive.  Enqueued.
+int jpk_jam_splice_enqueue(jpk_ctx *ctx, const JamSpliceFrame *d_frames, uint32_t n, uint8_t *d_out, uint64_t total, const uint8_t *in_lo, const uint8_t *in_hi);
 // the writer's stage chain on the device (prestage_dev.hip): R -> S2 (k_enc_wrap) into d_mid[b] (jpk_cli_stages_bound - 2 bytes; d_mid ==
 // nullptr: in ctx's arena) -> S4 = end token | Lpx::Encode(S2) (k_enc_lpx) into d_out[b] (jpk_cli_stages_bound bytes); in_len[b] < 0
 // skips block b.  Two launches; synchronises the stream.  flags & JPK_CLI_DEDUPE: the k_dd_* launches first, R -> S1' into d_out[b], one host

@@ -4,6 +4,8 @@
 //                from payload slots in scratch, organised by destination: a thread owns aligned 16-byte words of the output
 //   k_jam_gather delivers the pieces of a range read -- (source, destination, length) of decoded bytes -- organised by destination
 //                in the same way: a thread owns aligned 16-byte words of a piece's destination
+//   k_jam_splice writes a stretch of an updated archive -- kept frames copied from the old archive and new frames from payload slots, each
+//                with a BlockSize field of its own -- organised by destination as k_jam_pack is
 //   k_jam_scan_* the plausible frame headers of a window of an archive, in ascending order: where a walk past damage looks for the next
 //                frame (jam_resync.hpp; DESIGN 4.6, "Damaged archives")
 // The ABI entries that drive them are jpk_dev_jam_compress / jpk_dev_jam_decompress / jpk_dev_jam_read (jam_archive.hip).
@@ -159,6 +161,64 @@ __global__ __launch_bounds__(PACK_TB) void k_jam_gather(const JamGatherPiece *__
     }
 }
 
+// Organised by destination like k_jam_pack: word w is the aligned 16 bytes at base + 16 w (base = out rounded down to 16), and its owner
+// finds the frame of its first byte by a search over the frames' offsets.  The frames are of two sorts, in any mix: a kept frame is 15 +
+// psize contiguous bytes of the archive, header included; a new frame is a header made of its fields in front of a payload slot, the
+// BlockSize field its own.  A whole word inside one source -- a kept frame's span, a new frame's payload -- takes one unaligned 16-byte
+// load (two aligned ones) and one 16-byte store; the two aligned loads of a kept frame must stay inside [in_lo, in_hi), the archive, which
+// has no padding, so the few words at the archive's two ends go the other way: byte by byte, as every word that straddles a frame edge
+// or holds header bytes of a new frame.  Only the partial words at the two ends of the stretch use byte stores; nothing outside
+// [out, out + total) is written.  A stretch holds the kept frames between two passes, thousands perhaps, so the table is read through L2
+// as k_jam_gather's is (32-byte entries, log2(n) of them per word, neighbouring threads the same ones), not staged in LDS.
+__global__ __launch_bounds__(PACK_TB) void k_jam_splice(const JamSpliceFrame *__restrict__ frames, uint32_t n, uint8_t *__restrict__ out, uint64_t total,
+                                                        const uint8_t *in_lo, const uint8_t *in_hi)
+{
+    const uintptr_t base = (uintptr_t)out & ~(uintptr_t)15;
+    const int64_t lead = (int64_t)((uintptr_t)out - base);                     // bytes of the first word in front of the stretch
+    const uint64_t words = ((uint64_t)lead + total + 15u) / 16u;
+    for (uint64_t w = (uint64_t)blockIdx.x * PACK_TB + threadIdx.x; w < words; w += (uint64_t)gridDim.x * PACK_TB) {
+        const int64_t p0 = (int64_t)(w * 16u) - lead;                          // stretch position of the word's first byte (< 0: before the stretch)
+        const uint64_t first = p0 < 0 ? 0u : (uint64_t)p0;
+        uint32_t lo = 0, hi = n;                                              // frame of `first`: the last with off <= first
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (frames[mid].off <= first) lo = mid; else hi = mid; }
+        uint32_t f = lo;
+        JamSpliceFrame fr = frames[f];
+        uint8_t *dst = reinterpret_cast<uint8_t *>(base + w * 16u);
+        const bool whole = p0 >= 0 && (uint64_t)p0 + 16u <= total;
+        if (whole) {
+            // the contiguous source the word may lie in: the frame's span in the archive, or its payload in the slot
+            const uint64_t s0 = fr.off + (fr.kept ? 0u : (uint64_t)JPK_JAM_HEADER_BYTES), s1 = fr.off + JPK_JAM_HEADER_BYTES + (uint64_t)fr.psize;
+            if ((uint64_t)p0 >= s0 && (uint64_t)p0 + 16u <= s1) {
+                const uint8_t *src = fr.src + ((uint64_t)p0 - s0);
+                const uintptr_t a = (uintptr_t)src & ~(uintptr_t)15;
+                if (!fr.kept || (a >= (uintptr_t)in_lo && a + (((uintptr_t)src & 15u) ? 32u : 16u) <= (uintptr_t)in_hi)) {
+                    *reinterpret_cast<uint4 *>(dst) = load16_unaligned(src);
+                    continue;
+                }
+            }
+        }
+        uint32_t b[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const int64_t p = p0 + j;
+            b[j] = 0;
+            if (p < 0 || (uint64_t)p >= total) continue;
+            while (f + 1 < n && (uint64_t)p >= frames[f + 1].off) fr = frames[++f];
+            const uint64_t rel = (uint64_t)p - fr.off;
+            b[j] = fr.kept ? (uint32_t)fr.src[rel] : frame_byte(rel, fr.crc, fr.psize, fr.field, fr.src);
+            if (!whole) dst[j] = (uint8_t)b[j];
+        }
+        if (whole) {
+            uint4 v;
+            v.x = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            v.y = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+            v.z = b[8] | (b[9] << 8) | (b[10] << 16) | (b[11] << 24);
+            v.w = b[12] | (b[13] << 8) | (b[14] << 16) | (b[15] << 24);
+            *reinterpret_cast<uint4 *>(dst) = v;
+        }
+    }
+}
+
 // ---- k_jam_scan_count / k_jam_scan_emit: the plausible headers (jrs::magic_ok + jrs::fields_ok) that start in [start, end) -----------
 // A streaming read.  Word w is the aligned 16 bytes at base + 16 w, base = `in` rounded down to 16; a lane loads SCAN_ROWS words per tile,
 // 64 words apart, so a wave's loads are 1 KiB each and a tile is SCAN_TILE = 4 KiB of one wave's own.  A lane tests the 16 offsets of a
@@ -309,6 +369,17 @@ int jpk_jam_gather_enqueue(jpk_ctx *ctx, const JamGatherPiece *d_pieces, uint32_
     uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
     if (grid > 8192) grid = 8192;                                              // grid-stride beyond, as k_jam_pack
     JPK_LAUNCH(ctx, PROF_JAM, bytes, k_jam_gather, dim3((unsigned)grid), dim3(PACK_TB), d_pieces, n, words);
+    JPK_HIP(hipGetLastError());
+    return JPK_OK;
+}
+
+int jpk_jam_splice_enqueue(jpk_ctx *ctx, const JamSpliceFrame *d_frames, uint32_t n, uint8_t *d_out, uint64_t total, const uint8_t *in_lo, const uint8_t *in_hi)
+{
+    if (n == 0 || total == 0) return JPK_OK;
+    const uint64_t words = (total + 31u) / 16u;
+    uint64_t grid = (words + PACK_TB - 1) / PACK_TB;
+    if (grid > 8192) grid = 8192;                                              // grid-stride beyond, as k_jam_pack
+    JPK_LAUNCH(ctx, PROF_JAM, total, k_jam_splice, dim3((unsigned)grid), dim3(PACK_TB), d_frames, n, d_out, total, in_lo, in_hi);
     JPK_HIP(hipGetLastError());
     return JPK_OK;
 }

@@ -1,6 +1,6 @@
 // jam_archive.hip -- whole .jam archives of the C ABI (include/jampack_abi.h): the frame walks, the batched compress and decompress
 // calls of plain and stock-CLI archives with their host-buffer forms, the index + range reads, and the index, the salvage and the repair of damaged
-// archives (the rule they share with the kernels: jam_resync.hpp).  Host drivers only: the kernels
+// archives (the rule they share with the kernels: jam_resync.hpp), and the update of byte ranges (its plan: jam_update_plan.hpp).  Host drivers only: the kernels
 // are in jam.hip, prestage_dev.hip and checksum.hip, the batch engines in abi_blocks.hip and the context pool in abi_pool.hip.
 #include <algorithm>
 #include <atomic>
@@ -9,9 +9,11 @@
 
 #include "common.hpp"
 #include "jam_resync.hpp"
+#include "jam_update_plan.hpp"
 
 // ---- whole .jam archives: Jampack::Compress / Jampack::Decompress (jampack.cpp:186-336) through the batch engines --------------
-// Compress, per pass: one batched checksum of the pass's slices (crcs stay on the device), jpk_dev_blocks_compress into payload slots
+// Compress, per pass (jam_compress_frames, the form the update shares: a pointer, a length, a BlockSize and a kind per frame): one batched
+// checksum of the pass's slices (the crcs stay on the device for the pack and come to the host for an index), jpk_dev_blocks_compress into payload slots
 // in ctx->jam_scratch, the frame offsets on the host (64-bit), one k_jam_pack launch that writes the frames.  Decompress: the frame
 // walk (k_jam_walk, one launch + one read-back per JPK_JAM_PASS_FRAMES frames) and the decoded sizes (pass 1 of the batch decoder)
 // over the whole archive first -- that is what makes the capacity answer exact and leaves d_out untouched when it is too small --
@@ -185,56 +187,99 @@ int jam_result_done(const JamResult &r, int64_t len, size_t frames, int32_t bad)
 int32_t jam_bwt_len(int32_t len, bool cli) { return cli ? (int32_t)jpk_cli_stages_bound(len) : len; }
 int64_t jam_frame_bound(int32_t len, bool cli) { return JPK_JAM_HEADER_BYTES + (int64_t)jpk_multi_comp_cap(jam_bwt_len(len, cli)); }
 
-// one compress pass: consecutive block_size slices of d_in[0..len) (the last one short) -> frames at d_out[0..*pass_len); cli: frames
-// of the stock CLI, or staged frames (kind): S2 in slot A is the BWT's input, slot B the dedupe's room (none without the dedupe)
-int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
-                      int32_t in_flight, int kind, uint32_t flags)
+// One frame of a compress pass: its raw bytes, wherever they lie in HBM, the BlockSize it is written under and its kind (JAM_PLAIN,
+// JAM_CLI or JAM_STAGED) -- and what the pass makes of it: the payload slot in ctx->jam_scratch (at least 16 readable bytes behind the
+// payload: the aligned loads of k_jam_pack and k_jam_splice), the payload's size and the crc of the raw bytes
+struct JamNewFrame { const uint8_t *in; int32_t len; int32_t block_size; int kind; };
+struct JamPayload { const uint8_t *slot; int32_t psize; uint32_t crc; };
+
+// The compress pass in its general form: n <= JPK_JAM_PASS_FRAMES frames, each with a pointer, a length, a BlockSize and a kind of its
+// own.  One batched checksum of the raw frames (jampack.cpp:31; the crcs stay in the first n words of ctx->jam_scratch and come to the host
+// too), the stage chain of the stock-CLI frames and that of the staged ones -- S2 in slot A is a staged frame's BWT input, S4 in slot B a
+// stock-CLI frame's; slot B is also the dedupe's room --, then ONE batch compress of all frames into their payload slots.  *table = room
+// for JPK_JAM_PASS_FRAMES JamPackFrame entries in the scratch, the caller's.  Synchronised.
+int jam_compress_frames(jpk_ctx *ctx, const std::vector<JamNewFrame> &fr, uint32_t flags, int32_t in_flight, std::vector<JamPayload> &made, uint8_t **table)
 {
-    const bool cli = kind != JAM_PLAIN;
-    const bool slot_b = kind == JAM_CLI || (flags & JPK_CLI_DEDUPE) != 0;
-    const int n = (int)((len + block_size - 1) / block_size);
-    std::vector<const uint8_t *> ins((size_t)n), bwt_in((size_t)n);
-    std::vector<uint8_t *> slots((size_t)n), sa((size_t)n), sb((size_t)n, nullptr);
-    std::vector<int32_t> lens((size_t)n), blens((size_t)n), caps((size_t)n), outl((size_t)n), st((size_t)n);
+    const size_t n = fr.size();
+    std::vector<const uint8_t *> ins(n), bwt_in(n);
+    std::vector<uint8_t *> slots(n), sa(n, nullptr), sb(n, nullptr);
+    std::vector<int32_t> lens(n), blens(n), caps(n), outl(n), st(n);
     const size_t o_frames = jpk_align((size_t)JPK_JAM_PASS_FRAMES * 4), o_slots = o_frames + jpk_align((size_t)JPK_JAM_PASS_FRAMES * sizeof(JamPackFrame));
+    auto slot_b = [flags](int kind) { return kind == JAM_CLI || (kind == JAM_STAGED && (flags & JPK_CLI_DEDUPE) != 0); };
     size_t need = o_slots;
-    for (int i = 0; i < n; i++) {
-        ins[i] = d_in + (int64_t)i * block_size;
-        lens[i] = (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size);
+    for (size_t i = 0; i < n; i++) {
+        const bool cli = fr[i].kind != JAM_PLAIN;
+        ins[i] = fr[i].in;
+        lens[i] = fr[i].len;
         blens[i] = jam_bwt_len(lens[i], cli);
         caps[i] = (int32_t)jpk_multi_comp_cap(blens[i]);
         need += jpk_align((size_t)caps[i] + 64);          // (>= 16 bytes behind every payload: k_jam_pack's aligned loads)
-        if (cli) need += (slot_b ? 2 : 1) * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
+        if (cli) need += (slot_b(fr[i].kind) ? 2 : 1) * jpk_align((size_t)blens[i] + 64);     // slot A (S2) and slot B (S4)
     }
     JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_scratch, &ctx->jam_scratch_cap, need));
     uint32_t *d_crc = reinterpret_cast<uint32_t *>(ctx->jam_scratch);
-    JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(ctx->jam_scratch + o_frames);
+    *table = ctx->jam_scratch + o_frames;
     size_t off = o_slots;
-    for (int i = 0; i < n; i++) {
+    for (size_t i = 0; i < n; i++) {
         slots[i] = ctx->jam_scratch + off; off += jpk_align((size_t)caps[i] + 64);
         bwt_in[i] = ins[i];
-        if (cli) {
+        if (fr[i].kind != JAM_PLAIN) {
             sa[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64);
-            if (slot_b) { sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64); }
-            bwt_in[i] = kind == JAM_STAGED ? sa[i] : sb[i];
+            if (slot_b(fr[i].kind)) { sb[i] = ctx->jam_scratch + off; off += jpk_align((size_t)blens[i] + 64); }
+            bwt_in[i] = fr[i].kind == JAM_STAGED ? sa[i] : sb[i];
         }
     }
     // crcs of the inputs (jampack.cpp:31) first, in stream order in front of the batch (its workers wait for ctx's stream)
-    JPK_TRY(jpk_checksums_device(ctx, n, ins.data(), lens.data(), d_crc));
-    if (kind == JAM_CLI) JPK_TRY(jpk_cli_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
-    if (kind == JAM_STAGED) JPK_TRY(jpk_staged_stages_device(ctx, n, ins.data(), lens.data(), sa.data(), sb.data(), flags, blens.data()));
-    JPK_TRY(jpk_dev_blocks_compress(ctx, n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
-    for (int i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
+    std::vector<uint32_t> crc(n);
+    JPK_TRY(jam_crcs(ctx, (int)n, ins.data(), lens.data(), d_crc, crc.data()));
+    // the stage chain of one kind: its frames side by side, their BWT inputs' lengths back into blens
+    for (int kind : {JAM_CLI, JAM_STAGED}) {
+        std::vector<size_t> at;
+        std::vector<const uint8_t *> kin;
+        std::vector<uint8_t *> ka, kb;
+        std::vector<int32_t> klen;
+        for (size_t i = 0; i < n; i++)
+            if (fr[i].kind == kind) { at.push_back(i); kin.push_back(ins[i]); klen.push_back(lens[i]); ka.push_back(sa[i]); kb.push_back(sb[i]); }
+        if (at.empty()) continue;
+        std::vector<int32_t> got(at.size());
+        if (kind == JAM_CLI) JPK_TRY(jpk_cli_stages_device(ctx, (int)at.size(), kin.data(), klen.data(), ka.data(), kb.data(), flags, got.data()));
+        else JPK_TRY(jpk_staged_stages_device(ctx, (int)at.size(), kin.data(), klen.data(), ka.data(), kb.data(), flags, got.data()));
+        for (size_t q = 0; q < at.size(); q++) blens[at[q]] = got[q];
+    }
+    JPK_TRY(jpk_dev_blocks_compress(ctx, (int)n, bwt_in.data(), blens.data(), slots.data(), caps.data(), outl.data(), st.data(), in_flight));
+    for (size_t i = 0; i < n; i++) if (st[i] != JPK_OK) return st[i];
+    made.resize(n);
+    for (size_t i = 0; i < n; i++) made[i] = JamPayload{slots[i], outl[i], crc[i]};
+    return JPK_OK;
+}
+
+// one compress pass of the whole-archive writers: consecutive block_size slices of d_in[0..len) (the last one short), all of one kind ->
+// frames at d_out[0..*pass_len) through one k_jam_pack launch.  done (nullable) receives the frames as an index holds them, payload_off
+// counted from the pass's first byte
+int jam_compress_pass(jpk_ctx *ctx, const uint8_t *d_in, int64_t len, int32_t block_size, uint8_t *d_out, int64_t out_room, int64_t *pass_len,
+                      int32_t in_flight, int kind, uint32_t flags, std::vector<JamFrame> *done = nullptr)
+{
+    const int n = (int)((len + block_size - 1) / block_size);
+    std::vector<JamNewFrame> in((size_t)n);
+    for (int i = 0; i < n; i++) in[i] = JamNewFrame{d_in + (int64_t)i * block_size, (int32_t)std::min<int64_t>(block_size, len - (int64_t)i * block_size), block_size, kind};
+    std::vector<JamPayload> made;
+    uint8_t *table = nullptr;
+    JPK_TRY(jam_compress_frames(ctx, in, flags, in_flight, made, &table));
     std::vector<JamPackFrame> fr((size_t)n);
     uint64_t pos = 0;
     for (int i = 0; i < n; i++) {
-        fr[i].slot = slots[i]; fr[i].off = pos; fr[i].psize = outl[i]; fr[i].pad = 0;
-        pos += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)outl[i];
+        fr[i].slot = made[i].slot; fr[i].off = pos; fr[i].psize = made[i].psize; fr[i].pad = 0;
+        pos += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)made[i].psize;
     }
     if ((int64_t)pos > out_room) return JPK_E_CAPACITY;
+    JamPackFrame *d_frames = reinterpret_cast<JamPackFrame *>(table);
     JPK_HIP(hipMemcpyAsync(d_frames, fr.data(), (size_t)n * sizeof(JamPackFrame), hipMemcpyHostToDevice, ctx->stream));
-    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, d_crc, kind == JAM_STAGED ? (block_size | JPK_JAM_STAGED) : block_size, d_out, pos));
+    JPK_TRY(jpk_jam_pack_enqueue(ctx, d_frames, n, reinterpret_cast<const uint32_t *>(ctx->jam_scratch), kind == JAM_STAGED ? (block_size | JPK_JAM_STAGED) : block_size,
+                                 d_out, pos));
     JPK_HIP(hipStreamSynchronize(ctx->stream));
+    if (done)
+        for (int i = 0; i < n; i++)
+            done->push_back(JamFrame{(int64_t)fr[i].off + JPK_JAM_HEADER_BYTES, made[i].psize, made[i].crc, block_size, in[i].len, kind == JAM_STAGED});
     *pass_len = (int64_t)pos;
     return JPK_OK;
 }
@@ -1673,6 +1718,312 @@ extern "C" int jpk_jam_repair(const jpk_jam_index *index, const uint8_t *in, int
         for (const JamSpan &s : keep) { memcpy(out + pos, in + s.off, (size_t)s.len); pos += s.len; }
         return JPK_OK;
     } catch (const std::bad_alloc &) {
+        return JPK_E_ALLOC;
+    }
+}
+
+// ---- update: byte ranges of an archive replaced, only the touched frames encoded again ("Updating an archive") -----------------
+// The plan is jam_update_plan.hpp's: which frame is kept, which is rewritten, the pieces of the sources, the passes.  Per pass: the partly
+// covered frames through the reader (jam_read_run, one whole-frame range each: every one decodes, verified, in place in its slot of
+// ctx->jam_update), one gather launch that lays the sources over the slots, the compress pass in its general form (jam_compress_frames:
+// payload slots in ctx->jam_scratch, sizes and crcs to the host), and one k_jam_splice launch that writes the stretch of the output the
+// pass ends -- the kept frames since the pass before, copied from the archive, and the pass's new ones.  Behind the last pass one more
+// splice for the kept frames that are left, then the tail through the passes of the whole-archive writer of the index's kind.  The new
+// index is made of what these steps know; the output is not walked.  The host-buffer form runs the same passes: the payloads of the
+// partly covered frames, the pieces of the sources and the tail travel to the device, the new payloads travel back, and the kept frames
+// are copied with memcpy.
+namespace {
+int jam_update_kind(const jpk_jam_index *ix, const JamFrame &f) { return ix->kind == JPK_JAM_INDEX_CLI ? JAM_CLI : f.staged ? JAM_STAGED : JAM_PLAIN; }
+int jam_update_tail_kind(const jpk_jam_index *ix) { return ix->kind == JPK_JAM_INDEX_CLI ? JAM_CLI : ix->kind == JPK_JAM_INDEX_STAGED ? JAM_STAGED : JAM_PLAIN; }
+
+// what the bound and both entries refuse alike, and the plan of what they take; *bound = jpk_jam_update_bound's answer, *least = what the
+// output holds at least (the kept spans and a header per new frame)
+int jam_update_plan(const jpk_jam_index *ix, int32_t n, const int64_t *off, const int64_t *len, int64_t tail_len, int32_t tail_block_size, jup::Plan *plan,
+                    int64_t *bound, int64_t *least)
+{
+    if (!ix || tail_len < 0 || (tail_len > 0 && !jpk_jam_block_size_ok(tail_block_size))) return JPK_E_ARG;
+    if (!jup::check(ix->raw_off, n, off, len)) return JPK_E_ARG;
+    const bool cli = ix->kind == JPK_JAM_INDEX_CLI;
+    std::vector<int64_t> weight(ix->fr.size());
+    for (size_t k = 0; k < weight.size(); k++) weight[k] = jam_weight(ix->fr[k], cli);
+    *plan = jup::make(ix->raw_off, weight, n, off, len, jup::Limits{(size_t)JPK_JAM_PASS_FRAMES, JAM_PASS_RAW});
+    int64_t sum = 0, low = 0;
+    for (size_t k = 0; k < ix->fr.size(); k++) {
+        const JamFrame &f = ix->fr[k];
+        if (plan->cls[k] == jup::KEPT) { sum += (int64_t)JPK_JAM_HEADER_BYTES + f.psize; low += (int64_t)JPK_JAM_HEADER_BYTES + f.psize; }
+        else { sum += jam_frame_bound((int32_t)f.raw, jam_update_kind(ix, f) != JAM_PLAIN); low += JPK_JAM_HEADER_BYTES; }
+    }
+    if (tail_len > 0) {
+        sum += jam_compress_bound(tail_len, tail_block_size, jam_update_tail_kind(ix) != JAM_PLAIN);
+        low += (int64_t)JPK_JAM_HEADER_BYTES * ((tail_len + tail_block_size - 1) / tail_block_size);
+    }
+    *bound = sum;
+    if (least) *least = low;
+    return JPK_OK;
+}
+
+// the arguments of either entry: the archive, the sources, the tail and the output are device buffers, or (host) host buffers
+struct JamUpdate {
+    const jpk_jam_index *ix;
+    const uint8_t *in; int64_t in_len;
+    int32_t n; const int64_t *off, *len; const uint8_t *const *src;
+    const uint8_t *tail; int64_t tail_len; int32_t tail_block_size;
+    uint32_t flags; int32_t in_flight;
+    uint8_t *out; int64_t out_cap; int64_t *out_len;
+    jpk_jam_index **new_index; int32_t *rewritten, *bad_frame;
+    bool host;
+};
+
+// the argument checks, the plan and the first capacity answer: no device is looked for, nothing is written before they pass
+int jam_update_check(const JamUpdate &u, jup::Plan *plan, int64_t *bound)
+{
+    if (!u.ix || !u.out_len || !u.new_index || u.in_len != u.ix->archive_len || u.out_cap < 0 || (u.in_len > 0 && !u.in) || (u.out_cap > 0 && !u.out) ||
+        !JPK_CLI_FLAGS_OK(u.flags) || u.n < 0 || (u.n > 0 && (!u.off || !u.len || !u.src)) || u.tail_len < 0 || (u.tail_len > 0 && !u.tail))
+        return JPK_E_ARG;
+    for (int32_t r = 0; r < u.n; r++) if (u.len[r] > 0 && !u.src[r]) return JPK_E_ARG;
+    int64_t least = 0;
+    JPK_TRY(jam_update_plan(u.ix, u.n, u.off, u.len, u.tail_len, u.tail_block_size, plan, bound, &least));
+    *u.new_index = nullptr;
+    if (u.bad_frame) *u.bad_frame = -1;
+    if (u.rewritten) *u.rewritten = (int32_t)plan->rewritten.size();
+    *u.out_len = *bound;
+    return least > u.out_cap ? JPK_E_CAPACITY : JPK_OK;
+}
+
+// frames [f0, f1) of the index, every one kept, to out + *pos: one splice launch, or (host) a memcpy per frame
+int jam_update_kept(jpk_ctx *ctx, const JamUpdate &u, int32_t f0, int32_t f1, int64_t *pos, std::vector<JamFrame> &done)
+{
+    if (f0 >= f1) return JPK_OK;
+    std::vector<JamSpliceFrame> tab;
+    uint64_t o = 0;
+    for (int32_t f = f0; f < f1; f++) {
+        const JamFrame &x = u.ix->fr[(size_t)f];
+        tab.push_back(JamSpliceFrame{o, u.in + x.payload_off - JPK_JAM_HEADER_BYTES, x.psize, x.crc, 0, 1});
+        o += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)x.psize;
+    }
+    if ((int64_t)o > u.out_cap - *pos) return JPK_E_CAPACITY;
+    if (u.host) {
+        for (const JamSpliceFrame &t : tab) memcpy(u.out + *pos + t.off, t.src, (size_t)JPK_JAM_HEADER_BYTES + (size_t)t.psize);
+    } else {
+        JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_update, &ctx->jam_update_cap, tab.size() * sizeof(JamSpliceFrame)));
+        JamSpliceFrame *d_tab = reinterpret_cast<JamSpliceFrame *>(ctx->jam_update);
+        JPK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(JamSpliceFrame), hipMemcpyHostToDevice, ctx->stream));
+        JPK_TRY(jpk_jam_splice_enqueue(ctx, d_tab, (uint32_t)tab.size(), u.out + *pos, o, u.in, u.in + u.in_len));
+        JPK_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    for (int32_t f = f0; f < f1; f++) {
+        done.push_back(u.ix->fr[(size_t)f]);
+        done.back().payload_off = *pos + (int64_t)tab[(size_t)(f - f0)].off + JPK_JAM_HEADER_BYTES;
+    }
+    *pos += (int64_t)o;
+    return JPK_OK;
+}
+
+// one pass of the plan: its partly covered frames decoded, the sources laid over its slots, its frames compressed, its stretch written
+int jam_update_pass(jpk_ctx *ctx, const JamUpdate &u, const jup::Plan &plan, const jup::Pass &ps, int64_t *pos, std::vector<JamFrame> &done)
+{
+    const jpk_jam_index *ix = u.ix;
+    const size_t m = ps.q1 - ps.q0, p0 = plan.piece_at[ps.q0], p1 = plan.piece_at[ps.q1];
+    // ctx->jam_update: the gather table | the splice table | (host) the pieces of the sources | a slot per rewritten frame, padded as the reader's are
+    size_t src_bytes = 0, slot_bytes = 0;
+    if (u.host) for (size_t i = p0; i < p1; i++) src_bytes += (size_t)plan.pieces[i].len;
+    for (size_t q = ps.q0; q < ps.q1; q++) slot_bytes += jpk_align((size_t)ix->fr[(size_t)plan.rewritten[q]].raw + 64);
+    const size_t o_splice = jpk_align((p1 - p0) * sizeof(JamGatherPiece)), o_src = o_splice + jpk_align((size_t)(ps.f1 - ps.f0) * sizeof(JamSpliceFrame)),
+                 o_slots = o_src + jpk_align(src_bytes + 64);
+    JPK_TRY(jpk_buf_ensure(ctx, &ctx->jam_update, &ctx->jam_update_cap, o_slots + slot_bytes));
+    uint8_t *const d_srcs = ctx->jam_update + o_src;
+    std::vector<uint8_t *> slot(m);
+    {
+        size_t o = o_slots;
+        for (size_t q = 0; q < m; q++) { slot[q] = ctx->jam_update + o; o += jpk_align((size_t)ix->fr[(size_t)plan.rewritten[ps.q0 + q]].raw + 64); }
+    }
+    // 1. the partly covered frames: one whole-frame range each, so the reader decodes every one in place in its slot and verifies it
+    {
+        std::vector<int64_t> roff, rlen;
+        std::vector<uint8_t *> rout;
+        for (size_t q = 0; q < m; q++) {
+            const size_t f = (size_t)plan.rewritten[ps.q0 + q];
+            if (plan.cls[f] != jup::PART) continue;
+            roff.push_back(ix->raw_off[f]); rlen.push_back(ix->fr[f].raw); rout.push_back(slot[q]);
+        }
+        if (!roff.empty()) {
+            std::vector<int32_t> st(roff.size());
+            int32_t bad = -1;
+            JPK_TRY(jam_read_run(ctx, ix, u.host ? nullptr : u.in, u.host ? u.in : nullptr, (int32_t)roff.size(), roff.data(), rlen.data(), rout.data(), st.data(), &bad));
+            if (bad >= 0) {
+                JPK_HIP(hipStreamSynchronize(ctx->stream));
+                if (u.bad_frame) *u.bad_frame = bad;
+                for (int32_t s : st) if (s != JPK_OK) return s;
+                return JPK_E_CORRUPT;
+            }
+        }
+    }
+    // 2. the sources over the slots, one gather launch
+    {
+        std::vector<JamGatherPiece> tab;
+        tab.reserve(p1 - p0);
+        uint64_t words = 0, bytes = 0;
+        size_t at = 0;
+        for (size_t q = 0; q < m; q++)
+            for (size_t i = plan.piece_at[ps.q0 + q]; i < plan.piece_at[ps.q0 + q + 1]; i++) {
+                const jup::Piece &pc = plan.pieces[i];
+                const uint8_t *from = u.src[pc.write] + pc.write_off, *lo = u.src[pc.write], *hi = lo + u.len[pc.write];
+                if (u.host) {
+                    JPK_HIP(hipMemcpyAsync(d_srcs + at, from, (size_t)pc.len, hipMemcpyHostToDevice, ctx->stream));
+                    from = d_srcs + at; lo = d_srcs; hi = d_srcs + src_bytes;
+                    at += (size_t)pc.len;
+                }
+                jam_piece_add(tab, &words, from, slot[q] + pc.frame_off, (uint64_t)pc.len, lo, hi);
+                bytes += (uint64_t)pc.len;
+            }
+        JPK_TRY(jam_gather(ctx, reinterpret_cast<JamGatherPiece *>(ctx->jam_update), tab, words, bytes));
+    }
+    // 3. the new frames: each keeps its raw size, its BlockSize and its kind
+    std::vector<JamNewFrame> nf(m);
+    for (size_t q = 0; q < m; q++) {
+        const JamFrame &f = ix->fr[(size_t)plan.rewritten[ps.q0 + q]];
+        nf[q] = JamNewFrame{slot[q], (int32_t)f.raw, f.block_size, jam_update_kind(ix, f)};
+    }
+    std::vector<JamPayload> made;
+    uint8_t *unused = nullptr;
+    JPK_TRY(jam_compress_frames(ctx, nf, u.flags, u.in_flight, made, &unused));
+    // 4. the stretch: the kept frames since the pass before and between the new ones, and the new ones
+    std::vector<JamSpliceFrame> tab;
+    tab.reserve((size_t)(ps.f1 - ps.f0));
+    uint64_t o = 0;
+    size_t q = 0;
+    for (int32_t f = ps.f0; f < ps.f1; f++) {
+        const JamFrame &x = ix->fr[(size_t)f];
+        if (plan.cls[(size_t)f] == jup::KEPT) tab.push_back(JamSpliceFrame{o, u.in + x.payload_off - JPK_JAM_HEADER_BYTES, x.psize, x.crc, 0, 1});
+        else {
+            tab.push_back(JamSpliceFrame{o, made[q].slot, made[q].psize, made[q].crc, x.staged ? (x.block_size | JPK_JAM_STAGED) : x.block_size, 0});
+            q++;
+        }
+        o += (uint64_t)JPK_JAM_HEADER_BYTES + (uint64_t)tab.back().psize;
+    }
+    if ((int64_t)o > u.out_cap - *pos) return JPK_E_CAPACITY;
+    if (u.host) {
+        // only the new payloads travel back; the kept frames are the host's own bytes
+        for (const JamSpliceFrame &t : tab) {
+            uint8_t *at = u.out + *pos + t.off;
+            if (t.kept) { memcpy(at, t.src, (size_t)JPK_JAM_HEADER_BYTES + (size_t)t.psize); continue; }
+            jpk_jam_header_write(at, t.crc, t.psize, t.field);
+            if (t.psize) JPK_HIP(hipMemcpyAsync(at + JPK_JAM_HEADER_BYTES, t.src, (size_t)t.psize, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    } else {
+        JamSpliceFrame *d_tab = reinterpret_cast<JamSpliceFrame *>(ctx->jam_update + o_splice);
+        JPK_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(JamSpliceFrame), hipMemcpyHostToDevice, ctx->stream));
+        JPK_TRY(jpk_jam_splice_enqueue(ctx, d_tab, (uint32_t)tab.size(), u.out + *pos, o, u.in, u.in + u.in_len));
+    }
+    JPK_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof_on) jpk_prof_resolve(ctx);
+    for (int32_t f = ps.f0; f < ps.f1; f++) {
+        const JamSpliceFrame &t = tab[(size_t)(f - ps.f0)];
+        done.push_back(ix->fr[(size_t)f]);
+        JamFrame &d = done.back();
+        d.payload_off = *pos + (int64_t)t.off + JPK_JAM_HEADER_BYTES;
+        if (!t.kept) { d.psize = t.psize; d.crc = t.crc; }
+    }
+    *pos += (int64_t)o;
+    return JPK_OK;
+}
+
+// the tail: new frames behind the last one, through the passes of the whole-archive writer of the index's kind (host: staged pass by pass)
+int jam_update_tail(jpk_ctx *ctx, const JamUpdate &u, int64_t *pos, std::vector<JamFrame> &done)
+{
+    const int kind = jam_update_tail_kind(u.ix);
+    const int32_t bs = u.tail_block_size;
+    const int64_t step = (int64_t)jam_pass_frames(bs) * bs;
+    for (int64_t o = 0; o < u.tail_len; o += step) {
+        const int64_t len = std::min(step, u.tail_len - o);
+        const size_t first = done.size();
+        int64_t got = 0;
+        if (u.host) {
+            const int64_t room = jam_compress_bound(len, bs, kind != JAM_PLAIN);
+            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_in, &ctx->stage_in_cap, (size_t)len + 64));
+            JPK_TRY(jpk_buf_ensure(ctx, &ctx->stage_res, &ctx->stage_res_cap, (size_t)room + 64));
+            JPK_HIP(hipMemcpyAsync(ctx->stage_in, u.tail + o, (size_t)len, hipMemcpyHostToDevice, ctx->stream));
+            JPK_TRY(jam_compress_pass(ctx, ctx->stage_in, len, bs, ctx->stage_res, room, &got, u.in_flight, kind, u.flags, &done));
+            if (got > u.out_cap - *pos) return JPK_E_CAPACITY;
+            JPK_HIP(hipMemcpyAsync(u.out + *pos, ctx->stage_res, (size_t)got, hipMemcpyDeviceToHost, ctx->stream));
+            JPK_HIP(hipStreamSynchronize(ctx->stream));
+        } else {
+            JPK_TRY(jam_compress_pass(ctx, u.tail + o, len, bs, u.out + *pos, u.out_cap - *pos, &got, u.in_flight, kind, u.flags, &done));
+        }
+        for (size_t i = first; i < done.size(); i++) done[i].payload_off += *pos;
+        *pos += got;
+    }
+    return JPK_OK;
+}
+
+// the update behind its checks.  ctx may be NULL when the plan has no pass and there is no tail (the host form then makes no device call)
+int jam_update_run(jpk_ctx *ctx, const JamUpdate &u, const jup::Plan &plan, int64_t bound)
+{
+    std::vector<JamFrame> done;
+    done.reserve(u.ix->fr.size());
+    int64_t pos = 0;
+    int rc = JPK_OK;
+    for (size_t p = 0; p < plan.passes.size() && rc == JPK_OK; p++) rc = jam_update_pass(ctx, u, plan, plan.passes[p], &pos, done);
+    if (rc == JPK_OK) rc = jam_update_kept(ctx, u, plan.tail_f0, (int32_t)u.ix->fr.size(), &pos, done);
+    if (rc == JPK_OK) rc = jam_update_tail(ctx, u, &pos, done);
+    if (rc != JPK_OK) {
+        if (rc == JPK_E_CAPACITY) *u.out_len = bound;
+        return rc;
+    }
+    if (!(*u.new_index = jam_index_make(done, pos, -1, u.ix->kind))) return JPK_E_ALLOC;
+    *u.out_len = pos;
+    return JPK_OK;
+}
+}  // namespace
+
+extern "C" int64_t jpk_jam_update_bound(const jpk_jam_index *index, int32_t n, const int64_t *off, const int64_t *len, int64_t tail_len, int32_t tail_block_size)
+{
+    try {
+        jup::Plan plan;
+        int64_t bound = 0;
+        const int rc = jam_update_plan(index, n, off, len, tail_len, tail_block_size, &plan, &bound, nullptr);
+        return rc != JPK_OK ? rc : bound;
+    } catch (const std::bad_alloc &) {
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_dev_jam_update(jpk_ctx *ctx, const jpk_jam_index *index, const uint8_t *d_in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                                  const uint8_t *const *d_src, const uint8_t *d_tail, int64_t tail_len, int32_t tail_block_size, uint32_t flags, int32_t in_flight,
+                                  uint8_t *d_out, int64_t out_cap, int64_t *out_len, jpk_jam_index **new_index, int32_t *rewritten, int32_t *bad_frame)
+{
+    // (the argument checks and the first capacity answer come before the first device call)
+    if (!ctx) return JPK_E_ARG;
+    try {
+        const JamUpdate u{index, d_in, in_len, n, off, len, d_src, d_tail, tail_len, tail_block_size, flags, in_flight, d_out, out_cap, out_len, new_index, rewritten,
+                          bad_frame, false};
+        jup::Plan plan;
+        int64_t bound = 0;
+        JPK_TRY(jam_update_check(u, &plan, &bound));
+        JPK_HIP(hipSetDevice(ctx->device));
+        return jam_update_run(ctx, u, plan, bound);
+    } catch (const std::bad_alloc &) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return JPK_E_ALLOC;
+    }
+}
+
+extern "C" int jpk_jam_update(const jpk_jam_index *index, const uint8_t *in, int64_t in_len, int32_t n, const int64_t *off, const int64_t *len,
+                              const uint8_t *const *src, const uint8_t *tail, int64_t tail_len, int32_t tail_block_size, uint32_t flags, int32_t in_flight, uint8_t *out,
+                              int64_t out_cap, int64_t *out_len, jpk_jam_index **new_index, int32_t *rewritten, int32_t *bad_frame)
+{
+    jpk_ctx *ctx = nullptr;
+    try {
+        const JamUpdate u{index, in, in_len, n, off, len, src, tail, tail_len, tail_block_size, flags, in_flight, out, out_cap, out_len, new_index, rewritten, bad_frame,
+                          true};
+        jup::Plan plan;
+        int64_t bound = 0;
+        JPK_TRY(jam_update_check(u, &plan, &bound));
+        // no frame to rewrite and no tail: jpk_jam_repair's copies, and no device is looked for
+        if (!plan.passes.empty() || tail_len > 0) JPK_TRY(jpk_host_enter(&ctx, 0));
+        return jam_update_run(ctx, u, plan, bound);
+    } catch (const std::bad_alloc &) {
+        if (ctx) (void)hipStreamSynchronize(ctx->stream);
         return JPK_E_ALLOC;
     }
 }
