@@ -28,8 +28,17 @@ Events no valid stream reaches would go to UNREACHABLE, with the argument; the o
 The exponent model is kept for lanes 0..7 only: lanes 8..63 hold HI = 65536 for good (their mix target is 65536), lane 7 does too, and
 the lowest lane whose HI is above the range is taken, so no lane behind 7 is ever picked.
 
-The inputs are valid streams the oracle makes from crafted texts; none is mutated.  CASES are one-chunk texts, CHAINS lists of texts
-whose streams are concatenated (a valid chain: the test decodes every one with the oracle), BATCH block streams for one batched call."""
+The valid inputs are streams the oracle makes from crafted texts; none is mutated.  CASES are one-chunk texts, CHAINS lists of texts
+whose streams are concatenated (a valid chain: the test decodes every one with the oracle), BATCH block streams for one batched call.
+
+The refusal side (at the end of the file): REFUSED are streams built field by field and symbol by symbol from the oracle's pieces so
+that ONE acceptance test of the scheme refuses each (REASON names it; where the format ties two tests together both are named and the
+stream that separates them stands beside it), STILL_ACCEPTED their accepted neighbours, REFUSAL_MUTANTS the scheme with one such test
+dropped or moved by one.  Every acceptance test logs a refuse-* event of its own.  run, tot and carry_s of k_dec_rle, the header's
+values and fsum are kept in 32 bits as the kernels keep them: two of the streams depend on the wrap.  The model asserts its own bounds
+on the way -- every in[p - k] of the header walk inside the chunk's header, every gather step inside the chunk's symbols, every rank
+store below olen, the queue's reads clipped to the input as load() clips them: a stream on which verdict() returns has left no buffer
+in the scheme, which is the argument test_gpu_dec_refusals.py makes before it hands the stream to a kernel."""
 import collections
 import functools
 
@@ -90,11 +99,32 @@ RLE_MUTANTS = (
     "gather-limit-22",           # nb <= 22 in the gather's loop
 )
 BATCH_MUTANTS = ("no-rank-clear",)      # jpk_ans_decode_batch without the memset of the rank arrays
-MUTANTS = HDR_MUTANTS + QUEUE_MUTANTS + RANS_MUTANTS + RLE_MUTANTS + BATCH_MUTANTS
-# mutant -> why no valid stream can tell it from the scheme
+# one acceptance test dropped, or moved by one: told apart by a refused stream (REFUSED) or by an accepted neighbour
+REFUSAL_MUTANTS = (
+    "no-nlead-limit",            # k_dec_headers without nlead > 4
+    "no-since-limit",            # without since > 4
+    "no-freq-limit",             # without x > ANS_CHUNK on a frequency
+    "no-olen-limit", "olen-ge-chunk",       # without olen > ANS_CHUNK; olen >= ANS_CHUNK
+    "no-rlen-limit",             # without rlen > olen
+    "no-clen-fit",               # without clen > len - ip
+    "no-clen-min", "clen-lt-15",            # without clen < 16; clen < 15
+    "no-total-check",            # without total != olen
+    "no-states-check",           # k_dec_rans without the four R != RANS_L
+    "no-taken-check", "taken-ge-clen",      # without bq.taken() > clen; taken() >= clen
+    "no-nb-limit", "nb-limit-21",           # k_dec_rle without nb > 20; nb > 21
+    "no-store-flag", "run-le-olen",         # without the else atomicOr behind run < olen; run <= olen
+    "no-carry-check",            # without carry_s != olen
+)
+MUTANTS = HDR_MUTANTS + QUEUE_MUTANTS + RANS_MUTANTS + RLE_MUTANTS + BATCH_MUTANTS + REFUSAL_MUTANTS
+# mutant -> why no stream, valid or not, can tell it from the scheme (the test runs them on every refused stream too)
+_SINCE = ("`since` only ends the walk early.  Without it the walk goes on to the next window with nval < 259, so the first terminator "
+          "there is a header value: its nlead = l + since >= since > 4 and `nlead > 4` refuses it; with no terminator in that window "
+          "since grows by 64, and the windows end at pos >= len, which refuses too.  Either way the chunk is refused and nothing of it "
+          "is listed.  On a malformed header the limit decides which test refuses, never whether")
 EQUIVALENT = {
     "since-limit-5": "a LEB128 value has at most five bytes, four of them continuation bytes: in a valid header `since` never exceeds 4, "
-                     "so neither limit is ever met; the two differ only on a malformed header",
+                     "so neither limit is ever met.  " + _SINCE,
+    "no-since-limit": _SINCE,
     "load-g-negative-unchecked": "g = gbase + 4 (64 w + l) >= gbase = in_off - a, and a chunk's payload starts behind its header of at least "
                                  "259 bytes, so in_off - a >= 256 > 0: the test guards streams that begin with a payload, which the format "
                                  "does not have",
@@ -102,13 +132,23 @@ EQUIVALENT = {
                      "of the state pairs gives symbol j the pair (R0, R1) for even j and (R2, R3) for odd j, as the tile loop does, lanes "
                      "0..63 are all below `left` = 64 and are all stored, and the final check looks at all four states",
     "gather-limit-22": "the loop's limit only bounds the walk over a malformed group; a valid chunk decodes to at most 2^20 bytes, so a group "
-                       "has at most 20 digits, the walk ends on a non-digit or the chunk's start with nb <= 20 and `nb > 20` is never true",
+                       "has at most 20 digits, the walk ends on a non-digit or the chunk's start with nb <= 20 and `nb > 20` is never true.  "
+                       "On a malformed group of 21 digits or more the walk ends with nb = 21 or 22 under one limit and 21, 22 or 23 under "
+                       "the other: all above 20, so the group is refused and its count is never formed",
 }
 # event -> why no stream the encoder makes reaches it
 UNREACHABLE = {
     "rle-no-zero": "the rank coder's list starts in first-appearance order (rank.cpp:45-90), so the first byte of every chunk is at list position 0 "
                    "and codes as rank 0: every non-empty chunk's rank array holds at least one zero, the head of its first symbol's bucket.  "
                    "`rle-one-zero` names the nearest thing a stream has: that zero and no other",
+    "refuse-max-chunks": "nch >= max_chunks needs len / 275 + 2 accepted chunks inside len bytes.  An accepted chunk has 259 header values "
+                         "of at least one byte each and clen >= 16, so it takes 275 bytes or more, and n accepted chunks end at "
+                         "ip >= 275 n; the loop runs only while ip < len, so n < len / 275 + 1 when the test is made",
+    "refuse-ip-past-len": "ip is the byte behind the header's last terminator, and a terminator is a lane with p < len (the ballot tests it): "
+                          "ip <= len for every header the walk completes",
+    "refuse-rle-symbol-over-256": "k_dec_rans forms a symbol as the lane of classes 0..5 (0..63), 64 + m with m <= 63 or 128 + m with "
+                                  "m <= 128: at most 256 whatever the payload holds, and k_dec_rle reads only what k_dec_rans stored "
+                                  "(t < rlen, the look-ahead and the gather stay inside the chunk)",
 }
 
 _FIELDS = ("freq", "olen", "clen", "rlen")
@@ -130,7 +170,10 @@ RLE_EVENTS = ("rle-group-over-thread-edge", "rle-group-over-pass-edge", "rle-loo
               "rle-group-at-chunk-end", "rle-digits-end-then-digits-start", "rle-group-1-digits", "rle-group-2-digits", "rle-group-19-digits",
               "rle-group-20-digits", "rle-store-at-olen-1", "rle-pass-with-carry", "rle-no-zero", "rle-one-zero", "rle-only-zeros")
 BATCH_EVENTS = ("batch-block-offsets-nonzero", "batch-zero-over-dense", "batch-order-not-identity")
-EVENTS = HDR_EVENTS + QUEUE_EVENTS + RANS_EVENTS + RLE_EVENTS + BATCH_EVENTS
+# the three acceptance tests no stream reaches (UNREACHABLE); the refusal side has its own lists, REFUSE_EVENTS and INPUT_EVENTS, beside
+# the streams that reach the others
+DEAD_REFUSALS = ("refuse-max-chunks", "refuse-ip-past-len", "refuse-rle-symbol-over-256")
+EVENTS = HDR_EVENTS + QUEUE_EVENTS + RANS_EVENTS + RLE_EVENTS + BATCH_EVENTS + DEAD_REFUSALS
 
 
 def _log(ev, name, n=1):
@@ -155,9 +198,10 @@ def headers(stream, out_cap, mut=None, ev=None, blk=0):
     ip = op = rp = 0
     status = OK
     infos, freqs = [], []
-    leb_off = LEB_OFF + (0,)
+    leb_off = LEB_OFF + (0,) * 64
     while ip < ln and status == OK:
         if len(infos) >= max_chunks:
+            _log(ev, "refuse-max-chunks")
             status = E_CORRUPT
             break
         _log(ev, f"hdr-start-mod4-{ip % 4}")
@@ -171,8 +215,10 @@ def headers(stream, out_cap, mut=None, ev=None, blk=0):
         bad = False
         since = 0
         nwin = 0
+        fsum_mask = 0xffffffff                 # fsum and its wave sum are 32-bit registers
         while nval < 259:
             if pos >= ln:
+                _log(ev, "refuse-header-truncated")
                 bad = True
                 break
             nwin += 1
@@ -193,27 +239,31 @@ def headers(stream, out_cap, mut=None, ev=None, blk=0):
                     continue
                 prevmask = term & ((1 << l) - 1)
                 nlead = l - (prevmask.bit_length() - 1) - 1 if prevmask else l + since
-                if nlead > 4:
+                if nlead > 4 and mut != "no-nlead-limit":
+                    _log(ev, "refuse-nlead-over-4")
                     bad = True
                     continue
                 p = pos + l
                 x = 0
                 for k in range(nlead, 0, -1):
-                    x = (x << 7) | (s[p - k] if p - k >= 0 else 0)
-                x = (x << 7) | (win[l] & 0x7f)
+                    assert ip <= p - k < ln, "k_dec_headers reads in[p - k] outside the chunk's header"
+                    x = ((x << 7) | s[p - k]) & 0xffffffff
+                x = ((x << 7) | (win[l] & 0x7f)) & 0xffffffff
                 if nlead > 0:
-                    x += leb_off[nlead if mut == "leb-off-nlead" else nlead - 1]
+                    x = (x + leb_off[nlead if mut == "leb-off-nlead" else nlead - 1]) & 0xffffffff
+                    _log(ev, "hdr-5-byte-value-wraps", nlead == 4 and s[p - 4] >> 4 != 0)
                 field = _FIELDS[max(vidx - 255, 0)]
                 if not prevmask and since in (1, 2):
                     _log(ev, f"hdr-{field}-since{since}")
                 if vidx < 256 or (vidx == 256 and mut == "fsum-vidx-le-256"):
-                    if x > CHUNK:
+                    if x > CHUNK and mut != "no-freq-limit":
+                        _log(ev, "refuse-freq-over-chunk")
                         bad = True
                     if vidx < 256:
                         freq[vidx] = x
                         if nlead == 2:
                             _log(ev, "hdr-freq-3-bytes")
-                    fsum[l] += x
+                    fsum[l] = (fsum[l] + x) & fsum_mask
                 else:
                     fields[vidx - 256] += x
             nt = bin(term).count("1")
@@ -234,18 +284,31 @@ def headers(stream, out_cap, mut=None, ev=None, blk=0):
                 since = (64 - term.bit_length()) if nt else since + 64
                 if mut == "since-not-carried":
                     since = 0
-                if since > (5 if mut == "since-limit-5" else 4):
+                if since > (5 if mut == "since-limit-5" else 4) and mut != "no-since-limit":
+                    _log(ev, "refuse-since-over-window" if nt else "refuse-window-without-terminator")
                     bad = True
                     break
                 nval += nt
                 pos += 64
-        olen, clen, rlen = fields
-        total = sum(fsum)
+        olen, clen, rlen = (f & 0xffffffff for f in fields)
+        total = sum(fsum) & fsum_mask
         ip = pos
-        if bad or olen > CHUNK or rlen > olen or ip > ln or clen > ln - ip or clen < 16 or total != olen:
+        # the acceptance test, term by term: a walk that stopped inside the header (nval < 259) has no fields to test
+        tests = () if nval < 259 else (
+            ("refuse-olen-over-chunk", (olen >= CHUNK if mut == "olen-ge-chunk" else olen > CHUNK) and mut != "no-olen-limit"),
+            ("refuse-rlen-over-olen", rlen > olen and mut != "no-rlen-limit"),
+            ("refuse-ip-past-len", ip > ln),
+            ("refuse-clen-past-len", clen > ln - ip and mut != "no-clen-fit"),
+            ("refuse-clen-below-16", clen < (15 if mut == "clen-lt-15" else 16) and mut != "no-clen-min"),
+            ("refuse-total-ne-olen", total != olen and mut != "no-total-check"))
+        for name, fired in tests:
+            _log(ev, name, fired)
+            bad = bad or fired
+        if bad:
             status = E_CORRUPT
             break
         if op + olen > out_cap:
+            _log(ev, f"refuse-capacity-at-chunk-{len(infos) + 1}" if len(infos) < 2 else "refuse-capacity-later")
             status = E_CAPACITY
             break
         _log(ev, "hdr-5-windows", nwin == 5)
@@ -547,8 +610,12 @@ def rans(stream, info, lead=0, mut=None, ev=None):
         _log(ev, f"rlen-above-64-mod4-{rlen % 4}", rlen > 64 and rlen % 4 != 0)
         _log(ev, "tail-odd", left % 2 == 1)
         _log(ev, "queue-taken-equals-clen", bq.taken() == clen)
-    bad = any(r != RANS_L for r in R) or bq.taken() > clen
-    return out, (1 if bad else 0)
+    states = any(r != RANS_L for r in R) and mut != "no-states-check"
+    over = ((bq.taken() >= clen) if mut == "taken-ge-clen" else (bq.taken() > clen)) and mut != "no-taken-check"
+    _log(ev, "refuse-states", states)
+    _log(ev, "refuse-taken-over-clen", over)
+    assert mut is not None or all(0 <= x <= 256 for x in out), "k_dec_rans emits 0..256 only, whatever the payload holds"
+    return out, (1 if states or over else 0)
 
 
 # ---- k_dec_rle ---------------------------------------------------------------------------------------------------------------------------
@@ -568,7 +635,7 @@ def rle(symbols, info, stale=None, mut=None, ev=None):
     carry_s, bad_s = 0, 0
     tracking = ev is not None
     seen_zero = seen_other = False
-    zeros = 0
+    zeros = true_total = 0
     for b0 in range(0, rlen, PASS):
         if tracking:
             _log(ev, "rle-pass-with-carry", b0 > 0 and carry_s != 0)
@@ -578,24 +645,29 @@ def rle(symbols, info, stale=None, mut=None, ev=None):
             sy = src(t)
             cnt = val = 0
             if sy > 256:
+                _log(ev, "refuse-rle-symbol-over-256")
                 bad_s |= 1
             if sy > 1:
                 cnt, val = 1, sy - 1
                 seen_other = True
+                true_total += 1
             elif (t + 1 >= rlen and mut != "lookahead-unguarded") or src(t + 1) > 1:
                 bits = nb = 0
                 u = t
                 floor = b0 if mut == "gather-stops-at-b0" else (-base if mut == "gather-past-chunk-start" else 0)
                 while u >= floor and src(u) <= 1 and nb <= (22 if mut == "gather-limit-22" else 21):
-                    bits |= src(u) << nb
+                    assert mut is not None or 0 <= u < rlen, "k_dec_rle gathers outside the chunk's symbols"
+                    bits = (bits | src(u) << nb) & 0xffffffff
                     nb += 1
                     u -= 1
-                if nb > (19 if mut == "nb-limit-lower" else 20):
+                if nb > {"nb-limit-lower": 19, "nb-limit-21": 21}.get(mut, 20) and mut != "no-nb-limit":
+                    _log(ev, "refuse-rle-21-digits")
                     bad_s |= 1
                 else:
-                    cnt = ((1 << nb) | bits) - 1
+                    cnt = (((1 << nb) | bits) - 1) & 0xffffffff
                 seen_zero = True
                 zeros += cnt
+                true_total += cnt
                 if tracking:
                     first = u + 1
                     _log(ev, "rle-group-over-thread-edge", first // PER_THREAD != t // PER_THREAD)
@@ -607,20 +679,26 @@ def rle(symbols, info, stale=None, mut=None, ev=None):
             elif tracking:
                 _log(ev, "rle-lookahead-over-pass-edge", (t + 1) % PASS == 0)
             if val:
-                if run < olen:
+                if (run <= olen) if mut == "run-le-olen" else (run < olen):
+                    assert 0 <= run < olen, "k_dec_rle stores outside the chunk's rank array"
                     dst[run] = val & 0xff
                     if tracking:
                         _log(ev, "rle-store-at-olen-1", run == olen - 1)
-                else:
+                elif mut != "no-store-flag":
+                    _log(ev, "refuse-rle-store-at-olen")
                     bad_s |= 1
-            run += cnt
-            tot += cnt
-        carry_s += tot
+            run = (run + cnt) & 0xffffffff                              # run, tot and carry_s are 32-bit registers
+            tot = (tot + cnt) & 0xffffffff
+        carry_s = (carry_s + tot) & 0xffffffff
     if tracking:
         _log(ev, "rle-no-zero", rlen > 0 and not seen_zero)
         _log(ev, "rle-one-zero", zeros == 1 and seen_other)
         _log(ev, "rle-only-zeros", rlen > 0 and not seen_other)
-    return bytes(dst), (2 if carry_s != olen or bad_s else 0)
+    mismatch = carry_s != olen and mut != "no-carry-check"
+    _log(ev, "refuse-rle-short", mismatch and carry_s < olen)
+    _log(ev, "refuse-rle-long", mismatch and carry_s > olen)
+    _log(ev, "rle-count-wraps", true_total >> 32 != 0)
+    return bytes(dst), (2 if mismatch or bad_s else 0)
 
 
 # ---- the batch ---------------------------------------------------------------------------------------------------------------------------
@@ -931,3 +1009,330 @@ def stream(oracle, name):
         t.setflags(write=False)
         _streams[name] = (s, t)
     return _streams[name]
+
+
+# ---- refused streams ---------------------------------------------------------------------------------------------------------------------
+# Built field by field from the oracle's own pieces (leb_encode, model_pairs, rans_encode_pairs): for a valid text the result is the
+# oracle's stream byte for byte (test_the_pieces_rebuild_the_oracles_stream), so any header field and any RLE0 symbol sequence can stand in
+# an otherwise well-formed stream.  REFUSED: name -> builder(oracle) -> (stream bytes, out_cap); REASON: name -> the refuse-* events that
+# fire on it (one, wherever the format lets one acceptance test fire alone).  STILL_ACCEPTED: the neighbours both model and oracle decode.
+REFUSE_EVENTS = ("refuse-nlead-over-4", "refuse-since-over-window", "refuse-window-without-terminator", "refuse-header-truncated",
+                 "refuse-freq-over-chunk", "refuse-olen-over-chunk", "refuse-rlen-over-olen", "refuse-clen-past-len", "refuse-clen-below-16",
+                 "refuse-total-ne-olen", "refuse-capacity-at-chunk-1", "refuse-capacity-at-chunk-2", "refuse-capacity-later",
+                 "refuse-states", "refuse-taken-over-clen", "refuse-rle-21-digits", "refuse-rle-store-at-olen", "refuse-rle-short",
+                 "refuse-rle-long", "refuse-max-chunks", "refuse-ip-past-len", "refuse-rle-symbol-over-256")
+INPUT_EVENTS = ("hdr-5-byte-value-wraps", "rle-count-wraps")          # what a crafted input is, not why it is refused
+HEADER_REFUSALS = REFUSE_EVENTS[:13]
+T0_LEN = 300
+
+
+def base_text():
+    """300 bytes over the values 0..22, no two neighbours equal: every count is one LEB byte, values 23..255 have count 0 (one byte
+    0x80 each), and the text holds a zero byte"""
+    return ((np.arange(T0_LEN) * 7) % 23).astype(np.uint8)
+
+
+def side_text():
+    return _no_repeats(40)
+
+
+def leb5(v, extra=0):
+    """the five-byte form of the 32-bit value v; extra: bits 32..34 of the 35 the five bytes hold, which a 32-bit register drops"""
+    raw = (v - LEB_OFF[3]) & 0xffffffff
+    return bytes([(raw >> 28) | (extra << 4), (raw >> 21) & 0x7f, (raw >> 14) & 0x7f, (raw >> 7) & 0x7f, (raw & 0x7f) | 0x80])
+
+
+def payload_of(oracle, syms):
+    """the rANS payload of an RLE0 symbol sequence (any sequence over 0..256)"""
+    return oracle.rans_encode_pairs(oracle.model_pairs(np.asarray(syms, dtype=np.uint16))).tobytes()
+
+
+def fields_of(oracle, freq, olen, clen, rlen):
+    """the header's 259 values, one bytes object each"""
+    return [oracle.leb_encode(int(v)) for v in list(freq) + [olen, clen, rlen]]
+
+
+def chunk_of_symbols(oracle, freq, olen, syms):
+    pay = payload_of(oracle, syms)
+    return fields_of(oracle, freq, olen, len(pay), len(syms)), pay
+
+
+def chunk_of_text(oracle, text):
+    """(fields, payload, freq) of the chunk the oracle's encoder makes of a text of at most 2^20 bytes"""
+    r, f = oracle.rank_encode(text)
+    fields, pay = chunk_of_symbols(oracle, f, len(text), oracle.rle_encode(r))
+    return fields, pay, f
+
+
+def _join(fields, pay):
+    return b"".join(fields) + bytes(pay)
+
+
+def digits(v):
+    """the RLE0 digit group of a run of v zeros: v + 1 in binary without its leading one"""
+    return [int(c) for c in bin(v + 1)[3:]]
+
+
+def _base(oracle):
+    fields, pay, f = chunk_of_text(oracle, base_text())
+    assert all(len(x) == 1 for x in fields[:256]) and not f[23:].any() and f[0] > 0
+    return fields, pay, f
+
+
+def _side(oracle):
+    return oracle.ans_encode(side_text()).tobytes()
+
+
+def _placed(oracle, bad, k, ends, olen=T0_LEN):
+    """`bad` as chunk k (1 or 3) of a chain of four with valid neighbours; ends: nothing can follow it (the stream is cut in it)"""
+    v = _side(oracle)
+    n = (k - 1) + (0 if ends else 4 - k)
+    return v * (k - 1) + bad + (b"" if ends else v * (4 - k)), n * len(side_text()) + olen
+
+
+def _rle_freq(olen):
+    f = [0] * 256
+    f[0], f[65], f[66] = 1, olen - 2, 1
+    return f
+
+
+def _hdr_case(edit, ends=False):
+    """edit(oracle, fields, pay, freq) -> the bad chunk's bytes, from the base chunk's pieces"""
+    def at(k):
+        def build(oracle):
+            fields, pay, f = _base(oracle)
+            return _placed(oracle, edit(oracle, list(fields), pay, f.tolist()), k, ends)
+        return build
+    return at
+
+
+def _set(i, value):
+    def edit(oracle, fields, pay, f):
+        fields[i] = value(oracle, fields, pay, f) if callable(value) else value
+        return _join(fields, pay)
+    return edit
+
+
+def _refreq(changes, olen=None):
+    def edit(oracle, fields, pay, f):
+        for s, v in changes.items():
+            fields[s] = leb5(v) if v >= 1 << 31 else oracle.leb_encode(v)
+        if olen is not None:
+            fields[256] = oracle.leb_encode(olen)
+        return _join(fields, pay)
+    return edit
+
+
+def _rlen_plus_1(oracle, fields, pay, f):
+    fields, pay = chunk_of_symbols(oracle, f, T0_LEN, [2] * (T0_LEN + 1))
+    return _join(fields, pay)
+
+
+def _empty_chunk(oracle, clen=16):
+    return _join(fields_of(oracle, [0] * 256, 0, clen, 0), RANS_L.to_bytes(4, "little") * 4)
+
+
+# name -> (edit of the base chunk, the stream ends in it, the events that fire)
+_HDR = {
+    "nlead-6-bytes-in-window": (_set(30, bytes(5) + b"\x80"), False, ("refuse-nlead-over-4",)),
+    "since-5-at-window-edge": (_set(59, bytes(5) + b"\x80"), False, ("refuse-since-over-window",)),
+    "window-of-64-continuation-bytes": (_set(64, bytes(64) + b"\x80"), False, ("refuse-window-without-terminator",)),
+    "cut-at-window-edge": (lambda o, fields, pay, f: _join(fields, pay)[:128], True, ("refuse-header-truncated",)),
+    # the one byte of the last window is a terminator; the 63 lanes behind it read as 0, continuation bytes
+    "cut-one-byte-past-window-edge": (lambda o, fields, pay, f: _join(fields, pay)[:129], True, ("refuse-since-over-window",)),
+    "freq-chunk-plus-1": (_refreq({30: CHUNK + 1}), False, ("refuse-freq-over-chunk", "refuse-total-ne-olen")),
+    # two counts of 2^31: their 32-bit sum is 0, `total` is olen again and only the limit on a single count refuses
+    "freq-two-of-2^31": (_refreq({30: 1 << 31, 31: 1 << 31}), False, ("refuse-freq-over-chunk",)),
+    "olen-chunk-plus-1": (_refreq({30: CHUNK - T0_LEN, 31: 1}, CHUNK + 1), False, ("refuse-olen-over-chunk",)),
+    "rlen-olen-plus-1": (_rlen_plus_1, False, ("refuse-rlen-over-olen",)),
+    # five bytes whose 35 bits wrap onto a value with bit 31 set: above olen as the kernel reads it, below zero as the oracle does
+    "rlen-top-bit-set": (_set(258, lambda o, fields, pay, f: leb5(0x80000000 | 3, 5)), False, ("refuse-rlen-over-olen",)),
+    "clen-past-len": (_set(257, lambda o, fields, pay, f: o.leb_encode(len(pay) + 1)), True, ("refuse-clen-past-len",)),
+    "total-olen-minus-1": (_set(0, lambda o, fields, pay, f: o.leb_encode(f[0] - 1)), False, ("refuse-total-ne-olen",)),
+    "total-olen-plus-1": (_set(0, lambda o, fields, pay, f: o.leb_encode(f[0] + 1)), False, ("refuse-total-ne-olen",)),
+}
+
+
+def _clen_15(k):
+    def build(oracle):
+        return _placed(oracle, _empty_chunk(oracle, 15)[:-1], k, True, 0)
+    return build
+
+
+def _capacity(nvalid):
+    def build(oracle):
+        fields, pay, _ = _base(oracle)
+        return _side(oracle) * nvalid + _join(fields, pay), nvalid * len(side_text()) + T0_LEN - 1
+    return build
+
+
+def _flipped(oracle):
+    """one bit of one payload byte behind the 16 state bytes: the last such bit, counted from the payload's end, under which the final
+    states miss RANS_L and no byte beyond clen is taken (a flip may also send the decoder for more bytes than the chunk has; the model
+    says which flips do)"""
+    fields, pay, _ = _base(oracle)
+    for at in range(len(pay) - 1, 15, -1):
+        for bit in range(8):
+            s = _join(fields, pay[:at] + bytes([pay[at] ^ (1 << bit)]) + pay[at + 1:])
+            if verdict(s, T0_LEN)[1] == ("refuse-states",):
+                return s, T0_LEN
+    raise AssertionError("no flip isolates the states check")
+
+
+def _truncated(oracle):
+    fields, pay, _ = _base(oracle)
+    fields[257] = oracle.leb_encode(len(pay) - 1)
+    return _join(fields, pay[:-1]), T0_LEN
+
+
+def second_text_for(last):
+    """a text whose header starts with the byte `last`: that byte is the LEB form of its count of zero bytes, or the first of two"""
+    zeros = (last & 0x7f) if last & 0x80 else (last << 7) + 127
+    return np.concatenate((np.zeros(zeros, dtype=np.uint8), _no_repeats(30)))
+
+
+def _taken_over_clen(oracle):
+    """A, B with A's clen one short and B's first header byte lent to A as its last payload byte: every state of A ends at RANS_L and
+    only taken() > clen refuses it; the oracle refuses through p >= end"""
+    fields, pay, _ = _base(oracle)
+    b = second_text_for(pay[-1])
+    enc_b = oracle.ans_encode(b).tobytes()
+    assert enc_b[0] == pay[-1]
+    fields[257] = oracle.leb_encode(len(pay) - 1)
+    return _join(fields, pay) + enc_b[1:], T0_LEN + len(b)
+
+
+def _rle_case(make):
+    """make() -> (symbols, olen): under a valid header whose counts sum to olen"""
+    def build(oracle):
+        syms, olen = make()
+        fields, pay = chunk_of_symbols(oracle, _rle_freq(olen), olen, syms)
+        return _join(fields, pay), olen
+    return build
+
+
+_G = [1] * 6                                                          # a group of six digits: 126 zeros, so that rlen stays below olen
+
+
+def _n2(n):
+    return [2] * n                                                    # n ranks of 1, one byte each
+
+
+def _wraps():
+    """2048 x (2^21 - 2 zeros, a separator) and a last group of 2^20 + 2048 zeros: 2^32 + 2^20 in all, which a 32-bit register holds as
+    2^20 = olen.  Every separator lands at run >= olen; only their refused stores tell"""
+    syms = ([1] * 20 + [2]) * 2048 + digits((1 << 20) + 2048)
+    assert len(syms) == 43028
+    return syms, CHUNK
+
+
+REFUSED = collections.OrderedDict()
+REASON = {}
+for _n, (_edit, _ends, _why) in _HDR.items():
+    for _k in (1, 3):
+        REFUSED[f"{_n}@{_k}"] = _hdr_case(_edit, _ends)(_k)
+        REASON[f"{_n}@{_k}"] = _why
+for _k in (1, 3):
+    REFUSED[f"clen-15@{_k}"] = _clen_15(_k)
+    REASON[f"clen-15@{_k}"] = ("refuse-clen-below-16",)
+for _n, _b, _why in (
+        ("capacity-at-chunk-1", _capacity(0), ("refuse-capacity-at-chunk-1",)),
+        ("capacity-at-chunk-2", _capacity(1), ("refuse-capacity-at-chunk-2",)),
+        ("capacity-at-chunk-4", _capacity(3), ("refuse-capacity-later",)),
+        ("rans-last-byte-flipped", _flipped, ("refuse-states",)),
+        # the queue's byte-wise load() gives 0 for the missing byte: the states miss RANS_L and one byte more than clen was taken
+        ("rans-payload-truncated", _truncated, ("refuse-states", "refuse-taken-over-clen")),
+        ("rans-taken-over-clen", _taken_over_clen, ("refuse-taken-over-clen",)),
+        ("rle-21-digits-at-start", _rle_case(lambda: ([0] * 21 + _n2(50) + _G + _n2(50), 226)), ("refuse-rle-21-digits",)),
+        ("rle-21-digits-in-the-middle", _rle_case(lambda: (_n2(50) + _G + _n2(25) + [0, 1] * 10 + [1] + _n2(25), 226)), ("refuse-rle-21-digits",)),
+        ("rle-21-digits-over-pass-edge", _rle_case(lambda: (_G + _n2(4085) + [1] * 21 + _n2(50), 126 + 4135)), ("refuse-rle-21-digits",)),
+        ("rle-21-digits-at-end", _rle_case(lambda: (_n2(50) + _G + _n2(50) + [0] * 21, 226)), ("refuse-rle-21-digits",)),
+        ("rle-25-digits", _rle_case(lambda: (_n2(50) + _G + _n2(25) + [1, 0] * 12 + [1] + _n2(25), 226)), ("refuse-rle-21-digits",)),
+        # the last rank lands at run == olen: its store is refused, and with it the count is olen + 1
+        ("rle-store-at-olen", _rle_case(lambda: (_n2(50) + _G + _n2(50), 225)), ("refuse-rle-store-at-olen", "refuse-rle-long")),
+        ("rle-short", _rle_case(lambda: (_n2(50) + _G + _n2(50), 227)), ("refuse-rle-short",)),
+        ("rle-long-by-digits", _rle_case(lambda: (_n2(50) + digits(10), 59)), ("refuse-rle-long",)),
+        ("rle-count-wraps", _rle_case(_wraps), ("refuse-rle-store-at-olen",))):
+    REFUSED[_n] = _b
+    REASON[_n] = _why
+
+
+def _surplus(k):
+    def build(oracle):
+        fields, pay, _ = _base(oracle)
+        fields[257] = oracle.leb_encode(len(pay) + k)
+        return _join(fields, pay + bytes([0x5A, 0x80, 0xFF, 0x00][:k])), T0_LEN
+    return build
+
+
+def _with_empty(where):
+    def build(oracle):
+        v, e = _side(oracle), _empty_chunk(oracle)
+        return {"alone": e, "first": e + v + v, "middle": v + e + v, "last": v + v + e}[where], 0 if where == "alone" else 2 * len(side_text())
+    return build
+
+
+def _wrapped_olen(oracle):
+    fields, pay, _ = _base(oracle)
+    fields[256] = leb5(T0_LEN, 7)
+    return _join(fields, pay), T0_LEN
+
+
+MOVED = (2, 7)                                                        # the counts moved by +1 and -1
+
+
+def moved_text():
+    return np.random.default_rng(0).integers(0, 23, T0_LEN).astype(np.uint8)
+
+
+def _freq_two_moved(oracle):
+    """the sum is right, two counts are not: the header accepts, the ranks are the valid ones, and the bytes are whatever the rank
+    decoder makes of buckets that start one place off.  rank_rows_model says when that is defined: the text holds a zero byte, and no
+    two buckets name the same start position -- the base text cannot serve, every rank behind a first one is 22 there, and for two
+    buckets that name one position the kernel's winner and the reference's differ by design (the test asserts that this text and this
+    pair are inside the scope)"""
+    fields, pay, f = chunk_of_text(oracle, moved_text())
+    fields[MOVED[0]], fields[MOVED[1]] = oracle.leb_encode(int(f[MOVED[0]]) + 1), oracle.leb_encode(int(f[MOVED[1]]) - 1)
+    return _join(fields, pay), T0_LEN
+
+
+def _valid_base(oracle):
+    fields, pay, _ = _base(oracle)
+    return _join(fields, pay), T0_LEN
+
+
+STILL_ACCEPTED = collections.OrderedDict(
+    [("valid-base", _valid_base)] + [(f"surplus-payload-{k}", _surplus(k)) for k in (1, 3, 4)] +
+    [(f"empty-chunk-{w}", _with_empty(w)) for w in ("alone", "first", "middle", "last")] +
+    [("olen-5-bytes-wrapped", _wrapped_olen), ("freq-equals-chunk", lambda oracle: (stream(oracle, "zeros-1MiB")[0].tobytes(), CHUNK)),
+     ("freq-two-moved", _freq_two_moved)])
+
+_built = {}
+
+
+def crafted(oracle, name):
+    """(stream as a read-only uint8 array, out_cap) of a REFUSED or STILL_ACCEPTED name: built once, shared, left unchanged"""
+    if name not in _built:
+        s, cap = (REFUSED.get(name) or STILL_ACCEPTED[name])(oracle)
+        a = np.frombuffer(bytes(s), dtype=np.uint8)
+        _built[name] = (a, cap)
+    return _built[name]
+
+
+def verdict(stream, out_cap, lead=0, mut=None):
+    """-> (status, the refuse-* and input events that fired, the stage that refused: "headers", "payload" or None).  The model's bounds
+    assertions run on the way: this is the walk every stream takes before a kernel sees it"""
+    ev = {}
+    status, infos, _, totals = headers(stream, out_cap, mut, ev)
+    stage = "headers" if status != OK else None
+    if status == OK:
+        syms, bits = [STALE_SYM] * totals[1], 0
+        for ci in infos:
+            got, b = rans(stream, ci, lead, mut, ev)
+            syms[ci.rle_off: ci.rle_off + ci.rlen] = got
+            bits |= b
+        for ci in infos:
+            bits |= rle(syms, ci, None, mut, ev)[1]
+        if bits:
+            status, stage = E_CORRUPT, "payload"
+    return status, tuple(sorted(e for e in ev if e in REFUSE_EVENTS)), stage, {e: ev[e] for e in ev if e in INPUT_EVENTS}
