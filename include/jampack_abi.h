@@ -725,7 +725,10 @@ JPK_API int jpk_dev_suffix_array(jpk_ctx *ctx, const uint8_t *d_t, int32_t n, in
 JPK_API int jpk_dev_sort_pairs_u64(jpk_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, int32_t n, int32_t bit_lo, int32_t bit_hi);
 /* exclusive prefix sum of uint32[n] in place; returns the total in *total */
 JPK_API int jpk_dev_exclusive_scan_u32(jpk_ctx *ctx, uint32_t *d_data, int32_t n, uint32_t *total);
-/* entropy sub-stages of one chunk: rank array -> RLE0 symbols; symbols -> packed (low | freq<<16) pairs */
+/* entropy sub-stages of one chunk: rank array -> RLE0 symbols; symbols -> packed (low | freq<<16) pairs.
+ * jpk_dev_model_pairs takes the symbols of ONE chunk: rlen > JPK_ANS_CHUNK is JPK_E_ARG, refused with the other arguments before anything is allocated or launched (beyond a chunk a
+ * class can outrun the QuasiModel's rebuild schedule as the encoder tabulates it).  PRECONDITION: every symbol is <= 256, as RLE0
+ * produces them; the probe does not check it, and the kernels index their tables by the symbol. */
 JPK_API int jpk_dev_rle_encode(jpk_ctx *ctx, const uint8_t *d_ranks, int32_t len, uint16_t *d_rle, int32_t *rlen);
 JPK_API int jpk_dev_model_pairs(jpk_ctx *ctx, const uint16_t *d_rle, int32_t rlen, uint32_t *d_pairs);
 

@@ -552,6 +552,7 @@ extern "C" int jpk_dev_model_pairs(jpk_ctx *ctx, const uint16_t *d_rle, int32_t 
 {
     JPK_ENTER(ctx);
     if (rlen < 0 || (rlen > 0 && (!d_rle || !d_pairs))) return JPK_E_ARG;
+    if (rlen > JPK_ANS_CHUNK) return JPK_E_ARG;      // one chunk: beyond it a class can pass qbound(NQ) ordinals and qinterval would clamp
     return jpk_model_pairs_device(ctx, d_rle, rlen, d_pairs);
 }
 

@@ -30,7 +30,7 @@ __device__ __forceinline__ int class_alpha(int e) { return e == 7 ? 129 : (e == 
 // QuasiModel rebuild schedule (model.cpp:160-204): the model is rebuilt after EXP+1 symbols, EXP = 8,16,..,65536.
 // Interval q of a class covers class-ordinals [qbound(q), qbound(q+1)) and is coded with the CDF built from the
 // histogram of interval q-1 (interval 0: uniform CDF).
-__host__ __device__ __forceinline__ uint32_t qbound(int q)
+__host__ __device__ __forceinline__ constexpr uint32_t qbound(int q)
 {
     // q <= 13: sum_{k<q} (8*2^k + 1) = 8*(2^q - 1) + q ; afterwards +65537 each
     if (q <= 13) return 8u * ((1u << q) - 1u) + (uint32_t)q;
@@ -42,6 +42,10 @@ __device__ __forceinline__ int qinterval(uint32_t k)
     while (q + 1 < NQ && qbound(q + 1) <= k) q++;
     return q;
 }
+// one chunk never reaches the clamp: even a chunk of one class stays below interval NQ (its deepest interval is 27), and a table row
+// holds the widest alphabet, its cdf end and the word k_pairs reads behind the top mantissa (cdf[m + 1], m <= 128)
+static_assert(qbound(NQ) > (uint32_t)JPK_ANS_CHUNK, "qbound(NQ) > JPK_ANS_CHUNK: qinterval's clamp is unreachable inside a chunk");
+static_assert(QSTRIDE >= 130, "a row holds cdf[0 .. 129] of the alphabet of 129");
 
 // uniform CDF entry i of an alphabet of A symbols (model.cpp:85-95)
 __host__ __device__ __forceinline__ uint32_t uniform_cdf(int A, int i)
