@@ -5,8 +5,9 @@
 // Parallel restructuring (bytes identical to the reference):
 //   rank coding   MTF rank of byte i = #symbols whose last occurrence is later than the previous occurrence of
 //                 T[i]; last-occurrence tables are carried across 4 KiB tiles by a per-symbol max-scan, so every
-//                 tile is an independent wave-sequential pass over its run heads (lanes hold the 256 time stamps,
-//                 v_cmp -> popcount); the bucket scatter uses per-tile per-symbol prefix counts.
+//                 tile is independent, and inside a tile every run head counts its own window (the heads between it and
+//                 the previous head of its symbol whose symbol does not come again before it: no recency list, no walk
+//                 from head to head); the bucket scatter uses per-tile per-symbol prefix counts.
 //   RLE0          run heads found per tile, run lengths through a per-chunk "zeros that follow the tile" table,
 //                 output offsets by scans.
 //   models        QuasiModel tables only change at fixed per-class symbol counts -> built in parallel from

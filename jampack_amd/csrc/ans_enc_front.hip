@@ -85,30 +85,40 @@ __global__ __launch_bounds__(256) void k_enc_prep(EncDims d, uint32_t *__restric
     bstart[(size_t)c * 256 + s] = b;
 }
 
-// one wave per tile: wave-sequential MTF on the recency list itself + bucket scatter (rank.cpp:69-87).
-// The list lives in 4 registers per lane: lane p of lst_j holds the symbol at list position 64 j + p (0xFFFF behind the symbols seen
-// so far in the chunk: a symbol's first occurrence has rank = number of distinct symbols before it, i.e. it sits at the first free
-// position).  A head's rank is its position -- one v_cmp + s_ff1 when it is among the first 64, which is nearly every head of a BWT
-// image -- and the move to front is one DPP wave_shr:1 under a lane mask (positions below it move down by one, the symbol enters at
-// lane 0).  Positions 64.. are searched, and the shift carried from register to register, only when the first compare misses.  The
-// list at the start of the tile is rebuilt from the carried last-occurrence stamps: position = number of symbols with a later stamp.
-// Only run HEADS are walked serially (a repeat has rank 0, leaves the list unchanged and lands right behind its head in the same
-// bucket): a ballot marks them in each 64-byte group, the loop visits the set bits, and every lane then derives its own
-// (destination, rank) from the record of the head at or before it.  All loop control is wave-uniform (scalar branches, no exec-mask
-// loops): the wave index is read with readfirstlane.  A per-wave LDS table holds the bucket write positions (wave-uniform accesses).
-__device__ __forceinline__ uint32_t mtf_shr1(uint32_t carry_in, uint32_t v)          // lane i <- lane i - 1, lane 0 <- carry_in
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)carry_in, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
+// one wave per tile: the rank of every run head counted in its own window + bucket scatter (rank.cpp:69-87).  No recency list is kept:
+// in the index space of the tile's run heads (a repeat has rank 0 and lands right behind its head in the same bucket), with P(k) the
+// previous head of head k's symbol and N(j) the next head of head j's symbol,
+//     rank(k) = #{ j : P(k) < j < k and N(j) >= k }
+// -- every distinct symbol between the two occurrences, counted once at its last head there.  The wave goes over the tile in 64-byte
+// groups.  One wave match of the group's bytes gives every byte its bucket position (pos[sym] + equal bytes below it in the group; the
+// last lane of each set advances pos[sym]) and every head its P (the nearest equal head below it in the group, else lasth[sym]); the head
+// then writes nx[k] = INF and nx[P(k)] = k, so that when a group counts, nx[j] holds N(j) for every j whose N(j) lies at or before
+// the group and INF (>= every k) otherwise -- exactly what the compare needs.  The count itself has no running state:
+//   * every head tests the RW_CAP = 32 positions right below it from its own lane: one 64-byte LDS read from one address, two slots
+//     compared per subtraction.  83 % of the windows of the bench's first block end there (profiles/rank_window_ab.txt: median 6,
+//     75 % 20, 90 % 55, 99 % 227 heads);
+//   * a head whose window is longer gets the wave for the rest of it: 64 positions per LDS read, compare, ballot and popcount, two
+//     such heads at a time so that their reads overlap;
+//   * a symbol's FIRST head in the tile has no P in the tile.  Its window is the tile so far -- the number of first heads before it, a
+//     counter -- plus what the chunk carried in: the symbols without a head in the tile yet whose stamp (k_enc_prep's last occurrence
+//     before the tile) is later than its own.  The four stamp registers are compared as the old tile-start rebuild compared them; a symbol
+//     that got its head drops out by taking stamp -2.  At most 256 of these per tile, walked in order.
+// A head depends on no head before it: only the two tables (pos, lasth) run along the groups, at a handful of instructions per GROUP.
+// LDS: 9.7 KB per wave (nx is sized for a tile of 4096 heads, plus RW_CAP slots in front for the own-lane read of the tile's first heads
+// and the 63 positions a last window step reads past its end), 38.75 KB per workgroup of four tiles: four workgroups per CU, 4 waves
+// per SIMD (the serial walk had 16).  All loop control is wave-uniform (scalar branches).  tests/rank_window_model.py restates it.
+constexpr int RW_CAP = 32;                    // window positions a head tests from its own lane
+static_assert(RW_CAP == 32, "the own-lane flags fill one 32-bit word: sixteen dwords of two slots");
+constexpr uint32_t RW_NONE = 0x7FFFu;        // lasth: no head of the symbol in the tile yet; nx: no later head of the symbol so far
 
 __global__ __launch_bounds__(TB) void k_enc_mtf(const uint8_t *__restrict__ in, EncDims d, const uint32_t *__restrict__ tilebase,
                                                const int32_t *__restrict__ prevlast, const uint32_t *__restrict__ bstart,
                                                uint8_t *__restrict__ ranks)
 {
-    struct WaveLds {                       // one per wave; neighbours in one struct so that pairs of accesses share an address register
+    struct WaveLds {                       // one per wave
+        uint16_t nx[RW_CAP + ATILE + 64];  // N(j) of the tile's heads, as far as the groups walked so far know it; RW_CAP slots in front
+        uint16_t lasth[256];               // the last head of every symbol in the tile so far
         uint32_t pos[256];                 // next write position of every symbol's bucket
-        uint32_t dst[64], rk[64];          // (bucket position, rank) of the heads of the group in flight
-        uint32_t lst[256];                 // the list at the start of the tile, while it is built
     };
     __shared__ WaveLds s_w[TB / 64];
     const uint32_t c = chunk_of(d, blockIdx.y);
@@ -116,105 +126,124 @@ __global__ __launch_bounds__(TB) void k_enc_mtf(const uint8_t *__restrict__ in, 
     const uint32_t t = blockIdx.x * (TB / 64) + (uint32_t)w;
     const uint32_t clen = chunk_len(d, c), ts = t * ATILE;
     if (ts >= clen) return;
-    const int l = lane_id();
+    const uint32_t l = (uint32_t)lane_id();
+    const uint64_t lt = lanemask_lt();
     const size_t o = ((size_t)c * d.tpc + t) * 256;
-    const int32_t last0 = prevlast[o + l], last1 = prevlast[o + 64 + l], last2 = prevlast[o + 128 + l], last3 = prevlast[o + 192 + l];
+    int32_t last0 = prevlast[o + l], last1 = prevlast[o + 64 + l], last2 = prevlast[o + 128 + l], last3 = prevlast[o + 192 + l];
     const uint32_t *bs = bstart + (size_t)c * 256;
     WaveLds &L = s_w[w];
     const uint8_t *src = in + (size_t)c * d.chunk;
     uint8_t *dst = ranks + (size_t)c * d.chunk;
     const uint32_t te = (ts + ATILE < clen) ? ts + ATILE : clen;
-    uint32_t bn = ((uint32_t)l < te - ts) ? src[ts + l] : 0x100u;             // group in flight
+    uint32_t bn = (l < te - ts) ? src[ts + l] : 0x100u;                       // group in flight
 #pragma unroll
     for (int qq = 0; qq < 4; qq++) {
         L.pos[qq * 64 + l] = bs[qq * 64 + l] + tilebase[o + qq * 64 + l];
-        L.lst[qq * 64 + l] = 0xFFFFu;
+        L.lasth[qq * 64 + l] = (uint16_t)RW_NONE;
     }
-    // the list before the tile: every symbol seen so far goes to position #{symbols with a later stamp} (stamps are positions: distinct)
-    uint32_t nseen = 0;
-#define JPK_MTF_PLACE(LASTJ, J)                                                                                                   \
-    {                                                                                                                             \
-        uint64_t sm = __ballot(LASTJ >= 0);                                                                                       \
-        nseen += (uint32_t)__popcll(sm);                                                                                          \
-        while (sm) {                                                                                                              \
-            const uint32_t ln = (uint32_t)__builtin_ctzll(sm);                                                                    \
-            sm &= sm - 1;                                                                                                         \
-            const int32_t own = __builtin_amdgcn_readlane(LASTJ, (int)ln);                                                        \
-            const uint32_t at = (uint32_t)__popcll(__ballot(last0 > own)) + (uint32_t)__popcll(__ballot(last1 > own)) +           \
-                                (uint32_t)__popcll(__ballot(last2 > own)) + (uint32_t)__popcll(__ballot(last3 > own));            \
-            L.lst[at] = (uint32_t)(J) * 64u + ln;                              /* every lane stores the same value */              \
-        }                                                                                                                         \
-    }
-    JPK_MTF_PLACE(last0, 0)
-    JPK_MTF_PLACE(last1, 1)
-    JPK_MTF_PLACE(last2, 2)
-    JPK_MTF_PLACE(last3, 3)
-#undef JPK_MTF_PLACE
-    uint32_t lst0 = L.lst[l], lst1 = L.lst[64 + l], lst2 = L.lst[128 + l], lst3 = L.lst[192 + l];
     uint32_t prevc = 256;                                                     // no byte before the tile: its first byte is a head
+    uint32_t hb = 0;                                                          // heads of the tile before the group
+    uint32_t nfirst = 0;                                                      // first heads so far = distinct symbols of the tile so far
     for (uint32_t i0 = ts; i0 < te; i0 += 64) {
         const uint32_t nvalid = (te - i0 < 64u) ? te - i0 : 64u;
         const uint32_t b = bn;
-        if (i0 + 64 < te) bn = (i0 + 64 + (uint32_t)l < te) ? src[i0 + 64 + l] : 0x100u;      // next group, loaded under this one's walk
+        if (i0 + 64 < te) bn = (i0 + 64 + l < te) ? src[i0 + 64 + l] : 0x100u;                // next group, loaded under this one's work
+        const bool valid = l < nvalid;
+        const uint32_t sy = valid ? b : 0u;                                   // a table index for every lane
         // byte before mine (lane 0: the last byte of the previous group)
-        uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp((int)prevc, (int)b, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-        uint64_t rem = __ballot((uint32_t)l < nvalid && (b != pb || l == 0));     // lane 0 is always walked: a repeat gets rank 0 there
-        const uint64_t heads = rem;
-        // length of the run that starts at my lane (used by head lanes only): distance to the next head, or to the end of the group
-        const uint64_t above = (heads >> 1) >> l;
-        const uint32_t runlen = above ? (uint32_t)__builtin_ctzll(above) + 1u : nvalid - (uint32_t)l;
-        while (rem) {
-            const uint32_t k = (uint32_t)__builtin_ctzll(rem);
-            rem &= rem - 1;
-            const uint32_t cc = (uint32_t)__builtin_amdgcn_readlane((int)b, (int)k);
-            const uint32_t run = (uint32_t)__builtin_amdgcn_readlane((int)runlen, (int)k);
-            const uint32_t dpos = L.pos[cc];
-            const uint64_t m0 = __ballot(lst0 == cc);
-            uint32_t rank;
-            if (m0) {                                          // among the first 64: the common case
-                rank = (uint32_t)__builtin_ctzll(m0);
-            } else {                                           // search the rest; shift the registers behind the first here
-                const uint64_t m1 = __ballot(lst1 == cc), m2 = __ballot(lst2 == cc), m3 = __ballot(lst3 == cc);
-                if (m1) rank = 64u + (uint32_t)__builtin_ctzll(m1);
-                else if (m2) rank = 128u + (uint32_t)__builtin_ctzll(m2);
-                else if (m3) rank = 192u + (uint32_t)__builtin_ctzll(m3);
-                else rank = nseen++;                           // first occurrence in the chunk: enters from the first free position
-                const uint32_t j = rank >> 6, q = rank & 63u;
-                const bool part = (uint32_t)l <= q;            // lanes that move in the register holding the position
-                if (j >= 1) {
-                    const uint32_t c1 = (uint32_t)__builtin_amdgcn_readlane((int)lst0, 63);
-                    if (j == 1) {
-                        const uint32_t sh = mtf_shr1(c1, lst1);
-                        lst1 = part ? sh : lst1;
-                    } else {
-                        const uint32_t c2 = (uint32_t)__builtin_amdgcn_readlane((int)lst1, 63);
-                        lst1 = mtf_shr1(c1, lst1);
-                        if (j == 2) {
-                            const uint32_t sh = mtf_shr1(c2, lst2);
-                            lst2 = part ? sh : lst2;
-                        } else {
-                            const uint32_t c3 = (uint32_t)__builtin_amdgcn_readlane((int)lst2, 63);
-                            lst2 = mtf_shr1(c2, lst2);
-                            const uint32_t sh = mtf_shr1(c3, lst3);
-                            lst3 = part ? sh : lst3;
-                        }
-                    }
-                }
+        const uint32_t pb = (uint32_t)__builtin_amdgcn_update_dpp((int)prevc, (int)b, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        const uint64_t heads = __ballot(valid && b != pb);
+        const bool ishead = (heads >> l) & 1ull;
+        const uint64_t m = match_any8(b, valid);                              // the group's bytes equal to mine
+        const uint32_t p0 = L.pos[sy], lh = L.lasth[sy];                      // both tables as they stand in front of the group
+        // bucket position of every byte, head or repeat: the bytes of its symbol before it
+        const uint32_t dp = p0 + (uint32_t)__popcll(m & lt);
+        if (valid && ((m >> l) >> 1) == 0ull) L.pos[sy] = dp + 1u;            // the last lane of each set
+        // head index, and the previous head of the symbol: in the group, else in the table
+        const uint32_t k = hb + (uint32_t)__popcll(heads & lt);
+        const uint64_t mh = m & heads;
+        const uint64_t below = mh & lt;
+        const uint32_t top = 63u - (uint32_t)__clzll((long long)(below | 1ull));              // (lane 0 when there is none: not used then)
+        const int32_t pin = (int32_t)(hb + (uint32_t)__popcll(heads & ((1ull << top) - 1ull)));
+        const int32_t ptab = (lh == RW_NONE) ? -1 : (int32_t)lh;
+        const int32_t P = below ? pin : ptab;
+        if (ishead && ((mh >> l) >> 1) == 0ull) L.lasth[sy] = (uint16_t)k;    // the symbol's last head of the group
+        uint16_t *const nx = L.nx + RW_CAP;                                   // nx[j], j >= -RW_CAP
+        if (ishead) nx[k] = (uint16_t)RW_NONE;
+        if (ishead && P >= 0) nx[P] = (uint16_t)k;
+        // the window (Pw, k): empty for repeats and for first heads, which are counted below
+        const int32_t Pw = (ishead && P >= 0) ? P : (int32_t)k;
+        // own lane: positions k - 1 .. k - RW_CAP, all read (one address, 64 bytes), those inside the window counted.
+        // Two slots a dword, compared in one subtraction: every slot and k are below 0x8000, so (slot | 0x8000) - k keeps bit 15 exactly
+        // where slot >= k and never borrows from the half above.  Dword i's two flags go to bits 15 - i and 31 - i (a rotate and a
+        // bit-field insert): four instructions per pair of positions.  Slot e = 0 .. RW_CAP - 1 of the read is position k - RW_CAP + e.
+        uint32_t ge = 0;
+        {
+            uint32_t wd[RW_CAP / 2];
+            __builtin_memcpy(wd, L.nx + k, RW_CAP * 2);                       // L.nx + k = nx + (k - RW_CAP); 2-byte aligned
+            const uint32_t kk = k | (k << 16);
+#pragma unroll
+            for (int i = 0; i < RW_CAP / 2; i++) {
+                const uint32_t dd = (wd[i] | 0x80008000u) - kk;
+                const uint32_t at = 0x80008000u >> i;
+                ge = (__builtin_rotateright32(dd, (unsigned)i) & at) | (ge & ~at);
             }
-            {                                                  // first register: positions 0 .. min(rank, 63) move down, the symbol enters at 0
-                const uint32_t sh = mtf_shr1(cc, lst0);
-                lst0 = ((uint32_t)l <= rank) ? sh : lst0;
-            }
-            L.pos[cc] = dpos + run;
-            L.dst[k] = dpos;
-            L.rk[k] = rank;
         }
+        const uint32_t wl = k - (uint32_t)Pw;                                 // positions k - 1 .. k - (wl - 1); 0: no window
+        const uint32_t nown = (wl == 0u) ? 0u : (wl - 1u < (uint32_t)RW_CAP ? wl - 1u : (uint32_t)RW_CAP);
+        const uint32_t e0 = (uint32_t)RW_CAP - nown;                          // slots e0 .. RW_CAP - 1 lie inside the window
+        const uint32_t inwin = ((1u << (16u - ((e0 + 1u) >> 1))) - 1u) | (((1u << (16u - (e0 >> 1))) - 1u) << 16);
+        uint32_t cnt = (uint32_t)__popc(ge & inwin);
+        // the rest of a longer window: the wave, 64 positions a step; two heads at a time, so that their first reads overlap
+        uint64_t lng = __ballot(wl > (uint32_t)RW_CAP + 1u);
+        while (lng) {
+            const uint32_t la = (uint32_t)__builtin_ctzll(lng);
+            lng &= lng - 1;
+            const bool two = lng != 0ull;
+            const uint32_t lb = two ? (uint32_t)__builtin_ctzll(lng) : la;
+            lng &= lng - 1;
+            const uint32_t ka = (uint32_t)__builtin_amdgcn_readlane((int)k, (int)la), kb = (uint32_t)__builtin_amdgcn_readlane((int)k, (int)lb);
+            const uint32_t ja = (uint32_t)__builtin_amdgcn_readlane(Pw, (int)la) + 1u, jb = (uint32_t)__builtin_amdgcn_readlane(Pw, (int)lb) + 1u;
+            const uint32_t ha = ka - (uint32_t)RW_CAP, hbb = kb - (uint32_t)RW_CAP;            // positions [P + 1, k - RW_CAP) are left
+            const uint32_t va = nx[ja + l], vb = nx[jb + l];                  // index < ATILE + 63: inside nx
+            uint32_t sa = (uint32_t)__popcll(__ballot((ja + l < ha) & (va >= ka)));
+            uint32_t sb = (uint32_t)__popcll(__ballot((jb + l < hbb) & (vb >= kb)));
+            for (uint32_t j0 = ja + 64; j0 < ha; j0 += 64) {
+                const uint32_t v = nx[j0 + l];
+                sa += (uint32_t)__popcll(__ballot((j0 + l < ha) & (v >= ka)));
+            }
+            for (uint32_t j0 = jb + 64; j0 < hbb; j0 += 64) {
+                const uint32_t v = nx[j0 + l];
+                sb += (uint32_t)__popcll(__ballot((j0 + l < hbb) & (v >= kb)));
+            }
+            cnt += (l == la) ? sa : 0u;
+            cnt += (two && l == lb) ? sb : 0u;
+        }
+        uint64_t fh = __ballot(ishead && P < 0);
+        while (fh) {                                                          // first heads, in order
+            const uint32_t ln = (uint32_t)__builtin_ctzll(fh);
+            fh &= fh - 1;
+            const uint32_t cc = (uint32_t)__builtin_amdgcn_readlane((int)b, (int)ln);
+            const int q = (int)(cc & 63u);
+            int32_t own;
+            if (cc < 64u) own = __builtin_amdgcn_readlane(last0, q);
+            else if (cc < 128u) own = __builtin_amdgcn_readlane(last1, q);
+            else if (cc < 192u) own = __builtin_amdgcn_readlane(last2, q);
+            else own = __builtin_amdgcn_readlane(last3, q);
+            // stamps are positions (distinct), -1 = not seen in the chunk, -2 = has a head in this tile: own >= -1
+            const uint32_t carried = (uint32_t)__popcll(__ballot(last0 > own)) + (uint32_t)__popcll(__ballot(last1 > own)) +
+                                     (uint32_t)__popcll(__ballot(last2 > own)) + (uint32_t)__popcll(__ballot(last3 > own));
+            cnt = (l == ln) ? nfirst + carried : cnt;
+            nfirst++;
+            const uint32_t me = cc - l;
+            last0 = (me == 0u) ? -2 : last0;
+            last1 = (me == 64u) ? -2 : last1;
+            last2 = (me == 128u) ? -2 : last2;
+            last3 = (me == 192u) ? -2 : last3;
+        }
+        if (valid) dst[dp] = ishead ? (uint8_t)cnt : (uint8_t)0;
+        hb += (uint32_t)__popcll(heads);
         prevc = (uint32_t)__builtin_amdgcn_readlane((int)b, (int)(nvalid - 1u));
-        if ((uint32_t)l < nvalid) {
-            const uint32_t hl = 63u - (uint32_t)__builtin_clzll(heads & ((2ull << l) - 1ull));     // my head (bit 0 is always set)
-            const uint32_t dp = L.dst[hl] + ((uint32_t)l - hl);
-            dst[dp] = ((uint32_t)l == hl) ? (uint8_t)L.rk[hl] : (uint8_t)0;
-        }
     }
 }
 
